@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("workload", ["cfg2", "cfg3"])
 def test_bench_json_contract(workload):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--workload", workload,
-                          "--cell-n", "202", "--points", "40000", "--cpu-points", "5000"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--cell-n", "202", "--points", "40000", "--cpu-points", "5000", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, "stdout must hold ONE JSON line, got: %r" % lines
@@ -46,7 +46,7 @@ def test_bench_gpus_n_launches_its_own_ranks(world, C, N):
     tests/_torch_strips.py); with N devices the library's own RCCL path runs."""
     env = dict(os.environ, EMAP_BENCH_SUB_SIZES="cfg5:1024:300000,cfg4:1024:300000"); env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "1", "--cell-n", str(C),
-                          "--points", str(N), "--cpu-points", "5000", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
+                          "--points", str(N), "--cpu-points", "5000", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -62,7 +62,7 @@ def test_sharded_default_line_carries_cfg5_and_cfg4_next_to_their_n1_times():
     Sub-measurement sizes shrunk through the test hook; the code path is the one `bench.py --gpus 8` runs."""
     env = dict(os.environ, EMAP_BENCH_SUB_SIZES="cfg5:1024:300000,cfg4:1024:300000", EMAP_BENCH_BUCKET="force")      # (the bucketed-cloud code path of N > 1, on one rank)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-sharded", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-sharded", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -80,3 +80,22 @@ def test_sharded_default_line_carries_cfg5_and_cfg4_next_to_their_n1_times():
     assert sv["speedup_vs_n1"] == d["config"]["cfg5"]["speedup_vs_n1"] and sv["rccl_ranks"] == 1 and sv["n_gpus"] == 1
     assert d["config"]["cfg4"]["rays"] in ("by row", "by ray over an all-reduced window")
     assert d["config"]["cfg4"]["stage_ms_rank0"]["rays"] > 0
+
+
+def test_plain_line_times_exactly_its_steps_and_dumps_the_timed_map(tmp_path):
+    """without --full the line holds the headline figure alone; --dump-outputs writes the planes of the timed map after its last frame
+    (float32), and two runs with the same arguments start from the same seeded clouds"""
+    d = str(tmp_path / "out")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--cell-n", "202",
+                          "--points", "40000", "--dump-outputs", d], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    r = json.loads(lines[0])
+    assert r["steps"] == 7 and r["warmup"] == 2 and r["ms_per_step"] > 0 and r["value"] > 0 and r["unit"] == "Mpoints/s"
+    assert r["roofline"] is None and r["cpu_baseline"] is None and "cfg3" not in r["config"]
+    assert abs(r["value"] - 40000 / (r["ms_per_step"] * 1e3)) <= 0.01 * r["value"] + 0.01      # value and ms_per_step describe the same steps
+    import numpy as np
+    em, nm = np.load(os.path.join(d, "elevation_map.npy")), np.load(os.path.join(d, "normal_map.npy"))
+    assert em.dtype == np.float32 and em.shape == (7, 202, 202) and nm.dtype == np.float32 and nm.shape == (3, 202, 202)
+    assert (em[2] > 0.5).sum() > 1000 and np.isfinite(em[0][em[2] > 0.5]).all()

@@ -20,7 +20,7 @@ def _run(cmd, env=None):
 
 
 def test_self_launch_prints_one_json_line_with_the_ranks_that_ran():
-    out = _run([sys.executable, "bench.py", "--gpus", "3", "--dry-run"])
+    out = _run([sys.executable, "bench.py", "--gpus", "3", "--dry-run", "--full"])
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1

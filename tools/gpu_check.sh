@@ -2,8 +2,8 @@
 O=gpurun_out/${1:-check}; mkdir -p $O
 (time python -m pytest tests -m gpu -x -q) > $O/pytest.log 2>&1
 grep -E "passed|failed" $O/pytest.log
-python bench.py --no-cpu-baseline > $O/cfg2.json 2>> $O/err.log
-python bench.py --workload cfg3 --steps 20 --no-cpu-baseline > $O/cfg3.json 2>> $O/err.log
+python bench.py --full --no-cpu-baseline > $O/cfg2.json 2>> $O/err.log
+python bench.py --full --workload cfg3 --steps 20 --no-cpu-baseline > $O/cfg3.json 2>> $O/err.log
 python - <<PY
 import json
 for w in ("cfg2", "cfg3"):

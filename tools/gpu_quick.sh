@@ -5,8 +5,8 @@ DESEL="--deselect tests/test_hip_large_maps.py"; [ "${LARGE:-0}" = 1 ] && DESEL=
 (time python -m pytest tests -m gpu -q -x $DESEL ${K:+-k "$K"}) > $O/pytest.log 2>&1
 tail -5 $O/pytest.log | grep -E "passed|failed|error"
 grep -E "^(FAILED|ERROR)|^E  " $O/pytest.log | head -30
-python bench.py --no-cpu-baseline > $O/cfg2.json 2>> $O/err.log
-[ "${CFG5:-0}" = 1 ] && timeout 600 python bench.py --workload cfg5 --steps 10 --warmup 2 --no-cpu-baseline > $O/cfg5.json 2>> $O/err.log
+python bench.py --full --no-cpu-baseline > $O/cfg2.json 2>> $O/err.log
+[ "${CFG5:-0}" = 1 ] && timeout 600 python bench.py --full --workload cfg5 --steps 10 --warmup 2 --no-cpu-baseline > $O/cfg5.json 2>> $O/err.log
 python - <<PY
 import json, os
 for w in ("cfg2", "cfg5"):

@@ -3,11 +3,11 @@
 TAG=${1:-pq}; WL=${2:-cfg2}; shift; shift
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/${WL}_trace -- python $R/bench.py --workload $WL --steps 6 --warmup 2 --no-cpu-baseline --no-cfg3 --no-large "$@" > $O/${WL}_trace.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/${WL}_trace -- python $R/bench.py --full --workload $WL --steps 6 --warmup 2 --no-cpu-baseline --no-cfg3 --no-large "$@" > $O/${WL}_trace.log 2>&1
 python $R/tools/rocprof_summary.py $(ls $O/${WL}_trace/*/*_results.db | head -1) > $O/${WL}_stats.txt
 head -14 $O/${WL}_stats.txt | cut -c1-150
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c -d $O/${WL}_pmc_$c -- python $R/bench.py --workload $WL --steps 4 --warmup 2 --no-cpu-baseline --no-cfg3 --no-large "$@" > $O/${WL}_pmc_$c.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c -d $O/${WL}_pmc_$c -- python $R/bench.py --full --workload $WL --steps 4 --warmup 2 --no-cpu-baseline --no-cfg3 --no-large "$@" > $O/${WL}_pmc_$c.log 2>&1
 done
 python $R/tools/pmc_to_json.py $(ls $O/${WL}_pmc_FETCH_SIZE/*/*_results.db | head -1) $(ls $O/${WL}_pmc_WRITE_SIZE/*/*_results.db | head -1) > $O/${WL}_pmc.json
 python - <<PY
