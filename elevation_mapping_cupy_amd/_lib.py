@@ -60,7 +60,7 @@ SYMBOLS = [
     "emap_local_drift_sums", "emap_set_scatter_mode", "emap_fuse", "emap_fuse_average", "emap_commit", "emap_rays", "emap_average", "emap_overlap_clear",
     "emap_dilate", "emap_traversability_normals", "emap_post", "emap_post_part", "emap_update_variance", "emap_update_time", "emap_get_stats",
     "emap_get_layer", "emap_set_layer", "emap_publish_layer", "emap_shift", "emap_strip_logical_begin", "emap_semantic_configure", "emap_semantic_update", "emap_frame_semantics",
-    "emap_semantic_get_layer", "emap_semantic_set_layer", "emap_semantic_clear", "emap_semantic_get_alpha", "emap_semantic_set_alpha", "emap_semantic_class_max", "emap_semantic_accumulate", "emap_semantic_finalize", "emap_min_filter", "emap_max_filter", "emap_smooth_filter", "emap_erode", "emap_inpaint_u8", "emap_inpaint_telea_u8", "emap_inpaint_ns_u8", "emap_image_correspondence", "emap_image_get_correspondence",
+    "emap_semantic_get_layer", "emap_semantic_set_layer", "emap_semantic_clear", "emap_semantic_get_alpha", "emap_semantic_set_alpha", "emap_semantic_class_max", "emap_semantic_accumulate", "emap_semantic_finalize", "emap_min_filter", "emap_max_filter", "emap_smooth_filter", "emap_erode", "emap_inpaint_u8", "emap_inpaint_telea_u8", "emap_inpaint_ns_u8", "emap_inpainter_create", "emap_inpainter_destroy", "emap_inpainter_set_steps", "emap_inpaint_telea_fronts_u8", "emap_image_correspondence", "emap_image_get_correspondence",
     "emap_image_fuse", "emap_image_set_tolerance", "emap_image_fuse_arrays", "emap_polygon_mask", "emap_dilate_planes", "emap_halo_bytes", "emap_halo_pack", "emap_halo_unpack", "emap_normal_row_lag", "emap_normal_halo_pack", "emap_normal_halo_unpack", "emap_normal_lag_plan",
     "emap_comm_unique_id", "emap_comm_init", "emap_comm_destroy", "emap_comm_selftest", "emap_comm_count", "emap_comm_wire_bytes", "emap_comm_allreduce_host", "emap_comm_gather_layer", "emap_update_sharded", "emap_set_ray_mode",
     "emap_timer_begin", "emap_timer_end", "emap_enable_stage_timing", "emap_get_stage_times", "emap_last_update_path", "emap_small_frame_aborts",
@@ -96,6 +96,12 @@ def load():
             except AttributeError:
                 if not os.environ.get("EMAP_HIP_LIB"):      # an older build handed in for an A/B run may lack newer entry points
                     raise
+    if hasattr(lib, "emap_inpaint_telea_fronts_u8"):      # (pointer arguments: a handle must not be truncated to an int)
+        u8p = ct.POINTER(ct.c_uint8)
+        lib.emap_inpainter_create.argtypes = [ct.c_int32, ct.c_void_p, ct.POINTER(ct.c_void_p)]
+        lib.emap_inpainter_destroy.argtypes = [ct.c_void_p]
+        lib.emap_inpainter_set_steps.argtypes = [ct.c_void_p, ct.c_int32]
+        lib.emap_inpaint_telea_fronts_u8.argtypes = [ct.c_void_p, u8p, u8p, ct.c_int32, ct.c_int32, ct.c_int32, u8p, ct.POINTER(ct.c_int32)]
     got = int(lib.emap_abi_version())
     if got != ABI_VERSION and not os.environ.get("EMAP_HIP_LIB"):
         raise EmapError("%s speaks ABI version %d, this binding expects %d (include/emap_hip.h: EMAP_ABI_VERSION) -- rebuild with "

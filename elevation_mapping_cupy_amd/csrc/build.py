@@ -1,4 +1,4 @@
-"""Builds libemap_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: five translation units, compiled in parallel into
+"""Builds libemap_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: seven translation units, compiled in parallel into
 csrc/_obj/*.o (only the stale ones) and linked."""
 from __future__ import annotations
 
@@ -10,7 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(os.path.dirname(HERE), "libemap_hip.so")
 OBJ = os.path.join(HERE, "_obj")
-SOURCES = ["emap_kernels.hip", "emap_binned.hip", "emap_semantic.hip", "emap_api.hip", "emap_inpaint_host.hip", "emap_inpaint_ns.cpp"]      # (.cpp: host-only C++)
+SOURCES = ["emap_kernels.hip", "emap_binned.hip", "emap_semantic.hip", "emap_api.hip", "emap_inpaint_host.hip", "emap_inpaint_ns.cpp", "emap_inpaint_fronts.hip"]      # (.cpp: host-only C++)
 HEADERS = ["emap_device.h", os.path.join("..", "..", "include", "emap_hip.h")]
 DEPS = SOURCES + HEADERS
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-gpu-rdc",

@@ -160,6 +160,7 @@ class ElevationMap:
             raise EmapError("emap_create failed with status %d (no usable HIP device / invalid parameters); "
                             "the MI355X backend has no CPU fallback" % rc)
         self._params_struct = P
+        self.stream = int(stream or 0)           # (device-side plugins that keep handles of their own enqueue on the same stream)
         self.traversability_buffer = np.full((self.rows, self.cell_n), np.nan, np.float32)
 
         # managers are optional layers on top of the hot path (built lazily; see semantic_map / plugins)

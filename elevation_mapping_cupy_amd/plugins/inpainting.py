@@ -11,6 +11,12 @@ Same semantics around the fill as the reference: mask = ``is_valid < 0.5``, the 
   line-by-line restatement and checks the properties every implementation must have).
 * ``method="front"``: the round-1/2 device-side substitute (``emap_inpaint_u8``: front-by-front distance-weighted mean of the known
   8-neighbours on the MI355X) for maps where a host pass per publish is too slow; needs the owning ElevationMap.
+* ``method="telea_fronts"``: Telea's estimator ON THE MI355X (``emap_inpaint_telea_fronts_u8``, csrc/emap_inpaint_fronts.hip): the
+  arithmetic of the host ``"telea"`` with radius 1, scheduled by fronts of the L1 distance to the known cells (every cell of a front at
+  once) instead of by the serial priority queue -- exactly specified and deterministic, not bit-identical to ``"telea"`` (DESIGN.md §8:
+  agreement figures).  Same quantisation around the fill as ``"telea"``.  Its handle is created on first use on the owning
+  ElevationMap's device and stream (the manager injects ``emap``), else on the current device's null stream.  The reference has no
+  such name and falls back to telea for it (reference plugins/inpainting.py:26-31), so a YAML naming it runs on both.
 * ``method="ns"`` (``cv2.INPAINT_NS``, reference plugins/inpainting.py:33-38): the Navier-Stokes based method in its fast-marching form,
   HOST code as well (``emap_inpaint_ns_u8``): the same march as Telea's, a pixel = the mean of the known pixels within the radius
   weighted along the isophote direction.  Parity with OpenCV's values unpinned like "telea" (tests/test_inpaint_ns.py)."""
@@ -29,10 +35,12 @@ from .plugin_manager import PluginBase
 class Inpainting(PluginBase):
     def __init__(self, cell_n: int = 100, method: str = "telea", emap=None, **kwargs):
         super().__init__()
-        self.method = method if method in ("telea", "ns", "front") else "telea"      # (the reference falls back to telea for unknown names, :37-38)
+        self.method = method if method in ("telea", "ns", "front", "telea_fronts") else "telea"      # (the reference falls back to telea for unknown names, :37-38)
         self.cell_n = cell_n
         self.emap = emap
         self.sweeps_run = 0
+        self.fronts_run = 0
+        self._ip = None                            # emap_inpainter of method "telea_fronts" (created on first use)
 
     def __call__(self, elevation_map: np.ndarray, layer_names: List[str], plugin_layers: np.ndarray,
                  plugin_layer_names: List[str], *args) -> np.ndarray:
@@ -43,13 +51,19 @@ class Inpainting(PluginBase):
         h_max, h_min = float(h[known].max()), float(h[known].min())
         span = (h_max - h_min) if h_max > h_min else 1.0
         q8 = np.clip((h - h_min) * 255 / span, 0, 255).astype(np.uint8)            # 8-bit image, truncation like astype("uint8")
-        if self.method in ("telea", "ns"):
+        if self.method in ("telea", "ns", "telea_fronts"):
             lib = _lib.load()
             mask = np.ascontiguousarray(~known, np.uint8)
             out8 = np.empty_like(q8)
             p = lambda a: a.ctypes.data_as(ct.POINTER(ct.c_uint8))               # noqa: E731
-            fill = lib.emap_inpaint_telea_u8 if self.method == "telea" else lib.emap_inpaint_ns_u8
-            rc = fill(p(np.ascontiguousarray(q8)), p(mask), q8.shape[0], q8.shape[1], 1, p(out8))
+            if self.method == "telea_fronts":
+                n = ct.c_int32(0)
+                rc = lib.emap_inpaint_telea_fronts_u8(self._inpainter(lib), p(np.ascontiguousarray(q8)), p(mask), q8.shape[0], q8.shape[1], 1,
+                                                      p(out8), ct.byref(n))
+                self.fronts_run = n.value
+            else:
+                fill = lib.emap_inpaint_telea_u8 if self.method == "telea" else lib.emap_inpaint_ns_u8
+                rc = fill(p(np.ascontiguousarray(q8)), p(mask), q8.shape[0], q8.shape[1], 1, p(out8))
             if rc != 0:
                 raise _lib.EmapError("emap_inpaint_%s_u8 failed (%d)" % (self.method, rc))
             out = out8.astype(np.float32)
@@ -64,3 +78,30 @@ class Inpainting(PluginBase):
                                           int(2 * self.cell_n), f32p(out), ct.byref(n)))
             self.sweeps_run = n.value
         return (out * np.float32(span) / np.float32(255) + np.float32(h_min)).astype(np.float64)
+
+    def _inpainter(self, lib):
+        if self._ip is None:
+            if self.emap is not None:
+                device, stream = int(self.emap.param.device), int(getattr(self.emap, "stream", 0) or 0)
+            else:
+                device, stream = -1, 0                  # (-1: the current device)
+            h = ct.c_void_p()
+            rc = lib.emap_inpainter_create(device, ct.c_void_p(stream or None), ct.byref(h))
+            if rc != 0:
+                raise _lib.EmapError("emap_inpainter_create failed (%d): no usable HIP device %d" % (rc, device))
+            self._ip = h
+        return self._ip
+
+    def close(self):
+        """Free the device scratch of method "telea_fronts" (a later call creates it again).  The inpainter enqueues on the owning
+        ElevationMap's stream only while a call runs, and destroying it does not touch that stream, so closing after the stream is
+        gone is safe; a call after the stream is gone is not."""
+        ip, self._ip = getattr(self, "_ip", None), None
+        if ip is not None and ip.value:
+            _lib.load().emap_inpainter_destroy(ip)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

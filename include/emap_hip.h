@@ -258,6 +258,25 @@ int emap_inpaint_telea_u8(const uint8_t* image, const uint8_t* mask, int32_t row
    emap_inpaint_telea_u8; images of fewer than 2 x 2 pixels are rejected (EMAP_ERR_INVALID).  Parity with OpenCV's values is NOT pinned
    (OpenCV absent offline); pinned against oracle/ns_inpaint.py. */
 int emap_inpaint_ns_u8(const uint8_t* image, const uint8_t* mask, int32_t rows, int32_t cols, int32_t radius, uint8_t* out);
+/* Inpainting plugin, method "telea_fronts": Telea's estimator ON THE GPU, scheduled by fronts (csrc/emap_inpaint_fronts.hip, DESIGN.md
+ * §8).  d(p) = L1 distance from p to the nearest pixel with mask == 0; fronts k = 1 .. max d are filled in order, every pixel of front k
+ * at once, with the float32 arithmetic of emap_inpaint_telea_u8 (radius 1) in which "known" means d(q) < k (the 1-pixel frame around
+ * the image counts as known), pixels with d >= k read as T = 1e6 with their input value, and a known pixel 4-adjacent to the hole starts
+ * at T = -0.0f.  Deterministic and exactly specified (tests/_telea_fronts.py restates it); NOT equal to the serial host march, whose
+ * order is that of a priority queue (agreement measured in tests/test_inpaint_fronts.py).  HOST arrays in and out, like
+ * emap_inpaint_telea_u8; known pixels are returned unchanged; no known pixel or nothing to fill: out = image, *fronts_run = 0.
+ * Otherwise *fronts_run (may be NULL) = max d.  radius != 1, images of fewer than 2 x 2 pixels, NULL pointers: EMAP_ERR_INVALID.
+ * An inpainter is created on `device` (-1: the calling thread's current device) and enqueues on `stream` (a hipStream_t, NULL = the null stream); it keeps its device scratch,
+ * grown to the largest image seen, until destroyed.  Calls on one inpainter are serialised by the caller; each call returns after
+ * the stream has delivered `out`.  The stream is the caller's: it is used only inside emap_inpaint_telea_fronts_u8 and must be valid
+ * during each such call; emap_inpainter_destroy does not touch it.  emap_inpainter_set_steps: fronts advanced per launch (1 .. 16,
+ * default 16; results do not depend on it). */
+typedef struct emap_inpainter emap_inpainter;
+int emap_inpainter_create(int32_t device, void* stream, emap_inpainter** out);
+int emap_inpainter_destroy(emap_inpainter* ip);
+int emap_inpainter_set_steps(emap_inpainter* ip, int32_t steps);
+int emap_inpaint_telea_fronts_u8(emap_inpainter* ip, const uint8_t* image, const uint8_t* mask, int32_t rows, int32_t cols,
+                                 int32_t radius, uint8_t* out, int32_t* fronts_run);
 
 /* ---- camera path: ElevationMap.input_image (EM/elevation_mapping.py:468-562).
  * emap_image_correspondence = image_to_map_correspondence_kernel (EM/kernels/custom_image_kernels.py:9-157): x1, y1 = camera
