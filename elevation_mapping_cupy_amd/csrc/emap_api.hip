@@ -147,7 +147,6 @@ struct emap_ctx {
   unsigned int* inl_plane;         // newmap[3] of frames whose tile kernel commits itself (binned path + visibility pass), on demand
   float* ray_thr;                  // same frames: per 8 x 8 block height at or above which a ray sample cannot affect any cell of the block
   bool inert_zero;                 // the bitmap is all zero (k_ray_apply leaves it so; k_commit overwrites it)
-  bool rays_fused;                 // this frame: the tile kernel committed + averaged, k_ray_apply follows the rays
   // tile-binned scatter buffers (allocated on demand)
   int scatter_mode;                // 0 auto, 1 atomic, 2 binned
   int force_sub;                   // test hook: minimum bin height factor (emap_set_scatter_mode bits 8..15)
@@ -158,17 +157,14 @@ struct emap_ctx {
   void* sem_split_mem;             // scratch of the split semantic tile kernel (SemSplit), zero between launches
   volatile unsigned int* split_need;   // host-mapped word: the parts the last scan the device has finished would have listed
   bool split_dirty;                // k_tile_count has filled slots that no k_tile_fuse has cleared yet
-  GateFold gate_fold;              // multi-GPU frames: gate decision on the all-reduced totals folded into the tile kernel (mode 0: k_gate ran)
-  OverlapArgs ov_args;             // clear_overlap_map folded into the frame's rewriting kernels (on = 0: separate k_overlap launch)
-  bool fold_gate, gate_folded;     // emap_update on the atomic path: the gate rides in k_count's last workgroup (cnt_sync: its ticket words)
-  unsigned int* cnt_sync;
+  unsigned int* cnt_sync;          // ticket words of k_count's folded gate (Frame::fold_gate)
   // robot scale: count -> gate -> fuse -> commit + average in one launch (k_small_frame): its barriers' release words live behind the
   // ticket words of cnt_sync.  A launch whose grid barrier is ABORTED leaves map, accumulators and drift record exactly as it found
   // them, and the launches queued behind it do nothing (device-side poison word).  sf_host = two host-mapped words: [0] epoch of the
   // last launch that will be applied, [1] epoch of the first aborted launch.  The frames issued and not yet known to be applied wait
   // in sf_ring with everything needed to run them again; sf_settle (every entry point but the ones that only bind a cloud) learns
   // their fate and, after an abort, re-runs them in order on the chain of launches.
-  unsigned int sf_epoch; volatile unsigned int* sf_host; unsigned int* sf_host_dev; unsigned int* sf_poison; bool sf_off;
+  unsigned int sf_epoch; volatile unsigned int* sf_host; unsigned int* sf_host_dev; unsigned int* sf_poison;
   FrameDev* frame_save;            // the frame record as the gate of the last k_small_frame found it
   struct SfFrame { unsigned int epoch; float R[9], t[3]; double pn, on; Moves mv; const float* pts; long n_pts, n_pts_all; int stride; ChanView chan; int n_cols; };
   enum { SF_RING = 8 };
@@ -176,15 +172,12 @@ struct emap_ctx {
   bool sf_redo;                    // inside sf_recover: frames take the chain of launches
   unsigned int sf_aborts;          // frames re-run so far (emap_small_frame_aborts)
   int update_path;                 // emap_last_update_path
-  bool gate_possible;              // false inside emap_update when the host already knows that the drift gate cannot fire: the per-tile
-                                   // error statistics are then skipped (they could not have any effect; err_sum / err_cnt report 0)
   BinGeo bg; BinRec* bin_recs; BinStg* bin_own; unsigned int* bin_own_cnt; long bin_own_cap; bool bin_strip;   // bin_own*: staged records of the owned points per block (strip contexts without a visibility pass)
   unsigned int* bin_hist; unsigned int* bin_tile_total; unsigned int* bin_tile_start; long bin_cap; size_t bin_hist_cap;      // bin_cap: 16-byte units
   // The semantic fusion declared for the NEXT whole frame (emap_frame_semantics): run inside the frame.  A frame that can CARRIES the
-  // channels in 32-byte sorted records (bin_rs = 2, carry: which columns) and fuses them in the tile kernel itself (fsem_merged);
+  // channels in 32-byte sorted records (bin_rs = 2, carry: which columns) and fuses them in the tile kernel itself;
   // every other frame runs the stand-alone semantic kernels before it returns -- the result is the same either way.
-  bool fsem_set, fsem_merged; int fsem_keep_counts; SemSpec fsem;
-  bool carry_want;                 // this frame's emap_count may sort 32-byte records (decided by frame_sem_begin)
+  bool fsem_set; int fsem_keep_counts; SemSpec fsem;
   int bin_rs; SemCarry carry;      // stride of the current frame's sorted records in 16-byte units; the carried columns (on = 0: none)
   // semantic layers (planar float planes + double / uint32 accumulators), allocated on demand
   float* img_uv; unsigned char* img_valid; float* img_buf; size_t img_cap;   // camera path
@@ -202,17 +195,17 @@ struct emap_ctx {
   ChanView chan; int n_cols;                        // its extra channels (emap_device.h: ChanView); n_cols = columns of the caller's matrix (3 + K)
   int* tail_idx; unsigned char* tail_flags; long tail_cap;
   // frame state
-  double pos_noise, ori_noise; bool use_override; double sum_override; unsigned int cnt_override;
+  bool use_override; double sum_override; unsigned int cnt_override;
   bool committed;
   bool stage_timing; hipEvent_t ev[ST_N + 1]; float stage_ms[ST_N];
   hipEvent_t t0, t1;
-  bool want_ray_stats; bool in_update;
+  bool want_ray_stats;
   // row-strip communicator (emap_comm_init): RCCL resolved at run time, exchange on its own stream so that it overlaps the interior stencils
   struct RcclApi* rccl; ncclComm_t comm; int comm_rank, comm_world;
   float* gather_buf;            // cell_n x cell_n plane of emap_comm_gather_layer (on demand)
   // rays by ray (multi-GPU frames with a visibility pass): the replicated ray window around the sensor (emap_device.h: Win)
   int ray_mode;                 // 0 auto (by ray from 2048^2 cells on), 1 always by row, 2 by ray whenever the frame allows it
-  bool byray_frame;             // the current sharded frame marches its rays by ray
+  bool byray_allreduce;         // the communicator's by-ray exchange: three all-reduces instead of the owners' sends / receives (emap_comm_init)
   size_t wire_bytes;            // payload of the last by-ray frame's three all-reduces (bytes per rank)
   int ray_par;                  // parity of the k_ray_apply launches (FrameDev::quiet_sum)
   unsigned int* win_state; unsigned int* win_rec; unsigned long long* win_bits; float* win_thr; long long* win_dh; unsigned int* win_key; long win_cap;
@@ -221,7 +214,6 @@ struct emap_ctx {
   // the un-shifted normal planes after a row shift (normal_exchange): a row-aligned copy of the rows this strip's cells belong to
   std::vector<int> cut_begin, cut_count;   // every rank's owned PHYSICAL rows (gathered by emap_comm_init)
   float* nlag_buf; long nlag_cap;          // 3 planes of row_count x cell_n
-  bool nlag_ready;                         // filled for the current frame's visibility pass
   bool cuts_ok;                            // the gathered strips tile the map
   std::string err;
 };
@@ -231,6 +223,23 @@ struct emap_ctx {
        if (e_ != hipSuccess) { ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); return EMAP_ERR_HIP; } } while (0)
 #define CKARG(cond, msg) do { if (!(cond)) { if (ctx) ctx->err = msg; return EMAP_ERR_INVALID; } } while (0)
 
+// What one frame (frame_impl: emap_update, emap_update_sharded) decided, handed to the stage helpers it calls.  It lives on the
+// frame's stack: an error on the way leaves nothing behind for the next call.  The staged entry points pass nullptr: the per-tile
+// error statistics are gathered, plain 16-byte records sorted, the gate runs on its own, the rays march by row over the committed
+// snapshot, nothing is folded.
+struct Frame {
+  bool gate_possible;      // the drift gate can fire (elevation_mapping.py:346-349); if not, the per-tile error statistics are skipped
+                           // (they could not have any effect; err_sum / err_cnt report 0)
+  bool fold_gate;          // whole map on the atomic path: the gate rides in k_count's last workgroup (cnt_sync: its ticket words)
+  bool carry;              // the sort may carry the declared semantic channels in 32-byte records (frame_sem_begin)
+  bool by_ray;             // sharded frame whose visibility pass marches by ray (rays_by_ray_pass)
+  bool rays_fused;         // the tile kernel committed + averaged, k_ray_apply follows the rays
+  bool nlag;               // normal_exchange filled the row-aligned copy of the normal planes for the visibility pass
+  GateArgs gate;           // the drift gate's inputs (k_count's fold, k_small_frame, gate_fold)
+  GateFold gate_fold;      // sharded frame on the binned path: the decision on the all-reduced totals in the tile kernel's head (mode 0: k_gate ran)
+  OverlapArgs ov;          // clear_overlap_map, folded into the kernel that rewrites the cells last (tile kernel, k_average or k_ray_apply)
+};
+
 static float q16(float x) { return (float)(_Float16)x; }
 // The k_small_frame launches that are issued and not yet known to be applied (emap_ctx::sf_ring).  sf_settle waits until the device
 // has decided the fate of the last of them (a poll of a host-mapped word: the decision falls at the launch's second barrier, long
@@ -239,7 +248,7 @@ static float q16(float x) { return (float)(_Float16)x; }
 // on the chain of launches, each on the cloud that was bound when it was issued.  Every entry point that reads or changes the map, the
 // drift record or a cloud buffer passes through SF_CHECK first; binding another device cloud and emap_update's own small-frame path do
 // not (frames pipeline), they only make room in the ring.
-static int update_impl(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise, emap_stats* stats);
+static int frame_impl(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise, emap_stats* stats, bool sharded);
 static void sf_forget_applied(emap_ctx* ctx) {
   const unsigned int passed = ctx->sf_host[0];
   while (ctx->sf_count > 0 && ctx->sf_ring[ctx->sf_head].epoch <= passed) { ctx->sf_head = (ctx->sf_head + 1) % emap_ctx::SF_RING; --ctx->sf_count; }
@@ -263,7 +272,7 @@ static int sf_recover(emap_ctx* ctx) {
     if (!first_done) { ctx->kp.mv = f.mv; first_done = true; }      // the pending map shifts the aborted launch was to write out (later frames: none, no shift can lie between unsettled frames)
     ctx->pts = f.pts; ctx->n_pts = f.n_pts; ctx->n_pts_all = f.n_pts_all; ctx->stride = f.stride; ctx->chan = f.chan; ctx->n_cols = f.n_cols;
     ++ctx->sf_aborts;
-    if (rc == EMAP_OK) rc = update_impl(ctx, f.R, f.t, f.pn, f.on, nullptr);
+    if (rc == EMAP_OK) rc = frame_impl(ctx, f.R, f.t, f.pn, f.on, nullptr, false);
   }
   ctx->sf_redo = false; ctx->fsem_set = fsem_set;
   ctx->pts = pts; ctx->n_pts = n_pts; ctx->n_pts_all = n_all; ctx->stride = stride; ctx->chan = chan; ctx->n_cols = n_cols;
@@ -284,8 +293,8 @@ static int sf_settle(emap_ctx* ctx) {
   return EMAP_OK;
 }
 #define SF_CHECK() do { if (ctx->sf_count > 0) { int rc_sf_ = sf_settle(ctx); if (rc_sf_) return rc_sf_; } } while (0)
-static int frame_sem_begin(emap_ctx* ctx, bool rays_on);                               // (the frame's semantic fusion: defined next to emap_semantic_update)
-static int frame_sem_finish(emap_ctx* ctx, const float R[9], const float t[3]);
+static int frame_sem_begin(emap_ctx* ctx, bool rays_on, Frame* fr);                    // (the frame's semantic fusion: defined next to emap_semantic_update)
+static int frame_sem_finish(emap_ctx* ctx, const float R[9], const float t[3], bool merged);
 
 static void build_kp(emap_ctx* ctx) {
   const emap_params& p = ctx->prm;
@@ -842,7 +851,14 @@ static int bin_sub(const emap_ctx* ctx) {
   return 0;
 }
 static bool bins_possible(const emap_ctx* ctx) { return bin_sub(ctx) > 0; }
-static int ensure_bins(emap_ctx* ctx, bool raybin) {
+// Small clouds: two launches with global atomics win; large clouds: counting sort by tile + LDS reduction.  The crossover measured on
+// MI355X lies at 60-135 k points for 202^2 .. 1024^2 maps.  n: the size of the WHOLE cloud -- a cloud bucketed for a
+// strip decides by it, so every rank of a sharded frame takes the same path.
+#define BIN_MIN_POINTS 131072
+static bool takes_bins(const emap_ctx* ctx, long n) {
+  return ctx->scatter_mode == 2 || (ctx->scatter_mode == 0 && bins_possible(ctx) && n >= BIN_MIN_POINTS);
+}
+static int ensure_bins(emap_ctx* ctx, bool raybin, const Frame* f) {
   const long n = ctx->n_pts;
   BinGeo& g = ctx->bg;
   g.sub = bin_sub(ctx);
@@ -856,11 +872,11 @@ static int ensure_bins(emap_ctx* ctx, bool raybin) {
   // points in 42 us where the strip variants take 52
   // (a by-ray frame keeps the strip variants: there the EXACT ownership test decides which rank marches a point's ray -- a point the
   // host-side superset kept for two neighbouring strips must not ride in both ranks' ray-only bins)
-  ctx->bin_strip = ctx->strip.row_count < ctx->prm.cell_n && (!raybin || ctx->byray_frame) && !(ctx->pts_bucketed && !raybin);
+  ctx->bin_strip = ctx->strip.row_count < ctx->prm.cell_n && (!raybin || (f && f->by_ray)) && !(ctx->pts_bucketed && !raybin);
   if (const char* e = getenv("EMAP_BIN_STRIP")) { if (atoi(e) == 0) ctx->bin_strip = false; }      // test / tuning hook
   // 32-byte records that carry the frame's semantic channels (frame_sem_begin): plain point passes only (a strip's staging records
   // hold no channels), never in front of a visibility pass (k_rays walks 16-byte records)
-  ctx->bin_rs = (ctx->carry_want && !ctx->bin_strip && !raybin) ? 2 : 1;
+  ctx->bin_rs = (f && f->carry && !ctx->bin_strip && !raybin) ? 2 : 1;
   if (ctx->bin_rs == 1) ctx->carry.on = 0;
   // Blocks: ~4096 points each, but every block carries a row of the (block, tile) matrix through three passes (written, scanned,
   // read): keep the matrix (4 B x TB x B, x4) below the cloud's own traffic (12 B x n, x2) -- B <= n / (3 TB) -- without dropping
@@ -968,26 +984,29 @@ static GateArgs gate_args(emap_ctx* ctx, double position_noise, double orientati
   return g;
 }
 
+// The count stage.  gate_folded (frames only): k_count's last workgroup was the drift gate.
+static int count_impl(emap_ctx* ctx, const float R[9], const float t[3], const Frame* f, bool* gate_folded);
 int emap_count(emap_ctx* ctx, const float R[9], const float t[3]) {
   CKARG(ctx && R && t, "null argument"); SF_CHECK(); NEED_POINTS();
+  return count_impl(ctx, R, t, nullptr, nullptr);
+}
+static int count_impl(emap_ctx* ctx, const float R[9], const float t[3], const Frame* f, bool* gate_folded) {
   // a cloud bucketed for this strip holds the points of its rows under ONE pose and ONE row origin: the common entry point of every
   // frame (whole, sharded or staged) checks both -- a row shift in between moves the strip's logical rows under the kept points
   if (ctx->pts_bucketed) {
     CKARG(memcmp(ctx->bucket_R, R, sizeof ctx->bucket_R) == 0 && memcmp(ctx->bucket_t, t, sizeof ctx->bucket_t) == 0, "the bound cloud was bucketed for another pose (emap_upload_points_strip)");
     CKARG(ctx->bucket_org_r == ctx->kp.org_r, "the map's rows shifted since the bound cloud was bucketed for this strip (emap_upload_points_strip): upload it again");
   }
-  if (!ctx->in_update) { ctx->gate_possible = true; ctx->carry_want = false; }          // the staged API always gathers the statistics and sorts plain 16-byte records
+  const bool gate_possible = !f || f->gate_possible;
   ctx->bin_rs = 1;
   CK(hipSetDevice(ctx->device));
-  // small clouds: two launches with global atomics win; large clouds: counting sort by tile + LDS reduction
-  // (a cloud bucketed for a strip decides by the size of the WHOLE cloud: every rank of a sharded frame then takes the same path)
-  const bool binned = ctx->n_pts > 0 && (ctx->scatter_mode == 2 || (ctx->scatter_mode == 0 && bins_possible(ctx) && ctx->n_pts_all >= 131072));   // measured crossover on MI355X: 60-135 k points for 202^2 .. 1024^2 maps
+  const bool binned = ctx->n_pts > 0 && takes_bins(ctx, ctx->n_pts_all);
   ctx->frame_binned = binned;
+  const bool tm = ctx->stage_timing && f;
   if (binned) {
     // the ray-only sort bin exists when the parameters enable the visibility pass (a staged emap_rays call on a context without it
     // marches the cloud in its own order instead of the sorted records)
-    int rc = ensure_bins(ctx, ctx->prm.enable_visibility_cleanup != 0); if (rc) return rc;
-    const bool tm = ctx->stage_timing && ctx->in_update;
+    int rc = ensure_bins(ctx, ctx->prm.enable_visibility_cleanup != 0, f); if (rc) return rc;
     const Pose pose = make_pose(ctx, R, t);
     BinStg* own = ctx->bin_strip ? ctx->bin_own : nullptr;
     if (tm) CK(hipEventRecord(ctx->ev[ST_HIST], ctx->stream));
@@ -995,7 +1014,7 @@ int emap_count(emap_ctx* ctx, const float R[9], const float t[3]) {
     if (tm) CK(hipEventRecord(ctx->ev[ST_SCAN], ctx->stream));
     // heavy tiles are split only when k_tile_count runs in this frame (it leaves the per-cell counts k_tile_fuse's parts need)
     static const bool split_off = getenv("EMAP_SPLIT") && atoi(getenv("EMAP_SPLIT")) == 0;      // A/B and test hook
-    ctx->split.on = ctx->gate_possible && !split_off ? 1 : 0;
+    ctx->split.on = gate_possible && !split_off ? 1 : 0;
     {   // extra workgroups of this frame's tile kernels: what the most recent finished scan asked for, + 25 %, and never fewer than a
         // STANDING POOL (EMAP_SPLIT_POOL, default 0 = none).  A heavy tile takes as many parts as it finds room for (k_bin_scan's
         // tail), so a pool would split the heavy tiles of a scene the host has not heard of yet.  Measured with a pool of 16 (round 5,
@@ -1026,19 +1045,17 @@ int emap_count(emap_ctx* ctx, const float R[9], const float t[3]) {
     launch_bin_scatter(ctx->stream, ctx->kp, pose, ctx->bg, ctx->pts, ctx->n_pts, ctx->stride, ctx->bin_hist, ctx->bin_tile_start, ctx->bin_recs, own, ctx->bin_own_cnt,
                        ctx->chan, ctx->carry);
     if (tm) CK(hipEventRecord(ctx->ev[ST_GATE], ctx->stream));        // the "gate" stage = per-tile error sums + k_gate
-    if (ctx->gate_possible) launch_tile_count(ctx->stream, ctx->kp, ctx->bg, ctx->bin_recs, ctx->bin_rs, ctx->bin_tile_start, ctx->cells, ctx->slots, ctx->split, ctx->n_pts);
+    if (gate_possible) launch_tile_count(ctx->stream, ctx->kp, ctx->bg, ctx->bin_recs, ctx->bin_rs, ctx->bin_tile_start, ctx->cells, ctx->slots, ctx->split, ctx->n_pts);
   } else {
     ctx->carry.on = 0;
-    if (ctx->stage_timing && ctx->in_update)
-      for (int e = ST_HIST; e <= ST_SCATTER; ++e) CK(hipEventRecord(ctx->ev[e], ctx->stream));
+    if (tm) for (int e = ST_HIST; e <= ST_SCATTER; ++e) CK(hipEventRecord(ctx->ev[e], ctx->stream));
     // whole frames (emap_update) on this path: the drift gate rides in k_count's last workgroup, one launch less in a chain of six
     static const bool fold_off = getenv("EMAP_GATE_FOLD") && atoi(getenv("EMAP_GATE_FOLD")) == 0;      // A/B and test hook
-    GateArgs ga;
-    const bool fold = ctx->fold_gate && !fold_off && ctx->cnt_sync;
-    if (fold) { ctx->use_override = false; ga = gate_args(ctx, ctx->pos_noise, ctx->ori_noise); }
-    ctx->gate_folded = launch_count(ctx->stream, ctx->kp, make_pose(ctx, R, t), ctx->pts, ctx->n_pts, ctx->stride, ctx->cells, ctx->acc, ctx->slots,
-                                    fold ? &ga : nullptr, ctx->frame, ctx->cnt_sync);
-    if (ctx->stage_timing && ctx->in_update) CK(hipEventRecord(ctx->ev[ST_GATE], ctx->stream));
+    const bool fold = f && f->fold_gate && !fold_off && ctx->cnt_sync;
+    const bool folded = launch_count(ctx->stream, ctx->kp, make_pose(ctx, R, t), ctx->pts, ctx->n_pts, ctx->stride, ctx->cells, ctx->acc, ctx->slots,
+                                     fold ? &f->gate : nullptr, ctx->frame, ctx->cnt_sync);
+    if (gate_folded) *gate_folded = folded;
+    if (tm) CK(hipEventRecord(ctx->ev[ST_GATE], ctx->stream));
   }
   CK(hipGetLastError());
   return EMAP_OK;
@@ -1056,7 +1073,6 @@ static int gate_impl(emap_ctx* ctx, double position_noise, double orientation_no
 int emap_set_drift_inputs(emap_ctx* ctx, double position_noise, double orientation_noise, const double* err_sum_override,
                           const uint32_t* err_cnt_override) {
   CKARG(ctx, "null ctx"); SF_CHECK();
-  ctx->pos_noise = position_noise; ctx->ori_noise = orientation_noise;
   ctx->use_override = err_sum_override && err_cnt_override;
   if (ctx->use_override) { ctx->sum_override = *err_sum_override; ctx->cnt_override = *err_cnt_override; }
   return gate_impl(ctx, position_noise, orientation_noise, 0, nullptr, nullptr);
@@ -1086,7 +1102,9 @@ int emap_local_drift_sums(emap_ctx* ctx, double* err_sum, uint32_t* err_cnt) {
   return EMAP_OK;
 }
 
-static int fuse_impl(emap_ctx* ctx, const float R[9], const float t[3], bool fuse_average = false, bool rays = false) {
+// sem_merged (frames only): the tile kernel fused the declared semantic channels itself
+static int fuse_impl(emap_ctx* ctx, const float R[9], const float t[3], bool fuse_average = false, bool rays = false, const Frame* f = nullptr,
+                     bool* sem_merged = nullptr) {
   NEED_POINTS();
   CK(hipSetDevice(ctx->device));
   if (ctx->frame_binned) {
@@ -1111,13 +1129,12 @@ static int fuse_impl(emap_ctx* ctx, const float R[9], const float t[3], bool fus
       for (int q = 0; q < S.n_sum; ++q) { sm.slot[q] = S.sum_chan[q] - ctx->carry.c0; sm.layer[q] = S.sum_layer[q]; sm.kind[q] = S.sum_kind[q]; }
       if (S.n_col) { sm.col_slot = S.col_chan[0] - ctx->carry.c0; sm.col_layer = S.col_layer[0]; }
     }
-    ctx->fsem_merged = merged;
+    if (sem_merged) *sem_merged = merged;
     if (ctx->fsem_set) ctx->update_path |= merged ? 4 : (ctx->carry.on ? 8 : 0);      // (emap_last_update_path)
     launch_bin_fuse(ctx->stream, ctx->kp, ctx->bg, ctx->bin_recs, ctx->bin_rs, ctx->bin_tile_start, ctx->cells, ctx->acc, ctx->frame, fuse_average, rays,
-                    (merged && !ctx->fsem_keep_counts) ? nullptr : ctx->cnt_plane, ctx->inert, ctx->inl_plane, ctx->ray_thr, ctx->ov_args, ctx->gate_fold, ctx->split, ctx->n_pts,
-                    merged ? &sm : nullptr);
+                    (merged && !ctx->fsem_keep_counts) ? nullptr : ctx->cnt_plane, ctx->inert, ctx->inl_plane, ctx->ray_thr, f ? f->ov : OverlapArgs{},
+                    f ? f->gate_fold : GateFold{}, ctx->split, ctx->n_pts, merged ? &sm : nullptr);
     if (ctx->split.on) ctx->split_dirty = false;        // k_tile_fuse's parts cleared their slots (a frame that splits nothing leaves an older count stage's slots as they are)
-    ctx->gate_fold.mode = 0;
     if (fuse_average) ctx->kp.mv.n = 0;   // every owned cell rewritten: pending map shifts are in memory now
     CK(hipGetLastError());
     return EMAP_OK;
@@ -1152,23 +1169,28 @@ int emap_commit(emap_ctx* ctx) {
   return EMAP_OK;
 }
 
+static int rays_impl(emap_ctx* ctx, const float R[9], const float t[3], const Frame* f);
 int emap_rays(emap_ctx* ctx, const float R[9], const float t[3]) {
   CKARG(ctx && R && t, "null argument"); SF_CHECK(); NEED_POINTS();
+  return rays_impl(ctx, R, t, nullptr);
+}
+static int rays_impl(emap_ctx* ctx, const float R[9], const float t[3], const Frame* f) {
   CK(hipSetDevice(ctx->device));
-  CKARG(ctx->committed || ctx->rays_fused, "emap_rays needs emap_commit first (rays read snapshot S1)");
+  const bool fused = f && f->rays_fused, nlag = f && f->nlag;
+  CKARG(ctx->committed || fused, "emap_rays needs emap_commit first (rays read snapshot S1)");
   CKARG(!ctx->pts_bucketed, "a bucketed cloud (emap_upload_points_strip) cannot march its rays by row: every valid point marches a ray through every strip");
   // newmap[3]: the tile kernel's dense plane, or the high halves of AccF::pts_inl (5 x u64 records) on the staged / atomic path
-  const unsigned int* inl = ctx->rays_fused ? ctx->inl_plane : reinterpret_cast<const unsigned int*>(ctx->acc) + 1;
+  const unsigned int* inl = fused ? ctx->inl_plane : reinterpret_cast<const unsigned int*>(ctx->acc) + 1;
   const bool sorted = ctx->frame_binned && ctx->bg.raybin;      // the sorted records hold EVERY valid point only with the ray-only bin
   char* const ab = reinterpret_cast<char*>(ctx->accr);
   const AccRView av = {ab + offsetof(AccR, dec), ab + offsetof(AccR, hits), ab + offsetof(AccR, upper_key), (int)sizeof(AccR), (int)sizeof(AccR), (int)sizeof(AccR), 0};
   KP kr = ctx->kp;
-  kr.nlag = ctx->nlag_ready ? 1 : 0;                     // sharded frame after a row shift: the row-aligned copy of the normal planes (normal_exchange)
+  kr.nlag = nlag ? 1 : 0;                                // sharded frame after a row shift: the row-aligned copy of the normal planes (normal_exchange)
   kr.ray_pref = ctx->split_need ? (int)ctx->split_need[1] : 0;      // (host-mapped word written by k_ray_apply: FrameDev::ray_class)
   launch_rays(ctx->stream, kr, make_pose(ctx, R, t), ctx->rt, ctx->pts, ctx->n_pts, ctx->stride, ctx->cells, av,
-              ctx->nlag_ready ? ctx->nlag_buf : ctx->normal, ctx->nlag_ready ? (long)ctx->strip.row_count * ctx->prm.cell_n : ctx->ncells_alloc,
-              ctx->frame, ctx->want_ray_stats, ctx->inert, inl, ctx->rays_fused ? 1 : (int)(sizeof(AccF) / 4),
-              ctx->rays_fused ? ctx->ray_thr : nullptr,
+              nlag ? ctx->nlag_buf : ctx->normal, nlag ? (long)ctx->strip.row_count * ctx->prm.cell_n : ctx->ncells_alloc,
+              ctx->frame, ctx->want_ray_stats, ctx->inert, inl, fused ? 1 : (int)(sizeof(AccF) / 4),
+              fused ? ctx->ray_thr : nullptr,
               sorted ? reinterpret_cast<const unsigned int*>(ctx->bin_recs) : nullptr,        // march in tile-sorted order
               sorted ? ctx->bin_tile_start + ctx->bg.TB : nullptr);
   CK(hipGetLastError());
@@ -1195,9 +1217,8 @@ static OverlapArgs overlap_args(const emap_ctx* ctx, float t_z, bool on) {
   return o;
 }
 
-static int overlap_clear_impl(emap_ctx* ctx, float t_z);
-int emap_overlap_clear(emap_ctx* ctx, float t_z) { CKARG(ctx, "null ctx"); SF_CHECK(); return overlap_clear_impl(ctx, t_z); }
-static int overlap_clear_impl(emap_ctx* ctx, float t_z) {      // (inside a frame: no SF_CHECK -- a small frame just issued must not be waited for)
+int emap_overlap_clear(emap_ctx* ctx, float t_z) {
+  CKARG(ctx, "null ctx"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   FLUSH();
   const OverlapArgs o = overlap_args(ctx, t_z, true);
@@ -1243,7 +1264,7 @@ int emap_traversability_normals(emap_ctx* ctx) { return emap_post_part(ctx, 0); 
 // 2 = the remaining (boundary) rows.
 static int post_part_impl(emap_ctx* ctx, int32_t part);
 int emap_post_part(emap_ctx* ctx, int32_t part) { CKARG(ctx && part >= 0 && part <= 2, "bad argument"); SF_CHECK(); return post_part_impl(ctx, part); }
-static int post_part_impl(emap_ctx* ctx, int32_t part) {      // (inside a frame: no SF_CHECK, see overlap_clear_impl)
+static int post_part_impl(emap_ctx* ctx, int32_t part) {      // (inside a frame: no SF_CHECK -- a small frame just issued must not be waited for)
   CK(hipSetDevice(ctx->device));
   FLUSH();
   const int n = ctx->strip.row_count;
@@ -1272,105 +1293,6 @@ int emap_get_stats(emap_ctx* ctx, emap_stats* out) {
   out->err_sum = (double)f.err_sum_fix / EM_SCALE_E; out->err_cnt = (uint32_t)f.err_cnt; out->gate_fired = f.gate_fired;
   out->mean_error = f.mean_error; out->additive_mean_error = f.additive_mean_error; out->shift = f.shift;
   out->n_points = f.n_points; out->ray_visits = f.ray_visits;
-  return EMAP_OK;
-}
-
-int emap_update(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise, emap_stats* stats) {
-  const int rc = update_impl(ctx, R, t, position_noise, orientation_noise, stats);
-  if (ctx) { ctx->fsem_set = false; ctx->carry_want = false; }      // the declared semantic fusion belongs to ONE frame, whatever became of it
-  return rc;
-}
-static int update_impl(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise, emap_stats* stats) {
-  CKARG(ctx && R && t, "null argument"); NEED_POINTS();
-  CK(hipSetDevice(ctx->device));
-  const emap_params& p = ctx->prm;
-  const bool tm = ctx->stage_timing;
-  int rc;
-#define STAGE(i) do { if (tm) CK(hipEventRecord(ctx->ev[i], ctx->stream)); } while (0)
-  const bool rays_on = p.enable_visibility_cleanup != 0;
-  // robot scale (small clouds on small maps: the atomic path): count, gate, fuse and commit / average in ONE launch
-  static const bool sf_env_off = getenv("EMAP_SMALL_FRAME") && atoi(getenv("EMAP_SMALL_FRAME")) == 0;      // A/B and test hook
-  const bool atomic_path = !(ctx->scatter_mode == 2 || (ctx->scatter_mode == 0 && bins_possible(ctx) && ctx->n_pts_all >= 131072));      // (emap_count's choice)
-  // (not with a visibility pass or a declared semantic fusion behind it: an ABORTED launch must leave nothing for the rest of the frame to
-  // act on -- the stencil launch that follows is a pure function of the map -- until sf_recover has re-run the frame)
-  const int sf_grid = (!sf_env_off && !ctx->sf_off && !ctx->sf_redo && atomic_path && ctx->cnt_sync && !ctx->pts_bucketed && !rays_on && !ctx->fsem_set) ? small_frame_grid(ctx->kp, ctx->n_pts) : 0;
-  if (sf_grid == 0) SF_CHECK();                 // (a frame on any other path: the small frames in flight are settled first)
-  if ((rc = frame_sem_begin(ctx, rays_on))) return rc;
-  // clear_overlap_map rides on the kernel that rewrites the cells last (tile kernel / k_average, or k_ray_apply after a visibility pass)
-  ctx->ov_args = overlap_args(ctx, t[2], p.enable_overlap_clearance != 0);
-  const bool ov_folded = ctx->ov_args.on != 0;
-  // drift gate of elevation_mapping.py:346-349: with compensation off or both noises below their thresholds it cannot fire
-  ctx->gate_possible = p.enable_drift_compensation && (position_noise > p.position_noise_thresh || orientation_noise > p.orientation_noise_thresh);
-  ctx->pos_noise = position_noise; ctx->ori_noise = orientation_noise;
-  bool fused_small = false;
-  if (sf_grid > 0) {
-    if ((rc = ensure_barrier_word(ctx))) { ctx->ov_args.on = 0; return rc; }
-    sf_forget_applied(ctx);
-    if (ctx->sf_count == emap_ctx::SF_RING || ctx->sf_epoch >= 0x7ffffff0u) {      // no room to remember another frame (or the epochs wrap): settle the ones in flight
-      if ((rc = sf_settle(ctx))) { ctx->ov_args.on = 0; return rc; }
-      if (ctx->sf_epoch >= 0x7ffffff0u) { CK(hipStreamSynchronize(ctx->stream)); ctx->sf_epoch = 0u; ctx->sf_host[0] = 0u; }
-    }
-    for (int e = ST_HIST; e <= ST_SCATTER; ++e) STAGE(e);
-    ctx->frame_binned = false; ctx->use_override = false;
-    ++ctx->sf_epoch;
-    {   // what the launch stands for, should a barrier be aborted (sf_recover)
-      emap_ctx::SfFrame& f = ctx->sf_ring[(ctx->sf_head + ctx->sf_count) % emap_ctx::SF_RING];
-      f.epoch = ctx->sf_epoch; memcpy(f.R, R, sizeof f.R); memcpy(f.t, t, sizeof f.t); f.pn = position_noise; f.on = orientation_noise; f.mv = ctx->kp.mv;
-      f.pts = ctx->pts; f.n_pts = ctx->n_pts; f.n_pts_all = ctx->n_pts_all; f.stride = ctx->stride; f.chan = ctx->chan; f.n_cols = ctx->n_cols;
-      ++ctx->sf_count;
-    }
-    unsigned int spin = SF_SPIN_DEFAULT; int test_abort = 0;      // test hooks (read per frame: a test toggles them)
-    if (const char* e = getenv("EMAP_SF_SPIN_LIMIT")) { const long v = atol(e); if (v >= 1 && v <= (1L << 24)) spin = (unsigned int)v; }
-    if (const char* e = getenv("EMAP_SF_TEST_ABORT")) test_abort = atoi(e);
-    launch_small_frame(ctx->stream, sf_grid, ctx->kp, make_pose(ctx, R, t), ctx->pts, ctx->n_pts, ctx->stride, ctx->cells, ctx->acc,
-                       ctx->cnt_plane, ctx->ov_args, gate_args(ctx, position_noise, orientation_noise), ctx->frame, ctx->frame_save, ctx->slots,
-                       ctx->cnt_sync, ctx->cnt_sync + 2048, ctx->sf_host_dev, ctx->sf_poison, ctx->sf_epoch, spin, test_abort);
-    CK(hipGetLastError());
-    fused_small = true;
-    STAGE(ST_GATE);
-  } else {
-    ctx->in_update = true;
-    ctx->fold_gate = true; ctx->gate_folded = false;
-    rc = emap_count(ctx, R, t);                 // records ST_HIST / ST_SCAN / ST_SCATTER itself
-    ctx->in_update = false; ctx->fold_gate = false;
-    if (rc) { ctx->ov_args.on = 0; return rc; }            // (emap_count also recorded ST_GATE: the stage starts with the per-tile error sums)
-    if (ctx->gate_folded) { ctx->committed = false; ctx->gate_folded = false; }      // (small clouds: k_count's last workgroup was the gate)
-    else if ((rc = emap_set_drift_inputs(ctx, position_noise, orientation_noise, nullptr, nullptr))) { ctx->ov_args.on = 0; return rc; }
-  }
-  ctx->update_path = fused_small ? 2 : (ctx->frame_binned ? 1 : 0);
-  STAGE(ST_FUSE);
-  // binned scatter: fusion, commit and averaging happen in ONE tile kernel; with the visibility pass it also writes the inert
-  // bitmap and the inlier plane, and the ray effects are applied by k_ray_apply ("average" stage) afterwards
-  const bool fused_avg = ctx->frame_binned;
-  rc = fused_small ? EMAP_OK : fuse_impl(ctx, R, t, fused_avg, rays_on);
-  const OverlapArgs ov = ctx->ov_args; ctx->ov_args.on = 0;
-  if (rc) return rc;
-  STAGE(ST_COMMIT);
-  ctx->rays_fused = fused_avg && rays_on;
-  if (rays_on) {
-    if (!fused_avg && (rc = emap_commit(ctx))) return rc;
-    STAGE(ST_RAYS);
-    rc = emap_rays(ctx, R, t);
-    if (rc) { ctx->rays_fused = false; return rc; }
-  } else STAGE(ST_RAYS);
-  STAGE(ST_AVERAGE);
-  if (fused_small) ctx->kp.mv.n = 0;                        // (k_small_frame committed and averaged: every cell rewritten)
-  else if (!fused_avg) { launch_average(ctx->stream, ctx->kp, ctx->cells, ctx->acc, ctx->accr, ctx->frame, ctx->committed, rays_on, ctx->cnt_plane, ov); ctx->kp.mv.n = 0; }
-  else if (rays_on) { launch_ray_apply(ctx->stream, ctx->kp, ctx->cells, ctx->accr, ctx->inert, ov, ctx->frame, ctx->split.need_host ? ctx->split.need_host + 1 : nullptr, ctx->ray_par ^= 1); ctx->inert_zero = true; }
-  ctx->committed = false; ctx->rays_fused = false;
-  CK(hipGetLastError());
-  if ((rc = frame_sem_finish(ctx, R, t))) return rc;      // semantic_map.update_layers_pointcloud (elevation_mapping.py:368) -- unless the tile kernel fused the channels itself
-  STAGE(ST_OVERLAP);
-  if (p.enable_overlap_clearance && !ov_folded && (rc = overlap_clear_impl(ctx, t[2]))) return rc;
-  STAGE(ST_POST);
-  if ((rc = post_part_impl(ctx, 0))) return rc;
-  STAGE(ST_N);
-#undef STAGE
-  if (tm) {
-    CK(hipEventSynchronize(ctx->ev[ST_N]));
-    for (int i = 0; i < ST_N; ++i) CK(hipEventElapsedTime(&ctx->stage_ms[i], ctx->ev[i], ctx->ev[i + 1]));
-  }
-  if (stats) return emap_get_stats(ctx, stats);
   return EMAP_OK;
 }
 
@@ -1529,8 +1451,8 @@ int emap_frame_semantics(emap_ctx* ctx, const emap_sem_spec* spec_or_null, int32
 // (32-byte records): kinds average / class_average and at most one colour channel, at most four channel columns, all within four
 // consecutive columns of the cloud; no visibility pass (k_rays walks 16-byte records).  emap_count then settles it (tile-binned
 // path, plain point passes: ensure_bins).  EMAP_SEM_CARRY=0: never (A/B and test hook).
-static int frame_sem_begin(emap_ctx* ctx, bool rays_on) {
-  ctx->carry_want = false; ctx->fsem_merged = false; memset(&ctx->carry, 0, sizeof ctx->carry);
+static int frame_sem_begin(emap_ctx* ctx, bool rays_on, Frame* fr) {
+  memset(&ctx->carry, 0, sizeof ctx->carry);
   if (!ctx->fsem_set) return EMAP_OK;
   emap_sem_spec raw; memcpy(&raw, &ctx->fsem, sizeof raw);
   SemSpec S;
@@ -1544,17 +1466,17 @@ static int frame_sem_begin(emap_ctx* ctx, bool rays_on) {
   for (int k = 0; k < S.n_sum; ++k) { if (S.sum_kind[k] > 1) return EMAP_OK; cmin = std::min(cmin, S.sum_chan[k]); cmax = std::max(cmax, S.sum_chan[k]); }
   for (int k = 0; k < S.n_col; ++k) { cmin = std::min(cmin, S.col_chan[k]); cmax = std::max(cmax, S.col_chan[k]); }
   if (cmax - cmin >= 4) return EMAP_OK;
-  ctx->carry_want = true;
+  fr->carry = true;
   ctx->carry.c0 = cmin; ctx->carry.ncols = ctx->n_cols;
   // the de-interleaved (N, 4) channel matrix of an uploaded cloud: one aligned 16-byte load per point
   ctx->carry.on = (ctx->chan.stride == 4 && ctx->chan.col0 == cmin && ((uintptr_t)ctx->chan.p & 15) == 0) ? 2 : 1;
   return EMAP_OK;
 }
-// End of the frame's fusion stages: whatever the tile kernel did not fuse itself runs now (the frame's counts are in cnt_plane)
-static int frame_sem_finish(emap_ctx* ctx, const float R[9], const float t[3]) {
+// End of the frame's fusion stages: whatever the tile kernel did not fuse itself (merged) runs now (the frame's counts are in cnt_plane)
+static int frame_sem_finish(emap_ctx* ctx, const float R[9], const float t[3], bool merged) {
   if (!ctx->fsem_set) return EMAP_OK;
-  ctx->fsem_set = false; ctx->carry_want = false;
-  if (ctx->fsem_merged) { ctx->fsem_merged = false; return EMAP_OK; }
+  ctx->fsem_set = false;
+  if (merged) return EMAP_OK;
   return semantic_update_impl(ctx, R, t, ctx->fsem);
 }
 
@@ -2100,6 +2022,10 @@ static RcclApi* rccl_open(const char* path, std::string* why) {
 #define CKN(call)                                                                                                       \
   do { ncclResult_t r_ = (call);                                                                                        \
        if (r_ != ncclSuccess) { ctx->err = std::string(#call) + ": " + ctx->rccl->GetErrorString(r_); return EMAP_ERR_COMM; } } while (0)
+// the same between ncclGroupStart and ncclGroupEnd: a failure closes the group before it returns (the next call must not land in it)
+#define CKG(call)                                                                                                       \
+  do { ncclResult_t r_ = (call);                                                                                        \
+       if (r_ != ncclSuccess) { ctx->err = std::string(#call) + ": " + ctx->rccl->GetErrorString(r_); ctx->rccl->GroupEnd(); return EMAP_ERR_COMM; } } while (0)
 
 int emap_comm_unique_id(const char* rccl_path, uint8_t id_out[128]) {
   static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
@@ -2143,6 +2069,9 @@ int emap_comm_init(emap_ctx* ctx, const char* rccl_path, const uint8_t id[128], 
   if (local_rc == EMAP_OK) step(hipMemsetAsync(ctx->comm_sums, 0, sizeof(double) * 36, ctx->stream), "hipMemsetAsync(comm_sums)");
   if (local_rc == EMAP_OK && world > 1 && ctx->prm.enable_visibility_cleanup && ctx->win_cap < window_cap(ctx))      // rays by ray: see ensure_window
     local_rc = alloc_window(ctx, window_cap(ctx));
+  // EMAP_BYRAY_ALLREDUCE=1: the by-ray frames exchange their window by the three all-reduces of round 4 / 5 (rays_by_ray_pass); the
+  // ranks agree on it below -- one rank alone on the other protocol would wait forever
+  ctx->byray_allreduce = getenv("EMAP_BYRAY_ALLREDUCE") && atoi(getenv("EMAP_BYRAY_ALLREDUCE")) != 0;
   auto fail = [&](int rc) { const std::string keep = ctx->err; emap_comm_destroy(ctx); ctx->err = keep; return rc; };
   if (world > 1 && !ctx->comm_sums) return fail(local_rc ? local_rc : EMAP_ERR_HIP);      // (nothing to reduce through: the peers time out in RCCL -- an out-of-memory device at start-up)
   // every rank's owned physical rows (the strips need not be equally high): who holds which normal rows after a row shift
@@ -2151,11 +2080,11 @@ int emap_comm_init(emap_ctx* ctx, const char* rccl_path, const uint8_t id[128], 
   if (world > 1) {
     // Every rank must speak the same ABI: the halo rows are raw 16-byte cold half cells and the ray window raw 32-byte records, so a
     // peer built against another layout would exchange misaligned bytes silently.  max(v) and max(-v) over the ranks: equal and
-    // opposite iff all ranks agree; the third word is the worst local status.
-    const double mine[3] = {(double)EMAP_ABI_VERSION, -(double)EMAP_ABI_VERSION, (double)(local_rc != EMAP_OK)};
-    double got[3] = {0.0, 0.0, 0.0};
+    // opposite iff all ranks agree; the third word is the worst local status, the fourth the by-ray exchange (all-reduces if any rank asks).
+    const double mine[4] = {(double)EMAP_ABI_VERSION, -(double)EMAP_ABI_VERSION, (double)(local_rc != EMAP_OK), (double)ctx->byray_allreduce};
+    double got[4] = {0.0, 0.0, 0.0, 0.0};
     CK(hipMemcpyAsync(ctx->comm_sums + 16, mine, sizeof mine, hipMemcpyHostToDevice, ctx->stream));
-    CKN(a->AllReduce(ctx->comm_sums + 16, ctx->comm_sums + 20, 3, ncclFloat64, ncclMax, ctx->comm, ctx->stream));
+    CKN(a->AllReduce(ctx->comm_sums + 16, ctx->comm_sums + 20, 4, ncclFloat64, ncclMax, ctx->comm, ctx->stream));
     CK(hipMemcpyAsync(got, ctx->comm_sums + 20, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
     if (got[2] != 0.0) {
@@ -2166,6 +2095,7 @@ int emap_comm_init(emap_ctx* ctx, const char* rccl_path, const uint8_t id[128], 
       ctx->err = "emap_comm_init: the ranks were built against different EMAP_ABI_VERSIONs (" + std::to_string((int)-got[1]) + " .. " + std::to_string((int)got[0]) + ", this rank: " + std::to_string(EMAP_ABI_VERSION) + ")";
       return fail(EMAP_ERR_COMM);
     }
+    ctx->byray_allreduce = got[3] != 0.0;
     double cuts[32], all[32];
     for (int k = 0; k < 32; ++k) cuts[k] = 0.0;
     cuts[2 * rank] = ctx->strip.row_begin; cuts[2 * rank + 1] = ctx->strip.row_count;
@@ -2190,7 +2120,7 @@ int emap_comm_destroy(emap_ctx* ctx) {
   if (ctx->ev_ready) hipEventDestroy(ctx->ev_ready);
   if (ctx->ev_done) hipEventDestroy(ctx->ev_done);
   hipFree(ctx->comm_sums); hipFree(ctx->gather_buf); ctx->gather_buf = nullptr;
-  hipFree(ctx->nlag_buf); ctx->nlag_buf = nullptr; ctx->nlag_cap = 0; ctx->nlag_ready = false;
+  hipFree(ctx->nlag_buf); ctx->nlag_buf = nullptr; ctx->nlag_cap = 0;
   delete ctx->rccl;
   ctx->rccl = nullptr; ctx->comm = nullptr; ctx->comm_stream = nullptr; ctx->ev_ready = ctx->ev_done = nullptr; ctx->comm_sums = nullptr;
   return EMAP_OK;
@@ -2207,10 +2137,10 @@ static int ring_exchange(emap_ctx* ctx, char* base, size_t row_bytes, hipStream_
   const RcclApi* a = ctx->rccl;
   const int W = ctx->comm_world, prev = (ctx->comm_rank + W - 1) % W, next = (ctx->comm_rank + 1) % W;
   CKN(a->GroupStart());
-  CKN(a->Send(base + row_bytes * H, bytes, ncclChar, prev, ctx->comm, st));                  // first H owned rows
-  CKN(a->Send(base + row_bytes * n, bytes, ncclChar, next, ctx->comm, st));                  // rows [n-H, n) of the strip
-  CKN(a->Recv(base + row_bytes * (H + n), bytes, ncclChar, next, ctx->comm, st));            // upper halo
-  CKN(a->Recv(base, bytes, ncclChar, prev, ctx->comm, st));                                  // lower halo
+  CKG(a->Send(base + row_bytes * H, bytes, ncclChar, prev, ctx->comm, st));                  // first H owned rows
+  CKG(a->Send(base + row_bytes * n, bytes, ncclChar, next, ctx->comm, st));                  // rows [n-H, n) of the strip
+  CKG(a->Recv(base + row_bytes * (H + n), bytes, ncclChar, next, ctx->comm, st));            // upper halo
+  CKG(a->Recv(base, bytes, ncclChar, prev, ctx->comm, st));                                  // lower halo
   CKN(a->GroupEnd());
   return EMAP_OK;
 }
@@ -2281,27 +2211,25 @@ static int normal_exchange(emap_ctx* ctx) {
     for (int k = 0; k < 3; ++k) {
       float* dst = ctx->nlag_buf + (size_t)k * n * C + (size_t)pc.dst * C;                                                  // (q == me)
       const float* src = ctx->normal + (size_t)k * ctx->ncells_alloc + (size_t)(H + pc.src - ctx->strip.row_begin) * C;     // (r == me)
-      if (pc.q == me && pc.r == me) CK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-      else {
+      if (pc.q == me && pc.r == me) {
+        const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e != hipSuccess) { if (grouped) a->GroupEnd(); ctx->err = std::string("hipMemcpyAsync(normal rows): ") + hipGetErrorString(e); return EMAP_ERR_HIP; }
+      } else {
         if (!grouped) { CKN(a->GroupStart()); grouped = true; }
-        if (pc.q == me) CKN(a->Recv(dst, bytes, ncclChar, pc.r, ctx->comm, ctx->stream));
-        else CKN(a->Send(src, bytes, ncclChar, pc.q, ctx->comm, ctx->stream));
+        if (pc.q == me) CKG(a->Recv(dst, bytes, ncclChar, pc.r, ctx->comm, ctx->stream));
+        else CKG(a->Send(src, bytes, ncclChar, pc.q, ctx->comm, ctx->stream));
       }
     }
   }
   if (grouped) CKN(a->GroupEnd());
-  ctx->nlag_ready = true;
   return EMAP_OK;
 }
 
 // ---- rays by ray (emap_kernels.hip: k_win_pack / k_win_prepare / k_win_unpack) ---------------------------------------------------
 // Decided from values every rank shares (parameters, world size, cloud size): all ranks take the same branch of the collective code.
-static bool frame_binned_everywhere(const emap_ctx* ctx) {      // emap_count's choice, for a cloud of this size
-  return ctx->n_pts_all > 0 && (ctx->scatter_mode == 2 || (ctx->scatter_mode == 0 && bins_possible(ctx) && ctx->n_pts_all >= 131072));
-}
 static bool rays_by_ray(const emap_ctx* ctx) {
   if (!ctx->rccl || ctx->comm_world <= 1 || !ctx->prm.enable_visibility_cleanup || ctx->ray_mode == 1) return false;
-  if (!frame_binned_everywhere(ctx)) return false;                // the window march walks the frame's tile-sorted records
+  if (!(ctx->n_pts_all > 0 && takes_bins(ctx, ctx->n_pts_all))) return false;      // the window march walks the frame's tile-sorted records
   // by row below 2048^2 cells: the window exchange (three all-reduces) costs about what the whole pass costs there
   return ctx->ray_mode == 2 || ctx->prm.cell_n >= 2048;
 }
@@ -2357,7 +2285,7 @@ static int ensure_window(emap_ctx* ctx, Win* w) {
   return EMAP_OK;
 }
 // The visibility pass of a sharded frame, by ray: called where emap_rays would be, between the tile kernel and k_ray_apply.
-static int rays_by_ray_pass(emap_ctx* ctx, const float R[9], const float t[3]) {
+static int rays_by_ray_pass(emap_ctx* ctx, const float R[9], const float t[3], const Frame* f) {
   Win w; memset(&w, 0, sizeof w);
   if (!ray_window(ctx, t, &w)) return EMAP_OK;                    // the same decision on every rank: no collective is skipped one-sidedly
   int rc = ensure_window(ctx, &w); if (rc) return rc;
@@ -2367,19 +2295,18 @@ static int rays_by_ray_pass(emap_ctx* ctx, const float R[9], const float t[3]) {
   // (1) the window's cells, normals and wall flags as 32-byte records: owners fill their rows, an exact integer all-reduce replicates them
   CK(hipMemsetAsync(ctx->win_rec, 0, sizeof(unsigned int) * 8 * (size_t)n, st));
   KP kpk = ctx->kp;
-  kpk.nlag = ctx->nlag_ready ? 1 : 0;
-  launch_win_pack(st, kpk, w, ctx->cells, ctx->nlag_ready ? ctx->nlag_buf : ctx->normal, ctx->nlag_ready ? (long)ctx->strip.row_count * ctx->prm.cell_n : ctx->ncells_alloc,
+  kpk.nlag = f->nlag ? 1 : 0;
+  launch_win_pack(st, kpk, w, ctx->cells, f->nlag ? ctx->nlag_buf : ctx->normal, f->nlag ? (long)ctx->strip.row_count * ctx->prm.cell_n : ctx->ncells_alloc,
                   ctx->inl_plane, ctx->inert, ctx->rt.f_wall);
   CK(hipGetLastError());
   // Who owns which rows of the window: runs of consecutive window rows per owner, from the strips' physical rows (gathered by
   // emap_comm_init) and the map's row origin -- the same list on every rank.  With it the window is replicated by BROADCASTS from its
   // two or three owners and the effects return by REDUCTIONS to them (round 6): grouped sends / receives, every rank receives each window
   // byte once and only the owners receive effects -- a ring all-reduce moves 2 (W - 1) / W of the whole window through every rank, twice.
-  // EMAP_BYRAY_ALLREDUCE=1 (or strips that do not tile the map): the three all-reduces of round 4 / 5.
+  // EMAP_BYRAY_ALLREDUCE=1 on any rank (emap_comm_init), or strips that do not tile the map: the three all-reduces of round 4 / 5.
   struct Run { int q, a, rows; };
   std::vector<Run> runs;
-  static const bool force_allreduce = getenv("EMAP_BYRAY_ALLREDUCE") && atoi(getenv("EMAP_BYRAY_ALLREDUCE")) != 0;
-  bool owners = ctx->comm_world > 1 && ctx->cuts_ok && !force_allreduce && ctx->win_red_dh;
+  bool owners = ctx->comm_world > 1 && ctx->cuts_ok && !ctx->byray_allreduce;
   if (owners) {
     const int C = ctx->prm.cell_n;
     for (int wr = 0; wr < w.nr && w.r0 + wr < C && owners; ++wr) {
@@ -2398,8 +2325,8 @@ static int rays_by_ray_pass(emap_ctx* ctx, const float R[9], const float t[3]) {
     for (const Run& r : runs) {
       char* slab = reinterpret_cast<char*>(ctx->win_rec) + (size_t)r.a * w.nc * 32;
       const size_t bytes = (size_t)r.rows * w.nc * 32;
-      if (r.q == me) { for (int p = 0; p < W; ++p) if (p != me) { CKN(a->Send(slab, bytes, ncclChar, p, ctx->comm, st)); moved += bytes; } }
-      else { CKN(a->Recv(slab, bytes, ncclChar, r.q, ctx->comm, st)); moved += bytes; }
+      if (r.q == me) { for (int p = 0; p < W; ++p) if (p != me) { CKG(a->Send(slab, bytes, ncclChar, p, ctx->comm, st)); moved += bytes; } }
+      else { CKG(a->Recv(slab, bytes, ncclChar, r.q, ctx->comm, st)); moved += bytes; }
     }
     CKN(a->GroupEnd());
   } else {
@@ -2432,14 +2359,14 @@ static int rays_by_ray_pass(emap_ctx* ctx, const float R[9], const float t[3]) {
       const size_t cells = (size_t)r.rows * w.nc;
       if (r.q == me) {
         for (int p = 0, j = 0; p < W; ++p) if (p != me) {
-          CKN(a->Recv(reinterpret_cast<char*>(ctx->win_red_dh + 2 * ((size_t)j * ctx->win_cap + off)), cells * 16, ncclChar, p, ctx->comm, st));
-          CKN(a->Recv(reinterpret_cast<char*>(ctx->win_red_key + ((size_t)j * ctx->win_cap + off)), cells * 4, ncclChar, p, ctx->comm, st));
+          CKG(a->Recv(reinterpret_cast<char*>(ctx->win_red_dh + 2 * ((size_t)j * ctx->win_cap + off)), cells * 16, ncclChar, p, ctx->comm, st));
+          CKG(a->Recv(reinterpret_cast<char*>(ctx->win_red_key + ((size_t)j * ctx->win_cap + off)), cells * 4, ncclChar, p, ctx->comm, st));
           moved += cells * 20; ++j;
         }
         off += (long)cells;
       } else {
-        CKN(a->Send(reinterpret_cast<char*>(w.dh + 2 * (size_t)r.a * w.nc), cells * 16, ncclChar, r.q, ctx->comm, st));
-        CKN(a->Send(reinterpret_cast<char*>(w.key + (size_t)r.a * w.nc), cells * 4, ncclChar, r.q, ctx->comm, st));
+        CKG(a->Send(reinterpret_cast<char*>(w.dh + 2 * (size_t)r.a * w.nc), cells * 16, ncclChar, r.q, ctx->comm, st));
+        CKG(a->Send(reinterpret_cast<char*>(w.key + (size_t)r.a * w.nc), cells * 4, ncclChar, r.q, ctx->comm, st));
         moved += cells * 20;
       }
     }
@@ -2460,81 +2387,127 @@ static int rays_by_ray_pass(emap_ctx* ctx, const float R[9], const float t[3]) {
   return EMAP_OK;
 }
 
-// One frame of the strip: the stage order of ShardedElevationMap.update (sharded.py) with both exchange steps issued from
-// here -- no Python, no host synchronisation between the stages.
-static int update_sharded_impl(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise, emap_stats* stats);
-int emap_update_sharded(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise, emap_stats* stats) {
-  const int rc = update_sharded_impl(ctx, R, t, position_noise, orientation_noise, stats);
-  if (ctx) { ctx->fsem_set = false; ctx->carry_want = false; ctx->in_update = false; }
+// ---- one frame -----------------------------------------------------------------------------------------------------------
+// emap_update runs a whole map (or a strip on its own), emap_update_sharded a row strip of a map shared through the communicator: the
+// stage order of ShardedElevationMap.update (sharded.py) with both exchange steps issued from here -- no Python, no host
+// synchronisation between the stages.  The two differ only in whether the frame may take the small-frame path, how the drift gate
+// gets its totals, how the rays march and how the stencils run.  sf_recover re-runs aborted small frames through frame_impl too.
+static int run_frame(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise, emap_stats* stats, bool sharded) {
+  const int rc = frame_impl(ctx, R, t, position_noise, orientation_noise, stats, sharded);
+  if (ctx) ctx->fsem_set = false;      // the declared semantic fusion belongs to ONE frame, whatever became of it
   return rc;
 }
-static int update_sharded_impl(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise, emap_stats* stats) {
-  CKARG(ctx && R && t, "null argument"); SF_CHECK(); NEED_POINTS();
-  CKARG(ctx->rccl && ctx->comm, "emap_comm_init has not been called");
+int emap_update(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise, emap_stats* stats) {
+  return run_frame(ctx, R, t, position_noise, orientation_noise, stats, false);
+}
+int emap_update_sharded(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise, emap_stats* stats) {
+  return run_frame(ctx, R, t, position_noise, orientation_noise, stats, true);
+}
+static int frame_impl(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise, emap_stats* stats, bool sharded) {
+  CKARG(ctx && R && t, "null argument"); NEED_POINTS();
+  CKARG(!sharded || (ctx->rccl && ctx->comm), "emap_comm_init has not been called");
   CK(hipSetDevice(ctx->device));
   const emap_params& p = ctx->prm;
-  const RcclApi* a = ctx->rccl;
-  const bool tm = ctx->stage_timing;
+  const bool tm = ctx->stage_timing, rays_on = p.enable_visibility_cleanup != 0;
   int rc;
 #define STAGE(i) do { if (tm) CK(hipEventRecord(ctx->ev[i], ctx->stream)); } while (0)
-  if ((rc = frame_sem_begin(ctx, p.enable_visibility_cleanup != 0))) return rc;
-  ctx->in_update = true;
-  ctx->gate_possible = p.enable_drift_compensation && (position_noise > p.position_noise_thresh || orientation_noise > p.orientation_noise_thresh);
-  ctx->byray_frame = rays_by_ray(ctx);        // (before the sort: a by-ray frame sorts only the points of the strip's rows)
-  ctx->wire_bytes = 0;
-  if (ctx->pts_bucketed) {                    // emap_upload_points_strip: the cloud only holds the points of this strip's rows, for ONE pose
-    if (memcmp(ctx->bucket_R, R, sizeof ctx->bucket_R) != 0 || memcmp(ctx->bucket_t, t, sizeof ctx->bucket_t) != 0) {
-      ctx->in_update = false; ctx->byray_frame = false; ctx->err = "the bound cloud was bucketed for another pose (emap_upload_points_strip)"; return EMAP_ERR_INVALID; }
-    if (p.enable_visibility_cleanup && !ctx->byray_frame) {
-      ctx->in_update = false; ctx->err = "a bucketed cloud cannot feed a visibility pass that marches BY ROW (every valid point marches a ray through every strip): upload the whole cloud, or march by ray (emap_set_ray_mode)"; return EMAP_ERR_INVALID; }
-  }
-  rc = emap_count(ctx, R, t);                 // records ST_HIST / ST_SCAN / ST_SCATTER itself
-  ctx->in_update = false;
-  if (rc) { ctx->byray_frame = false; return rc; }          // "gate" (recorded by emap_count) = per-tile error sums + local sums + all-reduce + gate
-  if (ctx->byray_frame && !ctx->frame_binned) { ctx->byray_frame = false; ctx->err = "rays by ray: this rank could not take the tile-binned path the other ranks take"; return EMAP_ERR_INVALID; }
-  ctx->update_path = ctx->frame_binned ? 1 : 0;
+  // robot scale (small clouds on small maps: the atomic path): count, gate, fuse and commit / average in ONE launch
+  // (not with a visibility pass or a declared semantic fusion behind it: an ABORTED launch must leave nothing for the rest of the frame to
+  // act on -- the stencil launch that follows is a pure function of the map -- until sf_recover has re-run the frame)
+  static const bool sf_env_off = getenv("EMAP_SMALL_FRAME") && atoi(getenv("EMAP_SMALL_FRAME")) == 0;      // A/B and test hook
+  const int sf_grid = (!sharded && !sf_env_off && !ctx->sf_redo && !takes_bins(ctx, ctx->n_pts_all) && ctx->cnt_sync && !ctx->pts_bucketed && !rays_on && !ctx->fsem_set)
+                      ? small_frame_grid(ctx->kp, ctx->n_pts) : 0;
+  if (sf_grid == 0) SF_CHECK();                 // (a frame on any other path: the small frames in flight are settled first)
+  Frame fr; memset(&fr, 0, sizeof fr);
+  if ((rc = frame_sem_begin(ctx, rays_on, &fr))) return rc;
+  fr.gate_possible = p.enable_drift_compensation && (position_noise > p.position_noise_thresh || orientation_noise > p.orientation_noise_thresh);
+  fr.fold_gate = !sharded;
   ctx->use_override = false;
-  if ((rc = gate_impl(ctx, 0.0, 0.0, 1, ctx->comm_sums, nullptr))) return rc;                       // local sums -> device
-  CKN(a->AllReduce(ctx->comm_sums, ctx->comm_sums + 2, 2, ncclFloat64, ncclSum, ctx->comm, ctx->stream));   // exchange step 1
-  if (ctx->frame_binned) {        // the decision on the all-reduced totals rides in the head of the tile kernel
-    memset(&ctx->gate_fold, 0, sizeof ctx->gate_fold);
-    ctx->gate_fold.mode = 1; ctx->gate_fold.dev_totals = ctx->comm_sums + 2; ctx->gate_fold.A = gate_args(ctx, position_noise, orientation_noise);
-    ctx->committed = false;
-  } else if ((rc = gate_impl(ctx, position_noise, orientation_noise, 0, nullptr, ctx->comm_sums + 2))) return rc;
+  fr.gate = gate_args(ctx, position_noise, orientation_noise);
+  // clear_overlap_map rides on the kernel that rewrites the cells last (tile kernel / k_average, or k_ray_apply after a visibility pass)
+  fr.ov = overlap_args(ctx, t[2], p.enable_overlap_clearance != 0);
+  if (sharded) {
+    fr.by_ray = rays_by_ray(ctx);             // (before the sort: a by-ray frame sorts only the points of the strip's rows)
+    ctx->wire_bytes = 0;
+    if (ctx->pts_bucketed) {                  // emap_upload_points_strip: the cloud only holds the points of this strip's rows, for ONE pose
+      CKARG(memcmp(ctx->bucket_R, R, sizeof ctx->bucket_R) == 0 && memcmp(ctx->bucket_t, t, sizeof ctx->bucket_t) == 0, "the bound cloud was bucketed for another pose (emap_upload_points_strip)");
+      CKARG(!rays_on || fr.by_ray, "a bucketed cloud cannot feed a visibility pass that marches BY ROW (every valid point marches a ray through every strip): upload the whole cloud, or march by ray (emap_set_ray_mode)");
+    }
+  }
+  bool fused_small = false;
+  if (sf_grid > 0) {
+    if ((rc = ensure_barrier_word(ctx))) return rc;
+    sf_forget_applied(ctx);
+    if (ctx->sf_count == emap_ctx::SF_RING || ctx->sf_epoch >= 0x7ffffff0u) {      // no room to remember another frame (or the epochs wrap): settle the ones in flight
+      if ((rc = sf_settle(ctx))) return rc;
+      if (ctx->sf_epoch >= 0x7ffffff0u) { CK(hipStreamSynchronize(ctx->stream)); ctx->sf_epoch = 0u; ctx->sf_host[0] = 0u; }
+    }
+    for (int e = ST_HIST; e <= ST_SCATTER; ++e) STAGE(e);
+    ctx->frame_binned = false;
+    ++ctx->sf_epoch;
+    {   // what the launch stands for, should a barrier be aborted (sf_recover)
+      emap_ctx::SfFrame& f = ctx->sf_ring[(ctx->sf_head + ctx->sf_count) % emap_ctx::SF_RING];
+      f.epoch = ctx->sf_epoch; memcpy(f.R, R, sizeof f.R); memcpy(f.t, t, sizeof f.t); f.pn = position_noise; f.on = orientation_noise; f.mv = ctx->kp.mv;
+      f.pts = ctx->pts; f.n_pts = ctx->n_pts; f.n_pts_all = ctx->n_pts_all; f.stride = ctx->stride; f.chan = ctx->chan; f.n_cols = ctx->n_cols;
+      ++ctx->sf_count;
+    }
+    unsigned int spin = SF_SPIN_DEFAULT; int test_abort = 0;      // test hooks (read per frame: a test toggles them)
+    if (const char* e = getenv("EMAP_SF_SPIN_LIMIT")) { const long v = atol(e); if (v >= 1 && v <= (1L << 24)) spin = (unsigned int)v; }
+    if (const char* e = getenv("EMAP_SF_TEST_ABORT")) test_abort = atoi(e);
+    launch_small_frame(ctx->stream, sf_grid, ctx->kp, make_pose(ctx, R, t), ctx->pts, ctx->n_pts, ctx->stride, ctx->cells, ctx->acc,
+                       ctx->cnt_plane, fr.ov, fr.gate, ctx->frame, ctx->frame_save, ctx->slots,
+                       ctx->cnt_sync, ctx->cnt_sync + 2048, ctx->sf_host_dev, ctx->sf_poison, ctx->sf_epoch, spin, test_abort);
+    CK(hipGetLastError());
+    fused_small = true;
+    STAGE(ST_GATE);
+  } else {
+    bool gate_folded = false;
+    if ((rc = count_impl(ctx, R, t, &fr, &gate_folded))) return rc;     // records ST_HIST .. ST_GATE itself: "gate" starts with the per-tile error sums
+    CKARG(!fr.by_ray || ctx->frame_binned, "rays by ray: this rank could not take the tile-binned path the other ranks take");
+    if (gate_folded) ctx->committed = false;                              // (small clouds: k_count's last workgroup was the gate)
+    else if (!sharded) { if ((rc = gate_impl(ctx, position_noise, orientation_noise, 0, nullptr, nullptr))) return rc; }
+    else {                                    // local sums + all-reduce + gate
+      if ((rc = gate_impl(ctx, 0.0, 0.0, 1, ctx->comm_sums, nullptr))) return rc;                                     // local sums -> device
+      CKN(ctx->rccl->AllReduce(ctx->comm_sums, ctx->comm_sums + 2, 2, ncclFloat64, ncclSum, ctx->comm, ctx->stream));   // exchange step 1
+      if (ctx->frame_binned) {                // the decision on the all-reduced totals rides in the head of the tile kernel
+        fr.gate_fold.mode = 1; fr.gate_fold.dev_totals = ctx->comm_sums + 2; fr.gate_fold.A = fr.gate;
+        ctx->committed = false;
+      } else if ((rc = gate_impl(ctx, position_noise, orientation_noise, 0, nullptr, ctx->comm_sums + 2))) return rc;
+    }
+  }
+  ctx->update_path = fused_small ? 2 : (ctx->frame_binned ? 1 : 0);
   STAGE(ST_FUSE);
+  // binned scatter: fusion, commit and averaging happen in ONE tile kernel; with the visibility pass it also writes the inert
+  // bitmap and the inlier plane, and the ray effects are applied by k_ray_apply ("average" stage) afterwards
   const bool fused_avg = ctx->frame_binned;
-  const bool rays_on = p.enable_visibility_cleanup != 0;
-  // clear_overlap_map rides on the kernel that rewrites the cells last (tile kernel, or k_ray_apply after a visibility pass)
-  ctx->ov_args = overlap_args(ctx, t[2], p.enable_overlap_clearance != 0);
-  const bool ov_folded = ctx->ov_args.on != 0;
-  rc = fuse_impl(ctx, R, t, fused_avg, rays_on);
-  const OverlapArgs ov = ctx->ov_args; ctx->ov_args.on = 0;
-  if (rc) return rc;
+  bool sem_merged = false;
+  if (!fused_small && (rc = fuse_impl(ctx, R, t, fused_avg, rays_on, &fr, &sem_merged))) return rc;
   STAGE(ST_COMMIT);
-  ctx->rays_fused = fused_avg && rays_on;
+  fr.rays_fused = fused_avg && rays_on;
   if (rays_on) {
     if (!fused_avg && (rc = emap_commit(ctx))) return rc;
     STAGE(ST_RAYS);
-    if (ctx->comm_world > 1 && normal_row_lag(ctx) != 0 && (rc = normal_exchange(ctx))) { ctx->rays_fused = false; ctx->byray_frame = false; ctx->nlag_ready = false; return rc; }
-    rc = ctx->byray_frame ? rays_by_ray_pass(ctx, R, t) : emap_rays(ctx, R, t);
-    ctx->byray_frame = false; ctx->nlag_ready = false;
-    if (rc) { ctx->rays_fused = false; return rc; }
+    if (sharded && ctx->comm_world > 1 && normal_row_lag(ctx) != 0) {
+      if ((rc = normal_exchange(ctx))) return rc;
+      fr.nlag = true;
+    }
+    if ((rc = fr.by_ray ? rays_by_ray_pass(ctx, R, t, &fr) : rays_impl(ctx, R, t, &fr))) return rc;
   } else STAGE(ST_RAYS);
   STAGE(ST_AVERAGE);
-  if (!fused_avg) { launch_average(ctx->stream, ctx->kp, ctx->cells, ctx->acc, ctx->accr, ctx->frame, ctx->committed, rays_on, ctx->cnt_plane, ov); ctx->kp.mv.n = 0; }
-  else if (rays_on) { launch_ray_apply(ctx->stream, ctx->kp, ctx->cells, ctx->accr, ctx->inert, ov, ctx->frame, ctx->split.need_host ? ctx->split.need_host + 1 : nullptr, ctx->ray_par ^= 1); ctx->inert_zero = true; }
-  ctx->committed = false; ctx->rays_fused = false;
+  if (fused_small) ctx->kp.mv.n = 0;                        // (k_small_frame committed and averaged: every cell rewritten)
+  else if (!fused_avg) { launch_average(ctx->stream, ctx->kp, ctx->cells, ctx->acc, ctx->accr, ctx->frame, ctx->committed, rays_on, ctx->cnt_plane, fr.ov); ctx->kp.mv.n = 0; }
+  else if (rays_on) { launch_ray_apply(ctx->stream, ctx->kp, ctx->cells, ctx->accr, ctx->inert, fr.ov, ctx->frame, ctx->split.need_host ? ctx->split.need_host + 1 : nullptr, ctx->ray_par ^= 1); ctx->inert_zero = true; }
+  ctx->committed = false;
   CK(hipGetLastError());
-  if ((rc = frame_sem_finish(ctx, R, t))) return rc;      // (as in emap_update)
-  STAGE(ST_OVERLAP);
-  if (p.enable_overlap_clearance && !ov_folded && (rc = emap_overlap_clear(ctx, t[2]))) return rc;
+  if ((rc = frame_sem_finish(ctx, R, t, sem_merged))) return rc;      // semantic_map.update_layers_pointcloud (elevation_mapping.py:368) -- unless the tile kernel fused the channels itself
+  STAGE(ST_OVERLAP);                          // (empty: clear_overlap_map rode on the kernel that rewrote the cells last, fr.ov)
   STAGE(ST_POST);                             // "post" = halo exchange + stencils
-  if (ctx->comm_world > 1) {
+  if (sharded && ctx->comm_world > 1) {
     if ((rc = halo_exchange_start(ctx))) return rc;                                                 // exchange step 2 ...
-    if ((rc = emap_post_part(ctx, 1))) return rc;                                                   // ... overlapped with the interior tiles
+    if ((rc = post_part_impl(ctx, 1))) return rc;                                                   // ... overlapped with the interior tiles
     CK(hipStreamWaitEvent(ctx->stream, ctx->ev_done, 0));
-    if ((rc = emap_post_part(ctx, 2))) return rc;
-  } else if ((rc = emap_post_part(ctx, 0))) return rc;
+    if ((rc = post_part_impl(ctx, 2))) return rc;
+  } else if ((rc = post_part_impl(ctx, 0))) return rc;
   STAGE(ST_N);
 #undef STAGE
   if (tm) {
