@@ -67,6 +67,26 @@ template <int MODE> __device__ __forceinline__ bool row_owned(const KP& P, const
 // staging record of the strip variants: what k_bin_scatter needs to place a point, computed once by k_bin_hist
 struct __attribute__((aligned(16))) BinStg { unsigned int key; float z, v; unsigned int i; };      // key = (bin << 16) | cell in bin
 
+// Which chunk of the cloud (= row of the (block, tile) matrix, region of the staging array) workgroup b of the two point passes takes.
+// A tile's records are the runs of chunks 0, 1, 2, ... one behind the other, about four records (64 bytes) each at 1 M points; workgroup b
+// runs on XCD b % 8 (observed dispatch rule, as in bin_of_block: for speed only), so with chunk = b every 128-byte line of the record
+// buffer is put together from pieces that lie dirty in two or three different L2s and each piece goes to memory on its own.  rho sends
+// the workgroups of one residue class mod 8 to CONSECUTIVE chunks: neighbouring runs of a tile then meet in one L2.  A bijection on
+// [0, B) for every B (B = 8 q + r: class x holds q + (x < r) workgroups and starts at chunk x q + min(x, r); B < 8 is the identity);
+// rows stay indexed by chunk, so the scan, the record order and every byte of the sorted records are what they were -- only who
+// writes them changes, and nothing depends on the placement for correctness.  -DBIN_XCD_ORDER=0: the identity (A/B builds).
+#ifndef BIN_XCD_ORDER
+#define BIN_XCD_ORDER 1
+#endif
+__device__ __forceinline__ unsigned int bin_chunk_of_block() {
+#if BIN_XCD_ORDER
+  const unsigned int b = blockIdx.x, B = gridDim.x, q = B >> 3, r = B & 7u, x = b & 7u, j = b >> 3;
+  return x * q + min(x, r) + j;
+#else
+  return blockIdx.x;
+#endif
+}
+
 // STRIP: the context owns a row strip and no visibility pass follows (see the header).  The staged records of block b are
 // stg[b * chunk ...], their number stg_cnt[b].
 #ifndef HIST_U
@@ -78,7 +98,8 @@ __global__ __launch_bounds__(BLK) void k_bin_hist(KP P, Pose T, BinGeo G, const 
                                                   unsigned int* __restrict__ stg_cnt) {
   extern __shared__ __attribute__((aligned(16))) unsigned int h[];
   for (int t = threadIdx.x; t < G.TB; t += BLK) h[t] = 0u;
-  const long base = (long)blockIdx.x * G.chunk;
+  const unsigned int blk = bin_chunk_of_block();             // the chunk this workgroup takes
+  const long base = (long)blk * G.chunk;
   if (!STRIP) {
     __syncthreads();
     constexpr int U = HIST_U;                                  // loads in flight per thread (as in k_bin_scatter)
@@ -143,10 +164,10 @@ __global__ __launch_bounds__(BLK) void k_bin_hist(KP P, Pose T, BinGeo G, const 
     }
     if (qn > 0) work(0, qn);
     __syncthreads();
-    if (threadIdx.x == 0) stg_cnt[blockIdx.x] = *blk_cnt;
+    if (threadIdx.x == 0) stg_cnt[blk] = *blk_cnt;
   }
   __syncthreads();
-  unsigned int* row = hist + (long)blockIdx.x * G.pitch;
+  unsigned int* row = hist + (long)blk * G.pitch;
   for (int t = threadIdx.x; t < G.pitch; t += BLK) row[t] = t < G.TB ? h[t] : 0u;
 }
 
@@ -264,10 +285,11 @@ __global__ __launch_bounds__(BLK) void k_bin_scatter(KP P, Pose T, BinGeo G, con
                                                      const unsigned int* __restrict__ stg_cnt, ChanView V, SemCarry SC) {
   static_assert(!(STRIP && CH), "a strip's staged records carry no channels");
   extern __shared__ unsigned int cur[];
-  const unsigned int* row = hist + (long)blockIdx.x * G.pitch;
+  const unsigned int blk = bin_chunk_of_block();             // the chunk this workgroup takes (the one its twin in k_bin_hist counted)
+  const unsigned int* row = hist + (long)blk * G.pitch;
   for (int t = threadIdx.x; t < G.TB; t += BLK) cur[t] = tile_start[t] + row[t];
   __syncthreads();
-  const long base = (long)blockIdx.x * G.chunk;
+  const long base = (long)blk * G.chunk;
   // SCATTER_U loads in flight per thread (round 5): a block is ONE workgroup of eight waves on its CU (245 blocks of 4096 points at
   // 1 M points; 253 blocks and a 64-KB cursor array at 16 M), and a thread that walks its eight points one dependent load at a time
   // spends the pass waiting -- 8 round trips of ~1.5 us were the 13 us the pass took.
@@ -299,12 +321,12 @@ __global__ __launch_bounds__(BLK) void k_bin_scatter(KP P, Pose T, BinGeo G, con
           reinterpret_cast<BinRec32*>(recs)[pos] = o;
         } else {
           BinRec o; o.lc_inl = lc; o.z = g.z; o.v = g.v; o.i = (unsigned int)i;
-          recs[pos] = o;
+          recs[pos] = o;            // (plain: as write-through stores the scattered records cost the pass 2-3 us more, nt stores 3x -- DESIGN.md section 5)
         }
       }
     }
   } else {
-    const unsigned int m = stg_cnt[blockIdx.x];              // a pure permutation of the block's staged records
+    const unsigned int m = stg_cnt[blk];              // a pure permutation of the block's staged records
     for (unsigned int j0 = threadIdx.x; j0 < m; j0 += U * BLK) {
       BinStg r[U];
 #pragma unroll
@@ -671,8 +693,17 @@ __device__ __forceinline__ void tile_fuse_body(const KP& P, const BinGeo& G, con
           // points -- and its 16 bytes of write traffic stay away (round 5; the staged copy in LDS is what memory holds).
           if (P.mv.n == 0) whot = (__float_as_uint(m.h) ^ __float_as_uint(hq0.x)) | (__float_as_uint(m.v) ^ __float_as_uint(hq0.y)) |
                                   (__float_as_uint(m.valid) ^ __float_as_uint(hq0.z)) | (__float_as_uint(m.trav) ^ __float_as_uint(hq0.w));
-          if (whot) cells.hot[c] = make_float4(m.h, m.v, m.valid, m.trav);
-          if (wcold) cells.cold[c] = make_float4(m.time, m.upper, m.is_upper, m.valid);
+          // written THROUGH (st16_wt, emap_device.h) in launches of one or two rounds of workgroups (G.wt, uniform: launch_bin_fuse): plain
+          // stores would all lie dirty in L2 when the kernel ends; nothing in this launch reads the two halves again (the semantic pass
+          // below works on LDS and the semantic planes): 13.3 -> 11.1 us at 1024^2 / 1 M points.  The 4-byte planes behind them stay plain.
+          const float4 hot_out = make_float4(m.h, m.v, m.valid, m.trav), cold_out = make_float4(m.time, m.upper, m.is_upper, m.valid);
+          if (G.wt) {
+            if (whot) st16_wt(&cells.hot[c], hot_out);
+            if (wcold) st16_wt(&cells.cold[c], cold_out);
+          } else {
+            if (whot) cells.hot[c] = hot_out;
+            if (wcold) cells.cold[c] = cold_out;
+          }
           if (cnt_plane) cnt_plane[c] = s_cnt[lc];
           if (RAYS) inl_plane[c] = s_inl[lc];
         } else acc[c] = a;
@@ -861,12 +892,20 @@ void launch_tile_count(hipStream_t s, const KP& P, const BinGeo& G, const BinRec
 // commits + averages itself, without a visibility pass and without heavy-tile parts in the launch
 bool bin_fuse_takes_semantics(const SplitView& SV, bool fuse_average, bool rays, int rs) { return rs == 2 && fuse_average && !rays && !(SV.on && SV.cap > 0); }
 // rs: record stride in 16-byte units; sm (may be null): the frame's semantic fusion, run inside the kernel when bin_fuse_takes_semantics()
-void launch_bin_fuse(hipStream_t s, const KP& P, const BinGeo& G, const BinRec* recs, int rs, const unsigned int* tile_start, Cells cells,
+// Write-through cell stores (st16_wt) pay where everything the launch stores is still dirty in L2 when it ends: a tile workgroup writes
+// at most 32 KB of cells, the eight L2s hold 32 MB -- up to 1024 workgroups, two rounds of the 512 resident ones (1024^2: 13.3 -> 11.1 us).
+// A launch of many rounds (8192^2: 128) leaves only its last 32 MB dirty whatever its size: at most ~2 us to gain in a millisecond.
+// Measured there (8192^2 / 16 M points, written through in every launch): once 3.03 -> 3.30 ms per frame, once no difference on a
+// box that ran both builds at 3.31 ms -- nothing to win and possibly something to lose, so those keep plain stores.
+#define FUSE_WT_MAX_WGS 1024u
+void launch_bin_fuse(hipStream_t s, const KP& P, const BinGeo& G_, const BinRec* recs, int rs, const unsigned int* tile_start, Cells cells,
                      AccF* acc, FrameDev* F, bool fuse_average, bool rays, unsigned int* cnt_plane, unsigned long long* inert,
                      unsigned int* inl_plane, float* thr, const OverlapArgs& O, const GateFold& GF, const SplitView& SV, long n, const SemMini* sm) {
   (void)n;
   const bool split = SV.on && SV.cap > 0;
+  BinGeo G = G_;
   const dim3 g((split ? (unsigned int)SV.cap * G.sub : 0u) + tile_grid(G)), b(TF_BLOCK);
+  G.wt = g.x <= FUSE_WT_MAX_WGS;
   SemMini SM; memset(&SM, 0, sizeof SM);
 #define EM_FUSE_I(A, R, SP, RS_, SE) hipLaunchKernelGGL((k_tile_fuse<A, R, SP, RS_, SE>), g, b, 0, s, P, G, recs, tile_start, cells, acc, F, cnt_plane, inert, inl_plane, thr, O, GF, SV, SM)
 #define EM_FUSE(A, R) do { if (split) EM_FUSE_I(A, R, true, 1, false); else EM_FUSE_I(A, R, false, 1, false); } while (0)

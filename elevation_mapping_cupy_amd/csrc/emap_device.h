@@ -509,7 +509,7 @@ __device__ __forceinline__ bool overlap_cell(const KP& P, const OverlapArgs& O, 
 // valid points that fall OUTSIDE the owned cells when a visibility pass follows (raybin) -- they are not fused, but their rays are
 // marched (k_rays walks the sorted records).  B blocks of `chunk` points; pitch = row pitch of the (block, tile) matrix in words
 // (a multiple of 4).
-struct BinGeo { int tiles_x, tiles_y, T, B; long chunk; int sub, TB, pitch, raybin; };
+struct BinGeo { int tiles_x, tiles_y, T, B; long chunk; int sub, TB, pitch, raybin; int wt; };      // wt: set per launch by launch_bin_fuse (write-through cell stores)
 struct __attribute__((aligned(16))) BinRec { unsigned int lc_inl; float z, v; unsigned int i; };  // sorted by tile
 struct BinStg;                                                                                     // staging record of the strip variants
 // Records of a frame that CARRIES its semantic channels (round 6): the sorted record is 32 bytes -- the 16 above + the point's four
@@ -579,6 +579,29 @@ __device__ __forceinline__ void lds_dma16(const void* gsrc_lane, void* lds_base_
 }
 __device__ __forceinline__ void lds_dma16_at(const void* gsrc_lane, unsigned int lds_byte_offset_uniform) {      // destination given as an LDS byte offset
   __builtin_amdgcn_global_load_lds((em_glb_void*)gsrc_lane, (em_lds_void*)(size_t)lds_byte_offset_uniform, 16, 0, 0);
+}
+
+// ---- 16-byte WRITE-THROUGH store (global_store_dwordx4 ... sc1) -----------------------------------------------------------------
+// A plain store leaves its line dirty in the XCD's L2, and what is still dirty when the kernel ends goes to memory behind its body (a
+// kernel of one or two rounds of workgroups: nearly all of it); an sc1 store goes through while the kernel still runs and DROPS the
+// line from L2 -- so only for bytes nothing in the same launch reads again.  Streaming 32 MB in and out, followed by a dependent kernel:
+// 12.6 us with plain stores, 10.7 us written through, 6.7 us without the stores (tools/microbench.hip, `wb`).
+// Inline asm because the builtin with cache bits (raw_buffer_store_b128) addresses through a 32-bit buffer offset and the planes of
+// the largest maps pass 4 GB.  The compiler does not count the store -- nothing waits for it, and as memory operations return in order
+// it can only make the compiler's later waits conservative -- and pads nothing behind it: the s_nop keeps the next instruction off
+// the data registers.  Meant for launches whose stores all fit in L2: a launch of many rounds has its lines evicted under its own body
+// and only the last 32 MB are left at its end, so there is little to gain (launch_bin_fuse decides).  -DEMAP_WT_STORES=0: plain stores (A/B builds).
+#ifndef EMAP_WT_STORES
+#define EMAP_WT_STORES 1
+#endif
+__device__ __forceinline__ void st16_wt(float4* p, const float4 v) {
+#if EMAP_WT_STORES
+  typedef float em_f4v __attribute__((ext_vector_type(4)));
+  const em_f4v x = {v.x, v.y, v.z, v.w};
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(x) : "memory");
+#else
+  *p = v;
+#endif
 }
 
 // ---- host: raising a kernel's dynamic LDS limit beyond the default 64 KB ---------------------------------------------------

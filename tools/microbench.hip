@@ -1,6 +1,6 @@
 // Micro-benchmarks behind DESIGN.md's kernel decisions (not part of the product).  hipcc --offload-arch=gfx950 -O3
 // Measures the cost components of the point->cell scatter on MI355X: geometry ALU, cell gather, atomics by width /
-// scope / record layout / spatial coherence.
+// scope / record layout / spatial coherence.  `microbench wb [MB]`: what a kernel's dirty bytes cost at its end, by store flavour.
 #include "../elevation_mapping_cupy_amd/csrc/emap_device.h"
 #include <cstdio>
 #include <cstring>
@@ -75,6 +75,31 @@ __global__ void k_count_like(KP P, Pose T, const float* pts, long n, const Cell*
   }
 }
 
+// ---- write-back case (`microbench wb`): does a kernel pay for the bytes it leaves dirty in L2 AFTER its body? ----------------------
+// A streaming kernel reads `bytes` and (W != 0) writes `bytes` with one store flavour, as `wgs` workgroups of 1024 threads: 512 = one
+// round of resident workgroups on 256 CUs, 1024 = two.  It is timed TOGETHER with a trivial dependent kernel behind it, so the time
+// includes whatever the boundary costs.  W: 0 none, 1 plain 16 B, 2 sc1 16 B (write-through), 3 nt 16 B, 4 plain 4 B, 5 sc1 4 B.
+typedef float wb_f4 __attribute__((ext_vector_type(4)));
+template <int W> __global__ __launch_bounds__(1024) void k_wb_stream(const float4* __restrict__ src, float4* __restrict__ dst, long n16, float* sink) {
+  const long per = (n16 + gridDim.x - 1) / gridDim.x, lo = (long)blockIdx.x * per, hi = min(n16, lo + per);
+  float keep = 0.f;
+  for (long i = lo + threadIdx.x; i < hi; i += 1024) {
+    float4 v = src[i];
+    v.x = v.x * 1.5f + v.y; v.y = v.y * 0.5f + v.z; v.z += v.w; v.w += 1.0f;
+    if (W == 0) keep += v.x + v.y + v.z + v.w;
+    if (W == 1) dst[i] = v;
+    if (W == 2) st16_wt(&dst[i], v);
+    if (W == 3) { wb_f4 x = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(x, reinterpret_cast<wb_f4*>(&dst[i])); }
+    if (W == 4 && i - threadIdx.x + 1024 <= hi) { float* d = reinterpret_cast<float*>(dst) + (i - threadIdx.x) * 4 + threadIdx.x;      // 4-byte lane stores, four coalesced rows per trip
+                  d[0] = v.x; d[1024] = v.y; d[2048] = v.z; d[3072] = v.w; }
+    if (W == 5 && i - threadIdx.x + 1024 <= hi) { float* d = reinterpret_cast<float*>(dst) + (i - threadIdx.x) * 4 + threadIdx.x;
+                  __hip_atomic_store(d, v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(d + 1024, v.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                  __hip_atomic_store(d + 2048, v.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(d + 3072, v.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  }
+  if (W == 0 && keep == 12345.678f) *sink = keep;
+}
+__global__ void k_wb_after(const float4* __restrict__ dst, float* sink) { if (dst[(long)blockIdx.x * 256 + threadIdx.x].x == 12345.678f) *sink = 1.f; }
+
 template <class F> float timeit(F f, int reps = 20) {
   hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
   f(); hipDeviceSynchronize();
@@ -82,7 +107,37 @@ template <class F> float timeit(F f, int reps = 20) {
   float ms; hipEventElapsedTime(&ms, a, b); return ms * 1000.f / reps;
 }
 
+static int wb_main(int argc, char** argv) {
+  const long mb = argc > 2 ? atol(argv[2]) : 32; const long n16 = std::max(1l, mb / 16) << 20;                 // 16-MB steps: every workgroup of 512 or 1024 gets whole trips of 1024 float4
+  float4 *src, *dst; float* sink; CK(hipMalloc(&src, 16 * n16)); CK(hipMalloc(&dst, 16 * n16)); CK(hipMalloc(&sink, 4));
+  CK(hipMemset(src, 0, 16 * n16)); CK(hipMemset(dst, 0, 16 * n16));
+  printf("write-back case: %ld MB read (+ written) per launch, + a trivial dependent kernel (us per pair, median of 7 x 50 pairs)\n", n16 >> 16);
+  const char* names[6] = {"no stores", "plain 16 B", "sc1 16 B", "nt 16 B", "plain 4 B", "sc1 4 B"};
+  for (int wgs : {512, 1024}) {
+    for (int w = 0; w < 6; ++w) {
+      auto pair = [&] {
+        const dim3 g(wgs), b(1024);
+        switch (w) {
+          case 0: hipLaunchKernelGGL((k_wb_stream<0>), g, b, 0, 0, src, dst, n16, sink); break;
+          case 1: hipLaunchKernelGGL((k_wb_stream<1>), g, b, 0, 0, src, dst, n16, sink); break;
+          case 2: hipLaunchKernelGGL((k_wb_stream<2>), g, b, 0, 0, src, dst, n16, sink); break;
+          case 3: hipLaunchKernelGGL((k_wb_stream<3>), g, b, 0, 0, src, dst, n16, sink); break;
+          case 4: hipLaunchKernelGGL((k_wb_stream<4>), g, b, 0, 0, src, dst, n16, sink); break;
+          default: hipLaunchKernelGGL((k_wb_stream<5>), g, b, 0, 0, src, dst, n16, sink);
+        }
+        hipLaunchKernelGGL(k_wb_after, dim3(256), dim3(256), 0, 0, dst, sink);
+      };
+      std::vector<float> t; for (int r = 0; r < 7; ++r) t.push_back(timeit(pair, 50));
+      std::sort(t.begin(), t.end());
+      printf("  %5d workgroups  %-12s %8.2f  (min %.2f max %.2f)\n", wgs, names[w], t[3], t[0], t[6]);
+    }
+  }
+  CK(hipDeviceSynchronize());
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "wb")) return wb_main(argc, argv);
   const int C = argc > 1 ? atoi(argv[1]) : 1024; const long N = argc > 2 ? atol(argv[2]) : 1000000; const long L = (long)C * C;
   KP P; memset(&P, 0, sizeof P);
   P.C = C; P.mode = 0; P.row0 = 0; P.nrows = C; P.halo = 0; P.edge = 1; P.dil = 3; P.res = 0.04; P.half_w = 0.5 * C; P.snf = 0.05; P.mt = 2.0;
