@@ -9,8 +9,8 @@
     segments that end inside a wave's four rows), and a map width that is no multiple of 64 (a partial last column tile).  These are the
     cases in which a 16-byte-per-lane store path of k_post has fast and fallback waves in one launch; that path was built, measured
     slower than the 4-byte stores and taken out again -- the cases stay as the pin for the next attempt.
-k_post_dma is not covered here: the launcher picks it for 16-row tiles only (4096^2-class maps).  No test asserts a timing or a
-placement."""
+k_post_dma and the other tile heights of k_post are covered by tests/test_hip_post_variants.py (small maps, launcher hooks, one
+process per variant).  No test asserts a timing or a placement."""
 import threading
 
 import numpy as np
