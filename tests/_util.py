@@ -47,6 +47,21 @@ def assert_planes_equal(a, b, names=PLANE_NAMES, what=""):
                 what, name, int(bad.sum()), float(np.nanmax(np.abs(a[k].astype(np.float64) - b[k].astype(np.float64)))), i, a[k][i], b[k][i]))
 
 
+def kernel_trace_rows(trace_dir):
+    """(name, lds_size) of the dispatches of a rocprofv3 kernel trace in start order (the `kernels` view tools/rocprof_summary.py reads)"""
+    import glob
+    import os
+    import sqlite3
+    rows = []
+    dbs = sorted(glob.glob(os.path.join(trace_dir, "*", "*_results.db")))
+    assert dbs, "rocprofv3 left no *_results.db under %s" % trace_dir
+    for db in dbs:
+        con = sqlite3.connect(db)
+        rows += con.execute("select start, name, lds_size from kernels").fetchall()
+        con.close()
+    return [(n, int(l or 0)) for _, n, l in sorted(rows)]
+
+
 def rccl_stand_in(kind="blocking"):
     """Builds one of the in-process stand-ins for the ten RCCL entry points (tests/fake_rccl/) and returns the path to hand to
     emap_comm_init: "blocking" = fake_rccl.cpp (host-synchronised copies, g++), "stream" = stream_rccl.hip (stream-ordered events +

@@ -11,12 +11,10 @@ hook selected the kernel the values are credited to (a hook that silently fell b
 The twelve instantiations the launcher can reach are k_post<4|8|16|32, 0|1> and k_post_dma<16|32, 0|1>; k_post_dma<4|8, .> are compiled
 but unreachable (post_use_dma requires R >= 16).  The expectation below is a decision table derived by hand from post_tile_rows,
 post_use_dma and the LDS formulas and kept as literals on purpose: it is not recomputed from a copy of the launcher's arithmetic."""
-import glob
 import os
 import re
 import shutil
 import signal
-import sqlite3
 import subprocess
 import sys
 import time
@@ -25,7 +23,7 @@ import numpy as np
 import pytest
 
 import _post_variants as pv
-from _util import assert_planes_equal, make_pair
+from _util import assert_planes_equal, kernel_trace_rows, make_pair
 from oracle import emap_oracle as eo
 
 pytestmark = pytest.mark.gpu
@@ -72,15 +70,8 @@ def reachable_instantiations():
 
 
 def _kernel_names(trace_dir):
-    """the dispatches of a rocprofv3 kernel trace in start order (the `kernels` view tools/rocprof_summary.py reads)"""
-    rows = []
-    dbs = sorted(glob.glob(os.path.join(trace_dir, "*", "*_results.db")))
-    assert dbs, "rocprofv3 left no *_results.db under %s" % trace_dir
-    for db in dbs:
-        con = sqlite3.connect(db)
-        rows += con.execute("select start, name from kernels").fetchall()
-        con.close()
-    return [n for _, n in sorted(rows)]
+    """the dispatches of a rocprofv3 kernel trace in start order"""
+    return [n for n, _ in kernel_trace_rows(trace_dir)]
 
 
 def _run_child(variant, tmp):
