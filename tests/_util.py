@@ -47,8 +47,7 @@ def assert_planes_equal(a, b, names=PLANE_NAMES, what=""):
                 what, name, int(bad.sum()), float(np.nanmax(np.abs(a[k].astype(np.float64) - b[k].astype(np.float64)))), i, a[k][i], b[k][i]))
 
 
-def kernel_trace_rows(trace_dir):
-    """(name, lds_size) of the dispatches of a rocprofv3 kernel trace in start order (the `kernels` view tools/rocprof_summary.py reads)"""
+def _kernel_trace(trace_dir, columns):
     import glob
     import os
     import sqlite3
@@ -57,9 +56,20 @@ def kernel_trace_rows(trace_dir):
     assert dbs, "rocprofv3 left no *_results.db under %s" % trace_dir
     for db in dbs:
         con = sqlite3.connect(db)
-        rows += con.execute("select start, name, lds_size from kernels").fetchall()
+        rows += con.execute("select start, name, %s from kernels" % columns).fetchall()
         con.close()
-    return [(n, int(l or 0)) for _, n, l in sorted(rows)]
+    return sorted(rows)
+
+
+def kernel_trace_rows(trace_dir):
+    """(name, lds_size) of the dispatches of a rocprofv3 kernel trace in start order (the `kernels` view tools/rocprof_summary.py reads)"""
+    return [(n, int(l or 0)) for _, n, l in _kernel_trace(trace_dir, "lds_size")]
+
+
+def kernel_trace_grid_rows(trace_dir):
+    """(name, lds_size, grid_x, workgroup_x) of the dispatches of a rocprofv3 kernel trace in start order; grid_x counts WORK-ITEMS
+    (grid_x // workgroup_x workgroups)"""
+    return [(n, int(l or 0), int(g or 0), int(w or 0)) for _, n, l, g, w in _kernel_trace(trace_dir, "lds_size, grid_x, workgroup_x")]
 
 
 def rccl_stand_in(kind="blocking"):
