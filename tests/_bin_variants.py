@@ -16,7 +16,6 @@ frames that declare an RGB / semantic fusion, "strip" = two row strips as thread
 OFF the sensor, so that the squeezed points stay beyond min_valid_distance -- | ("tile",): all points in one 16 x 64 tile (tile_cloud) |
 ("semantic",): fx.semantic_cloud.  `heavy_from`: the first frame in which a sort bin holds more than 4096 records (None: never) --
 tests/test_bin_variant_cases.py checks the column against the oracle's point_index."""
-import os
 import sys
 
 import numpy as np
@@ -257,11 +256,8 @@ def _run_hip(case, weights, out):
 
 
 def main(path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if root not in sys.path:
-        sys.path.insert(0, root)
-    w = np.load(os.path.join(root, "tests", "golden", "weights.npz"))
-    weights = {k: w[k] for k in ("w1", "w2", "w3", "w_out")}
+    from _variant_children import child_setup
+    weights = child_setup()
     out = {}
     for case in CASES:
         _run_hip(case, weights, out)

@@ -5,7 +5,6 @@ executes every case on the GPU with whatever tile height / kernel the EMAP_POST_
     python tests/_post_variants.py <out.npz>
 
 The parent builds the same states with state() and compares the recorded arrays with the oracle."""
-import os
 import sys
 
 import numpy as np
@@ -113,13 +112,10 @@ def _record(out, key, hip):
 
 
 def main(path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if root not in sys.path:
-        sys.path.insert(0, root)
+    from _variant_children import child_setup
+    weights = child_setup()
     from _util import make_pair
     from oracle import emap_oracle as eo
-    w = np.load(os.path.join(root, "tests", "golden", "weights.npz"))
-    weights = {k: w[k] for k in ("w1", "w2", "w3", "w_out")}
     out = {}
     for C, d in CASES:
         cfg = dict(eo.YAML, dilation_size=d)

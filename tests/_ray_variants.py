@@ -6,7 +6,6 @@ EMAP_RAY_LMAP and EMAP_RAY_WINDOW once per process; emap_api.hip: build_ray_tabl
 
 Every case is two whole frames with rays and overlap clearance on a fresh context.  The parent runs the same calls on the oracle
 (run_case) and compares the recorded arrays."""
-import os
 import sys
 
 import numpy as np
@@ -110,13 +109,10 @@ def oracle_run(case, weights, cleanup=True):
 
 
 def main(path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if root not in sys.path:
-        sys.path.insert(0, root)
+    from _variant_children import child_setup
+    weights = child_setup()
     from _util import make_pair
     from oracle import emap_oracle as eo
-    w = np.load(os.path.join(root, "tests", "golden", "weights.npz"))
-    weights = {k: w[k] for k in ("w1", "w2", "w3", "w_out")}
     out = {}
     for case in CASES:
         hip, _ = make_pair(case_config(case, eo.YAML), case["C"], case["mode"], weights)

@@ -31,20 +31,14 @@ branches of the kernel are independent, tests/test_hip_frame_semantics.py runs f
 false> and k_tile_semantic<false, 2> (32-byte records exist only in frames with a declaration, and those fuse in the tile kernel unless
 the launch holds parts); k_tile_fuse<false, false, ., 2, false> (the staged count stage never carries channels)."""
 import os
-import re
-import shutil
-import signal
-import subprocess
-import sys
-import time
 from collections import Counter
 
 import numpy as np
 import pytest
 
 import _bin_variants as bv
+import _variant_children as vc
 from _util import assert_planes_equal, kernel_trace_grid_rows
-from oracle import emap_oracle as eo
 
 pytestmark = pytest.mark.gpu
 
@@ -85,7 +79,6 @@ HIST_WGS = {
 # kernels on a strip context 2048 (14 and 25)
 STRIP_HIST_WGS = {"default": {27000: 7, 50000: 13}, "plain": {27000: 14, 50000: 25}}
 
-HIP_ERROR = re.compile(r"hipError|HIP error|HSA_STATUS_ERROR|illegal memory access|Memory access fault|GPU core dump", re.I)
 B = ("false", "true")
 
 
@@ -154,53 +147,12 @@ def reachable_instantiations(deterministic_only=False):
     return out
 
 
-TYPES = {"k_bin_hist": "iib", "k_bin_scatter": "iibb", "k_tile_count": "bi", "k_tile_fuse": "bbbib", "k_tile_semantic": "bi"}
-
-
-def _canonical(name):
-    """the traced dispatch name of one of the six kernels with its template arguments in one spelling, None for every other kernel"""
-    if re.search(r"\bk_bin_scan\b", name):
-        return "k_bin_scan"
-    m = re.search(r"\b(k_bin_hist|k_bin_scatter|k_tile_count|k_tile_fuse|k_tile_semantic)<([^<>]*)>", name)
-    if not m:
-        return None
-    a = [x.strip() for x in m.group(2).split(",")]
-    types = TYPES[m.group(1)]
-    if len(a) != len(types):
-        return "%s<%s>" % (m.group(1), m.group(2))
-    flag = {"true": "true", "false": "false", "(bool)1": "true", "(bool)0": "false", "1": "true", "0": "false"}
-    return "%s<%s>" % (m.group(1), ", ".join(flag[x] if ty == "b" else str(int(x)) for x, ty in zip(a, types)))
-
-
-class BadExit(Exception):
-    """a child that ran into its time limit, was ended by a signal, exited with an error or reported a HIP error"""
+TYPES = {"k_bin_hist": "iib", "k_bin_scan": "", "k_bin_scatter": "iibb", "k_tile_count": "bi", "k_tile_fuse": "bbbib", "k_tile_semantic": "bi"}
 
 
 def _run_child(variant, tmp):
-    env = {k: v for k, v in os.environ.items() if k not in HOOKS}
-    env.update(VARIANTS[variant])
-    prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
-    assert os.path.exists(prof), "rocprofv3 not found: the kernel selection cannot be verified"
-    out, trace = os.path.join(tmp, "out.npz"), os.path.join(tmp, "trace")
-    child = os.path.join(os.path.dirname(os.path.abspath(bv.__file__)), "_bin_variants.py")
-    cmd = [prof, "--kernel-trace", "-d", trace, "--", sys.executable, child, out]
-    t0 = time.time()
-    p = subprocess.Popen(cmd, env=env, stdin=subprocess.DEVNULL, stdout=subprocess.PIPE, stderr=subprocess.PIPE, start_new_session=True)
-    try:
-        _, err = p.communicate(timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        os.killpg(p.pid, signal.SIGKILL)
-        _, err = p.communicate()
-        raise BadExit("variant %s: the child ran into its time limit of %d s; stderr ends:\n%s" % (variant, CHILD_TIMEOUT_S, err.decode(errors="replace")[-3000:]))
-    print("variant %s: child took %.1f s" % (variant, time.time() - t0))
-    err = err.decode(errors="replace")
-    if p.returncode != 0:
-        raise BadExit("variant %s: the child exited with %d; stderr ends:\n%s" % (variant, p.returncode, err[-3000:]))
-    if HIP_ERROR.search(err):
-        raise BadExit("variant %s: the child's stderr names a HIP error:\n%s" % (variant, err[-3000:]))
-    with np.load(out) as z:
-        arrays = {k: z[k] for k in z.files}
-    rows = [(c, g // w) for c, g, w in ((_canonical(n), g, w) for n, _, g, w in kernel_trace_grid_rows(trace)) if c]
+    arrays, trace = vc.run_child(os.path.abspath(bv.__file__), variant, VARIANTS[variant], HOOKS, tmp, CHILD_TIMEOUT_S)
+    rows = [(c, g // w) for c, g, w in ((vc.canonical_kernel_name(n, TYPES), g, w) for n, _, g, w in kernel_trace_grid_rows(trace)) if c]
     return arrays, _segments(variant, rows)
 
 
@@ -226,44 +178,14 @@ def _segments(variant, rows):
 @pytest.fixture(scope="module")
 def children(tmp_path_factory):
     """variant -> (recorded arrays, dispatches per case and frame): one child per variant, started the first time a test needs it, never
-    twice.  After a bad exit (BadExit) NO further child is started: a process that faulted or hung may have left the device in a state
-    in which the next one does the same, so every test that still needs a child fails with that first message.  A child that merely
-    computed wrong values stops nothing."""
-    done, halted = {}, []
-
-    def get(variant):
-        if variant not in done:
-            if halted:
-                pytest.fail("not started: an earlier child ended badly -- %s" % halted[0], pytrace=False)
-            try:
-                done[variant] = _run_child(variant, str(tmp_path_factory.mktemp("bins_" + variant)))
-            except BadExit as e:
-                halted.append(str(e))
-                done[variant] = e
-            except Exception as e:          # remembered, not retried
-                done[variant] = e
-        if isinstance(done[variant], Exception):
-            pytest.fail("%s" % done[variant], pytrace=False)
-        return done[variant]
-
-    return get
+    twice; after a child that ended badly none is started (tests/_variant_children.py)"""
+    return vc.lazy_children(lambda v: _run_child(v, str(tmp_path_factory.mktemp("bins_" + v))))
 
 
 @pytest.fixture(scope="module")
 def oracle(weights):
     """case key -> the oracle's arrays (bv.oracle_run), computed once, read-only"""
-    done = {}
-
-    def get(key):
-        if key not in done:
-            eo.set_threads(8)
-            try:
-                done[key] = bv.oracle_run(bv.case_of(key), weights)
-            finally:
-                eo.set_threads(1)
-        return done[key]
-
-    return get
+    return vc.cached_oracle(lambda key: bv.oracle_run(bv.case_of(key), weights))
 
 
 SINGLE = [k for k in bv.KEYS if bv.case_of(k)["kind"] != "strip"]
@@ -280,9 +202,7 @@ def test_values_equal_the_oracle(variant, key, children, oracle):
     frames = bv.case_of(key)["frames"]
     if bv.case_of(key)["kind"] != "staged":
         assert list(got[key + "_path"]) == ["binned"] * frames, (what, got[key + "_path"])
-    assert_planes_equal(got[key + "_map"], want["map"], what=what)
-    assert_planes_equal(got[key + "_normal"], want["normal"], names=["nx", "ny", "nz"], what=what)
-    assert_planes_equal(got[key + "_trav_in"][None], want["trav_in"][None], names=["traversability_input"], what=what)
+    vc.assert_case_planes(got, key, want["map"], want["normal"], want["trav_in"], what)
     assert float(got[key + "_add"][0]) == float(want["add"][0]), (what, got[key + "_add"], want["add"])
 
 

@@ -13,17 +13,13 @@ but unreachable (post_use_dma requires R >= 16).  The expectation below is a dec
 post_use_dma and the LDS formulas and kept as literals on purpose: it is not recomputed from a copy of the launcher's arithmetic."""
 import os
 import re
-import shutil
-import signal
-import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
 
 import _post_variants as pv
-from _util import assert_planes_equal, kernel_trace_rows, make_pair
+import _variant_children as vc
+from _util import kernel_trace_rows, make_pair
 from oracle import emap_oracle as eo
 
 pytestmark = pytest.mark.gpu
@@ -75,84 +71,45 @@ def _kernel_names(trace_dir):
 
 
 def _run_child(variant, tmp):
-    env = {k: v for k, v in os.environ.items() if not k.startswith("EMAP_POST_")}
-    env.update(VARIANTS[variant])
-    prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
-    assert os.path.exists(prof), "rocprofv3 not found: the kernel selection cannot be verified"
-    out, trace = os.path.join(tmp, "out.npz"), os.path.join(tmp, "trace")
-    child = os.path.join(os.path.dirname(os.path.abspath(pv.__file__)), "_post_variants.py")
-    cmd = [prof, "--kernel-trace", "-d", trace, "--", sys.executable, child, out]
-    t0 = time.time()
-    p = subprocess.Popen(cmd, env=env, stdin=subprocess.DEVNULL, stdout=subprocess.PIPE, stderr=subprocess.PIPE, start_new_session=True)
-    try:
-        _, err = p.communicate(timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        os.killpg(p.pid, signal.SIGKILL)
-        _, err = p.communicate()
-        raise AssertionError("variant %s: the child ran into its time limit of %d s; stderr ends:\n%s" % (variant, CHILD_TIMEOUT_S, err.decode(errors="replace")[-3000:]))
-    print("variant %s: child took %.1f s" % (variant, time.time() - t0))
-    assert p.returncode == 0, "variant %s: the child exited with %d; stderr ends:\n%s" % (variant, p.returncode, err.decode(errors="replace")[-3000:])
-    with np.load(out) as z:
-        arrays = {k: z[k] for k in z.files}
+    arrays, trace = vc.run_child(os.path.abspath(pv.__file__), variant, VARIANTS[variant], lambda k: k.startswith("EMAP_POST_"), tmp, CHILD_TIMEOUT_S)
     names = [m.group(1) for m in (re.match(r"void (k_post(?:_dma)?<\d+, [01]>)", n) for n in _kernel_names(trace)) if m]
     return arrays, names
 
 
 @pytest.fixture(scope="module")
 def children(tmp_path_factory):
-    """variant -> (recorded arrays, k_post* dispatch names): one child per variant, started the first time a test needs it, never twice --
-    a child that failed fails every test of its variant with the same message"""
-    done = {}
+    """variant -> (recorded arrays, k_post* dispatch names): one child per variant, started the first time a test needs it, never twice;
+    after a child that ended badly none is started (tests/_variant_children.py)"""
+    return vc.lazy_children(lambda v: _run_child(v, str(tmp_path_factory.mktemp("post_" + v))))
 
-    def get(variant):
-        if variant not in done:
-            try:
-                done[variant] = _run_child(variant, str(tmp_path_factory.mktemp("post_" + variant)))
-            except Exception as e:          # remembered, not retried
-                done[variant] = e
-        if isinstance(done[variant], Exception):
-            pytest.fail("%s" % done[variant], pytrace=False)
-        return done[variant]
 
-    return get
+def _oracle_case(key, weights):
+    if key == pv.FRAME_KEY:
+        _, orc = make_pair(eo.YAML, pv.FRAME["C"], "reference_fp16", weights)
+        pv.run_frames(orc, False)
+        dil = None
+    else:
+        C, d = next(c for c in pv.CASES if pv.case_key(*c) == key)
+        _, orc = make_pair(dict(eo.YAML, dilation_size=d), C, "reference_fp16", weights)
+        orc.elevation_map[...] = pv.state(C, d, pv.case_seed(C, d))
+        orc.dilate()
+        dil = orc.traversability_input.copy()
+        orc.traversability(); orc.normals()
+    out = tuple(None if a is None else np.array(a, np.float32) for a in (dil, orc.elevation_map, orc.normal_map, orc.traversability_input))
+    for a in out:
+        if a is not None:
+            a.setflags(write=False)
+    return out
 
 
 @pytest.fixture(scope="module")
 def oracle(weights):
     """case key -> the oracle's arrays, computed once: (stage-1 dilation, elevation_map, normal_map, traversability_input)"""
-    done = {}
-
-    def get(key):
-        if key in done:
-            return done[key]
-        eo.set_threads(8)
-        try:
-            if key == pv.FRAME_KEY:
-                _, orc = make_pair(eo.YAML, pv.FRAME["C"], "reference_fp16", weights)
-                pv.run_frames(orc, False)
-                dil = None
-            else:
-                C, d = next(c for c in pv.CASES if pv.case_key(*c) == key)
-                _, orc = make_pair(dict(eo.YAML, dilation_size=d), C, "reference_fp16", weights)
-                orc.elevation_map[...] = pv.state(C, d, pv.case_seed(C, d))
-                orc.dilate()
-                dil = orc.traversability_input.copy()
-                orc.traversability(); orc.normals()
-        finally:
-            eo.set_threads(1)
-        done[key] = tuple(None if a is None else np.array(a, np.float32) for a in (dil, orc.elevation_map, orc.normal_map, orc.traversability_input))
-        for a in done[key]:
-            if a is not None:
-                a.setflags(write=False)
-        return done[key]
-
-    return get
+    return vc.cached_oracle(lambda key: _oracle_case(key, weights))
 
 
 def _check(got, key, want, what):
-    assert_planes_equal(got[key + "_map"], want[1], what=what)
-    assert_planes_equal(got[key + "_normal"], want[2], names=["nx", "ny", "nz"], what=what)
-    assert_planes_equal(got[key + "_trav_in"][None], want[3][None], names=["traversability_input"], what=what)
+    vc.assert_case_planes(got, key, want[1], want[2], want[3], what)
 
 
 @pytest.mark.parametrize("case", pv.CASES, ids=[pv.case_key(*c) for c in pv.CASES])

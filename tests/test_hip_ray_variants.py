@@ -18,19 +18,13 @@ unreachable on affordable maps: it needs a half -> index table that cannot be bu
 STRIP = true (row strips, by-ray windows) is the subject of the strip tests.  The expectation below is a decision table derived by hand and
 kept as literals on purpose: it is not recomputed from a copy of the launcher's arithmetic."""
 import os
-import re
-import shutil
-import signal
-import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
 
 import _ray_variants as rv
-from _util import assert_planes_equal, kernel_trace_rows
-from oracle import emap_oracle as eo
+import _variant_children as vc
+from _util import kernel_trace_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -60,7 +54,6 @@ IDX = {
     "table_lds":    (1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, 1),
     "table_global": (1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, 1),
 }
-HIP_ERROR = re.compile(r"hipError|HIP error|HSA_STATUS_ERROR|illegal memory access|Memory access fault|GPU core dump", re.I)
 
 
 def name_of(mode, stats, idx, strip, block, lmap, lpr):
@@ -83,91 +76,23 @@ def reachable_instantiations():
     return {n for v in VARIANTS for k in rv.KEYS for n in expected_names(v, k)}
 
 
-def _canonical(name):
-    """'k_rays<...>' of a traced dispatch name with its template arguments in one spelling (booleans as false / true)"""
-    m = re.search(r"\bk_rays<([^<>]*)>", name)
-    if not m:
-        return None
-    a = [x.strip() for x in m.group(1).split(",")]
-    if len(a) != 7:
-        return "k_rays<%s>" % m.group(1)
-    flag = lambda x: {"true": 1, "false": 0, "(bool)1": 1, "(bool)0": 0, "1": 1, "0": 0}[x]      # noqa: E731
-    return name_of(int(a[0]), flag(a[1]), int(a[2]), flag(a[3]), int(a[4]), flag(a[5]), int(a[6]))
-
-
-class BadExit(Exception):
-    """a child that ran into its time limit, was ended by a signal, exited with an error or reported a HIP error"""
-
-
 def _run_child(variant, tmp):
-    env = {k: v for k, v in os.environ.items() if k not in HOOKS}
-    env.update(VARIANTS[variant])
-    prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
-    assert os.path.exists(prof), "rocprofv3 not found: the kernel selection cannot be verified"
-    out, trace = os.path.join(tmp, "out.npz"), os.path.join(tmp, "trace")
-    child = os.path.join(os.path.dirname(os.path.abspath(rv.__file__)), "_ray_variants.py")
-    cmd = [prof, "--kernel-trace", "-d", trace, "--", sys.executable, child, out]
-    t0 = time.time()
-    p = subprocess.Popen(cmd, env=env, stdin=subprocess.DEVNULL, stdout=subprocess.PIPE, stderr=subprocess.PIPE, start_new_session=True)
-    try:
-        _, err = p.communicate(timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        os.killpg(p.pid, signal.SIGKILL)
-        _, err = p.communicate()
-        raise BadExit("variant %s: the child ran into its time limit of %d s; stderr ends:\n%s" % (variant, CHILD_TIMEOUT_S, err.decode(errors="replace")[-3000:]))
-    print("variant %s: child took %.1f s" % (variant, time.time() - t0))
-    err = err.decode(errors="replace")
-    if p.returncode != 0:
-        raise BadExit("variant %s: the child exited with %d; stderr ends:\n%s" % (variant, p.returncode, err[-3000:]))
-    if HIP_ERROR.search(err):
-        raise BadExit("variant %s: the child's stderr names a HIP error:\n%s" % (variant, err[-3000:]))
-    with np.load(out) as z:
-        arrays = {k: z[k] for k in z.files}
-    rows = [(c, l) for c, l in ((_canonical(n), l) for n, l in kernel_trace_rows(trace)) if c]
+    arrays, trace = vc.run_child(os.path.abspath(rv.__file__), variant, VARIANTS[variant], HOOKS, tmp, CHILD_TIMEOUT_S)
+    rows = [(c, l) for c, l in ((vc.canonical_kernel_name(n, {"k_rays": "ibibibi"}), l) for n, l in kernel_trace_rows(trace)) if c]
     return arrays, rows
 
 
 @pytest.fixture(scope="module")
 def children(tmp_path_factory):
     """variant -> (recorded arrays, [(k_rays dispatch name, lds_size)] in start order): one child per variant, started the first time a
-    test needs it, never twice.  After a bad exit (BadExit) NO further child is started: a process that faulted or hung may have left the
-    device in a state in which the next one does the same, so every test that still needs a child fails with that first message.  A child
-    that merely computed wrong values stops nothing."""
-    done, halted = {}, []
-
-    def get(variant):
-        if variant not in done:
-            if halted:
-                pytest.fail("not started: an earlier child ended badly -- %s" % halted[0], pytrace=False)
-            try:
-                done[variant] = _run_child(variant, str(tmp_path_factory.mktemp("rays_" + variant)))
-            except BadExit as e:
-                halted.append(str(e))
-                done[variant] = e
-            except Exception as e:          # remembered, not retried
-                done[variant] = e
-        if isinstance(done[variant], Exception):
-            pytest.fail("%s" % done[variant], pytrace=False)
-        return done[variant]
-
-    return get
+    test needs it, never twice; after a child that ended badly none is started (tests/_variant_children.py)"""
+    return vc.lazy_children(lambda v: _run_child(v, str(tmp_path_factory.mktemp("rays_" + v))))
 
 
 @pytest.fixture(scope="module")
 def oracle(weights):
     """case key -> (elevation_map, normal_map, traversability_input, visits per frame) of the oracle, computed once"""
-    done = {}
-
-    def get(key):
-        if key not in done:
-            eo.set_threads(8)
-            try:
-                done[key] = rv.oracle_run(rv.case_of(key), weights)
-            finally:
-                eo.set_threads(1)
-        return done[key]
-
-    return get
+    return vc.cached_oracle(lambda key: rv.oracle_run(rv.case_of(key), weights))
 
 
 @pytest.mark.parametrize("key", rv.KEYS)
@@ -176,9 +101,7 @@ def test_values_equal_the_oracle(variant, key, children, oracle):
     got, _ = children(variant)
     want = oracle(key)
     what = "%s %s" % (variant, key)
-    assert_planes_equal(got[key + "_map"], want[0], what=what)
-    assert_planes_equal(got[key + "_normal"], want[1], names=["nx", "ny", "nz"], what=what)
-    assert_planes_equal(got[key + "_trav_in"][None], want[2][None], names=["traversability_input"], what=what)
+    vc.assert_case_planes(got, key, want[0], want[1], want[2], what)
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS))
