@@ -1,4 +1,4 @@
-"""Builds libemap_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: seven translation units, compiled in parallel into
+"""Builds libemap_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: the translation units of SOURCES, compiled in parallel into
 csrc/_obj/*.o (only the stale ones) and linked."""
 from __future__ import annotations
 
@@ -10,8 +10,9 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(os.path.dirname(HERE), "libemap_hip.so")
 OBJ = os.path.join(HERE, "_obj")
-SOURCES = ["emap_kernels.hip", "emap_binned.hip", "emap_semantic.hip", "emap_api.hip", "emap_inpaint_host.hip", "emap_inpaint_ns.cpp", "emap_inpaint_fronts.hip"]      # (.cpp: host-only C++)
-HEADERS = ["emap_device.h", os.path.join("..", "..", "include", "emap_hip.h")]
+SOURCES = ["emap_kernels.hip", "emap_binned.hip", "emap_semantic.hip", "emap_api.hip", "emap_api_semantic.hip", "emap_api_plugins.hip", "emap_api_comm.hip",
+           "emap_inpaint_host.hip", "emap_inpaint_ns.cpp", "emap_inpaint_fronts.hip"]      # (.cpp: host-only C++)
+HEADERS = ["emap_device.h", "emap_launch.h", "emap_host.h", os.path.join("..", "..", "include", "emap_hip.h")]
 DEPS = SOURCES + HEADERS
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
@@ -49,7 +50,7 @@ def build(force=False, verbose=False):
 
     with ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
         list(ex.map(compile_one, zip(SOURCES, objs)))
-    cmd = [hipcc, "--offload-arch=gfx950", "-fno-gpu-rdc", "-shared", "-fPIC"] + objs + ["-o", LIB]
+    cmd = [hipcc, "--offload-arch=gfx950", "-fno-gpu-rdc", "-shared", "-fPIC", "-Wl,--no-undefined"] + objs + ["-o", LIB]      # (a launcher declared and defined nowhere fails the build, not the first call)
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

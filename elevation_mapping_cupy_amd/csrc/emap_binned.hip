@@ -32,16 +32,15 @@
 // records (N / G of them) and is a pure permutation.  So the full geometry, the atomics and the record traffic shrink with G; only
 // ONE 12-byte stream over the cloud per frame does not.  With a visibility pass every VALID point marches a ray through the strip
 // (custom_kernels.py:199-258), validity needs the full geometry, and the non-strip kernels run (same records, ray-only bin).
-#include "emap_device.h"
+#include "emap_launch.h"
 #include <cstring>
 #include <cstdlib>
 
 #define BIN_TR 16
 #define BIN_TC 64
-#define BIN_MAX_T 16384   /* LDS histogram / cursor arrays are dynamic: 4 B per tile */
 #define BIN_QCAP 128      /* entries of a wave's compaction queue (strip variants): < 64 pending + <= 64 pushed per step */
 
-// (BinGeo, BinRec: emap_device.h)
+// (BinGeo, BinRec: emap_device.h; BIN_MAX_T: emap_launch.h)
 
 // sort bin of a point (-1: none) and its cell inside the bin.  Tiles are PHYSICAL: 16 owned rows x 64 columns of memory.
 __device__ __forceinline__ int bin_of(const KP& P, const BinGeo& G, const Geo& g, unsigned int& lc) {

@@ -94,10 +94,10 @@ struct Moves { int n, pad_; int org_r[EM_MAX_MOVES], org_c[EM_MAX_MOVES], sr[EM_
 struct KP {
   int C, mode, row0, nrows, halo, edge, dil, idx_formula;   // idx_formula: reference_fp16 cell index by the float formula (host-proven exact, build_ray_tables)
   // k_rays only: the arrays it addresses hold `ncols` columns starting at column col0 with a row pitch of `pitch` cells -- (0, C, C) for
-  // every map / strip context; the RAY WINDOW of a multi-GPU frame (rays marched by ray owner, emap_api.hip: rays_by_ray) is a small
+  // every map / strip context; the RAY WINDOW of a multi-GPU frame (rays marched by ray owner, emap_api_comm.hip: rays_by_ray) is a small
   // rectangle of the map in logical coordinates with its own pitch (wmode = 1: normals are addressed like the cells)
   int col0, ncols, pitch, wmode;
-  // row strips after a ROW shift: the normal planes handed to k_rays / k_win_pack are a row-aligned copy (emap_api.hip:
+  // row strips after a ROW shift: the normal planes handed to k_rays / k_win_pack are a row-aligned copy (emap_api_comm.hip:
   // normal_exchange) -- row j holds the normals that belong to the cells of owned row j, columns still at the planes' own origin
   int nlag;
   int ray_pref;      // host side only (launch_rays): 1 = the map is mostly unknown / stale (FrameDev::ray_class): keep the ray kernel's bitmap in global memory

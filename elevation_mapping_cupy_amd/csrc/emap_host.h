@@ -1,0 +1,210 @@
+// What the host files of the C ABI share (emap_api.hip: the core; emap_api_semantic.hip: semantic layers and the camera path;
+// emap_api_plugins.hip: the publish-time plugins on caller planes; emap_api_comm.hip: halos, the RCCL communicator, rays by ray):
+// the context, the frame record, the error macros, the one call-scoped device buffer and the few helpers that cross a file boundary.
+// Whatever has a symbol here lives in namespace emap_host, so that nothing can collide with a symbol of the program that loads the
+// library.  RCCL stays inside emap_api_comm.hip: the context holds the communicator and the bound entry points as opaque pointers.
+#pragma once
+#include "emap_launch.h"
+#include "../../include/emap_hip.h"
+#include <condition_variable>
+#include <functional>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+// timed stages of emap_update (emap_get_stage_times): hist+scan are 0 on the atomic path, where "scatter" is k_count
+enum { ST_HIST = 0, ST_SCAN, ST_SCATTER, ST_GATE, ST_FUSE, ST_COMMIT, ST_RAYS, ST_AVERAGE, ST_OVERLAP, ST_POST, ST_N };
+
+struct RcclApi;      // the RCCL entry points of the path, bound with dlsym (emap_api_comm.hip)
+struct ncclComm;     // (rccl.h: ncclComm_t is a pointer to it)
+
+namespace emap_host {
+// ---- asynchronous cloud upload (a1: ElevationMap.input_pointcloud, EM/elevation_mapping.py:456-458) ------------------------------
+// The ROS wrapper hands over a pageable float64 matrix.  It is converted to float32 on the HOST by a few worker threads straight
+// into a pinned slot (so only 12 of the 24 bytes per point cross PCIe and no device-side cast pass is needed), chunk by chunk, each
+// chunk's DMA on a copy stream overlapping the next chunk's conversion; the device buffer is double buffered so the upload of frame
+// k+1 overlaps the kernels of frame k.  The call returns when the caller's buffer has been consumed (it is only borrowed).
+struct Workers {
+  std::vector<std::thread> th; std::mutex m; std::condition_variable cv, done_cv;
+  std::function<void(int, int)> job; int gen = 0, pending = 0; bool stop = false;
+  explicit Workers(int n) {
+    for (int i = 0; i < n; ++i) th.emplace_back([this, i, n] {
+      int seen = 0;
+      for (;;) {
+        std::unique_lock<std::mutex> l(m);
+        cv.wait(l, [&] { return stop || gen != seen; });
+        if (stop) return;
+        seen = gen; auto f = job; l.unlock();
+        f(i, n);
+        l.lock(); if (--pending == 0) done_cv.notify_all();
+      }
+    });
+  }
+  void run(const std::function<void(int, int)>& f) {       // f(worker, n_workers) on every worker; returns when all are done
+    std::unique_lock<std::mutex> l(m);
+    job = f; pending = (int)th.size(); ++gen; cv.notify_all();
+    done_cv.wait(l, [&] { return pending == 0; });
+  }
+  ~Workers() { { std::lock_guard<std::mutex> l(m); stop = true; } cv.notify_all(); for (auto& t : th) t.join(); }
+};
+
+// A device buffer for the duration of a call, freed when it goes out of scope on every way out: plain scratch (alloc), or the device
+// copy of a host array (put) that get() copies back.
+struct DevBuf {
+  void* d = nullptr; size_t bytes = 0; void* back = nullptr;
+  hipError_t alloc(size_t n) { bytes = n; return hipMalloc(&d, n); }
+  hipError_t put(const void* host, size_t n, hipStream_t s, void* write_back) {
+    bytes = n; back = write_back;
+    if (!n) return hipSuccess;
+    hipError_t e = hipMalloc(&d, n);
+    if (e != hipSuccess) return e;
+    return hipMemcpyAsync(d, host, n, hipMemcpyHostToDevice, s);
+  }
+  hipError_t get(hipStream_t s) { return (back && bytes) ? hipMemcpyAsync(back, d, bytes, hipMemcpyDeviceToHost, s) : hipSuccess; }
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (d) hipFree(d); }
+};
+}  // namespace emap_host
+
+struct emap_ctx {
+  emap_params prm;
+  emap_strip strip;
+  KP kp;
+  int device;
+  hipStream_t stream;
+  bool own_stream;
+  long ncells_alloc;        // (rows + 2*halo) * C
+  Cells cells;                     // two planes of 16-byte half cells (emap_device.h)
+  int torg_r, torg_c;              // origin traversability_input was written with (kp.norg_*: the normal planes)
+  AccF* acc; AccR* accr;
+  float* trav_in; float* normal;   // normal: 3 planes of ncells_alloc
+  float* scratch;                  // one plane (get/set staging)
+  float* plug_buf; size_t plug_cap; unsigned int* plug_cnt; int plug_cnt_cap;   // plane scratch of the publish-time plugins (kept between calls)
+  ErrSlot* slots; FrameDev* frame;
+  RayTab rt; float* ray_S; unsigned short* ray_lut;
+  unsigned long long* inert;       // 1 bit per owned cell (rows of ceil(C/64) words), written by k_commit / k_tile_fuse<true, true>
+  unsigned int* inl_plane;         // newmap[3] of frames whose tile kernel commits itself (binned path + visibility pass), on demand
+  float* ray_thr;                  // same frames: per 8 x 8 block height at or above which a ray sample cannot affect any cell of the block
+  bool inert_zero;                 // the bitmap is all zero (k_ray_apply leaves it so; k_commit overwrites it)
+  // tile-binned scatter buffers (allocated on demand)
+  int scatter_mode;                // 0 auto, 1 atomic, 2 binned
+  int force_sub;                   // test hook: minimum bin height factor (emap_set_scatter_mode bits 8..15)
+  bool frame_binned;               // the count stage of the current frame used the binned path
+  unsigned int* bin_sync;          // ticket counters of k_bin_scan (last_block_ticket), zero between launches
+  SplitView split;                 // heavy tiles reduced by several workgroups (emap_device.h); split.on: this frame's scan listed them
+  void* split_mem;                 // one allocation behind split's arrays
+  void* sem_split_mem;             // scratch of the split semantic tile kernel (SemSplit), zero between launches
+  volatile unsigned int* split_need;   // host-mapped word: the parts the last scan the device has finished would have listed
+  bool split_dirty;                // k_tile_count has filled slots that no k_tile_fuse has cleared yet
+  unsigned int* cnt_sync;          // ticket words of k_count's folded gate (Frame::fold_gate)
+  // robot scale: count -> gate -> fuse -> commit + average in one launch (k_small_frame): its barriers' release words live behind the
+  // ticket words of cnt_sync.  A launch whose grid barrier is ABORTED leaves map, accumulators and drift record exactly as it found
+  // them, and the launches queued behind it do nothing (device-side poison word).  sf_host = two host-mapped words: [0] epoch of the
+  // last launch that will be applied, [1] epoch of the first aborted launch.  The frames issued and not yet known to be applied wait
+  // in sf_ring with everything needed to run them again; sf_settle (every entry point but the ones that only bind a cloud) learns
+  // their fate and, after an abort, re-runs them in order on the chain of launches.
+  unsigned int sf_epoch; volatile unsigned int* sf_host; unsigned int* sf_host_dev; unsigned int* sf_poison;
+  FrameDev* frame_save;            // the frame record as the gate of the last k_small_frame found it
+  struct SfFrame { unsigned int epoch; float R[9], t[3]; double pn, on; Moves mv; const float* pts; long n_pts, n_pts_all; int stride; ChanView chan; int n_cols; };
+  enum { SF_RING = 8 };
+  SfFrame sf_ring[SF_RING]; int sf_head, sf_count;
+  bool sf_redo;                    // inside sf_recover: frames take the chain of launches
+  unsigned int sf_aborts;          // frames re-run so far (emap_small_frame_aborts)
+  int update_path;                 // emap_last_update_path
+  BinGeo bg; BinRec* bin_recs; BinStg* bin_own; unsigned int* bin_own_cnt; long bin_own_cap; bool bin_strip;   // bin_own*: staged records of the owned points per block (strip contexts without a visibility pass)
+  unsigned int* bin_hist; unsigned int* bin_tile_total; unsigned int* bin_tile_start; long bin_cap; size_t bin_hist_cap;      // bin_cap: 16-byte units
+  // The semantic fusion declared for the NEXT whole frame (emap_frame_semantics): run inside the frame.  A frame that can CARRIES the
+  // channels in 32-byte sorted records (bin_rs = 2, carry: which columns) and fuses them in the tile kernel itself;
+  // every other frame runs the stand-alone semantic kernels before it returns -- the result is the same either way.
+  bool fsem_set; int fsem_keep_counts; SemSpec fsem;
+  int bin_rs; SemCarry carry;      // stride of the current frame's sorted records in 16-byte units; the carried columns (on = 0: none)
+  // semantic layers (planar float planes + double / uint32 accumulators), allocated on demand
+  float* img_uv; unsigned char* img_valid; float* img_buf; size_t img_cap;   // camera path
+  double img_tol; bool img_tol_set;   // tolerance_z_collision of the occlusion walk (0.10 unless emap_image_set_tolerance was called)
+  float* sem_alpha;   // class_bayesian pseudo-counts (the reference's persistent new_map layers), sem_layers planes, on demand
+  int sem_layers; float* sem; double* sem_sums; unsigned int* sem_col; unsigned int* cnt_plane;
+  // point cloud
+  float* pts_dev[2]; long pts_cap[2];      // owned device buffers (floats), ping-pong between consecutive uploads
+  float* pts_pin[2]; long pin_cap[2];      // pinned host slots the clouds are converted / copied into
+  hipEvent_t ev_copied[2], ev_used[2];     // DMA of slot done (copy stream) / the frame that read the slot's device buffer done (main stream)
+  int up_slot; bool up_used[2]; hipStream_t copy_stream; emap_host::Workers* workers;
+  const float* pts; long n_pts; int stride;         // xyz of the bound cloud: rows of `stride` floats (3 for a de-interleaved cloud)
+  long n_pts_all;                                   // size of the cloud the caller handed over (> n_pts for a bucketed one): what every rank of a sharded map shares
+  bool pts_bucketed; float bucket_R[9], bucket_t[3]; int bucket_org_r;   // the bound cloud only holds the points that can land in this strip's rows under this pose (emap_upload_points_strip)
+  ChanView chan; int n_cols;                        // its extra channels (emap_device.h: ChanView); n_cols = columns of the caller's matrix (3 + K)
+  int* tail_idx; unsigned char* tail_flags; long tail_cap;
+  // frame state
+  bool use_override; double sum_override; unsigned int cnt_override;
+  bool committed;
+  bool stage_timing; hipEvent_t ev[ST_N + 1]; float stage_ms[ST_N];
+  hipEvent_t t0, t1;
+  bool want_ray_stats;
+  // row-strip communicator (emap_comm_init): RCCL resolved at run time, exchange on its own stream so that it overlaps the interior stencils
+  struct RcclApi* rccl; struct ncclComm* comm; int comm_rank, comm_world;      // (both opaque here: emap_api_comm.hip)
+  float* gather_buf;            // cell_n x cell_n plane of emap_comm_gather_layer (on demand)
+  // rays by ray (multi-GPU frames with a visibility pass): the replicated ray window around the sensor (emap_device.h: Win)
+  int ray_mode;                 // 0 auto (by ray from 2048^2 cells on), 1 always by row, 2 by ray whenever the frame allows it
+  bool byray_allreduce;         // the communicator's by-ray exchange: three all-reduces instead of the owners' sends / receives (emap_comm_init)
+  size_t wire_bytes;            // payload of the last by-ray frame's three all-reduces (bytes per rank)
+  int ray_par;                  // parity of the k_ray_apply launches (FrameDev::quiet_sum)
+  unsigned int* win_state; unsigned int* win_rec; unsigned long long* win_bits; float* win_thr; long long* win_dh; unsigned int* win_key; long win_cap;
+  long long* win_red_dh; unsigned int* win_red_key;      // by-ray effects reduced to the owners: (world - 1) parts of win_cap cells each
+  hipStream_t comm_stream; hipEvent_t ev_ready, ev_done; double* comm_sums;   // [0..1] local err_sum / err_cnt, [2..3] totals, [4..36) emap_comm_allreduce_host
+  // the un-shifted normal planes after a row shift (normal_exchange): a row-aligned copy of the rows this strip's cells belong to
+  std::vector<int> cut_begin, cut_count;   // every rank's owned PHYSICAL rows (gathered by emap_comm_init)
+  float* nlag_buf; long nlag_cap;          // 3 planes of row_count x cell_n
+  bool cuts_ok;                            // the gathered strips tile the map
+  std::string err;
+};
+
+#define CK(call)                                                                                         \
+  do { hipError_t e_ = (call);                                                                           \
+       if (e_ != hipSuccess) { ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); return EMAP_ERR_HIP; } } while (0)
+#define CKARG(cond, msg) do { if (!(cond)) { if (ctx) ctx->err = msg; return EMAP_ERR_INVALID; } } while (0)
+
+// What one frame (frame_impl: emap_update, emap_update_sharded) decided, handed to the stage helpers it calls.  It lives on the
+// frame's stack: an error on the way leaves nothing behind for the next call.  The staged entry points pass nullptr: the per-tile
+// error statistics are gathered, plain 16-byte records sorted, the gate runs on its own, the rays march by row over the committed
+// snapshot, nothing is folded.
+struct Frame {
+  bool gate_possible;      // the drift gate can fire (elevation_mapping.py:346-349); if not, the per-tile error statistics are skipped
+                           // (they could not have any effect; err_sum / err_cnt report 0)
+  bool fold_gate;          // whole map on the atomic path: the gate rides in k_count's last workgroup (cnt_sync: its ticket words)
+  bool carry;              // the sort may carry the declared semantic channels in 32-byte records (frame_sem_begin)
+  bool by_ray;             // sharded frame whose visibility pass marches by ray (rays_by_ray_pass)
+  bool rays_fused;         // the tile kernel committed + averaged, k_ray_apply follows the rays
+  bool nlag;               // normal_exchange filled the row-aligned copy of the normal planes for the visibility pass
+  GateArgs gate;           // the drift gate's inputs (k_count's fold, k_small_frame, gate_fold)
+  GateFold gate_fold;      // sharded frame on the binned path: the decision on the all-reduced totals in the tile kernel's head (mode 0: k_gate ran)
+  OverlapArgs ov;          // clear_overlap_map, folded into the kernel that rewrites the cells last (tile kernel, k_average or k_ray_apply)
+};
+
+// ---- the helpers that cross a file boundary ------------------------------------------------------------------------------------------
+namespace emap_host {
+// emap_api.hip
+float q16(float x);
+int sf_settle(emap_ctx* ctx);
+Pose make_pose(const emap_ctx* ctx, const float R[9], const float t[3]);
+int flush_moves(emap_ctx* ctx);
+int normal_row_lag(const emap_ctx* ctx);
+int plugin_scratch(emap_ctx* ctx, size_t planes, int counters);
+bool takes_bins(const emap_ctx* ctx, long n);
+// emap_api_semantic.hip: the frame's semantic fusion
+int frame_sem_begin(emap_ctx* ctx, bool rays_on, Frame* fr);
+int frame_sem_finish(emap_ctx* ctx, const float R[9], const float t[3], bool merged);
+// emap_api_comm.hip: the exchange steps of a sharded frame
+int drift_allreduce(emap_ctx* ctx);
+int halo_exchange_start(emap_ctx* ctx);
+int normal_exchange(emap_ctx* ctx);
+bool rays_by_ray(const emap_ctx* ctx);
+int rays_by_ray_pass(emap_ctx* ctx, const float R[9], const float t[3], const Frame* f);
+}  // namespace emap_host
+
+// Every entry point that reads or changes the map, the drift record or a cloud buffer settles the small frames in flight first
+// (emap_api.hip: sf_settle); map shifts are lazy (emap_shift) and written out before anything but a frame kernel looks at the cells.
+#define SF_CHECK() do { if (ctx->sf_count > 0) { int rc_sf_ = emap_host::sf_settle(ctx); if (rc_sf_) return rc_sf_; } } while (0)
+#define FLUSH() do { int rc_ = emap_host::flush_moves(ctx); if (rc_) return rc_; } while (0)
+#define NEED_POINTS() do { if (!ctx->pts && ctx->n_pts) { ctx->err = "no point cloud bound"; return EMAP_ERR_NO_POINTS; } } while (0)

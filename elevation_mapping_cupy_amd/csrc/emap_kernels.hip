@@ -3,7 +3,7 @@
 // execution model: the deterministic two-phase contract of DESIGN.md (fuse and ray passes only READ the map and
 // write integer/fixed-point accumulators, per-cell passes commit) -- not a translation of the CuPy kernels.
 // Compiled with -ffp-contract=off: decisions (indices, gates) must be bit-identical to the oracle.
-#include "emap_device.h"
+#include "emap_launch.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -910,7 +910,7 @@ __global__ __launch_bounds__(EM_BLOCK) void k_ray_apply(KP P, Cells cells, AccR*
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Rays by ray on row strips (multi-GPU frames, emap_api.hip: rays_by_ray).  Every ray starts at the sensor, so the strips around it
+// Rays by ray on row strips (multi-GPU frames, emap_api_comm.hip: rays_by_ray).  Every ray starts at the sensor, so the strips around it
 // march what the whole map marches -- row strips do not scale the visibility pass (measured: 1.02x at 1024^2, 1.34x at 4096^2 on 8
 // ranks).  Instead every rank marches the rays of ITS points (those whose end cell lies in its rows: 1 / G of a uniform cloud, already
 // tile sorted) over a replicated copy of the RAY WINDOW -- the (2 max_ray_length / resolution)^2 cells around the sensor that any ray
@@ -1614,7 +1614,7 @@ __global__ __launch_bounds__(EM_BLOCK) void k_point_index(KP P, Pose T, const fl
 
 // halo rows: contiguous 32-B cells, so pack/unpack are plain device copies done by the host API.
 
-// ---- launch wrappers used by emap_api.hip -------------------------------------------------------------
+// ---- launch wrappers (emap_launch.h) -------------------------------------------------------------------
 static inline unsigned int nblk(long n) { return (unsigned int)((n + EM_BLOCK - 1) / EM_BLOCK); }
 
 // gate != nullptr: the drift gate rides in the last workgroup (whole frames: emap_update); false is returned when nothing was launched

@@ -1,0 +1,76 @@
+// The launchers of the kernel files, the kernel argument structs that travel by value between a host file and a kernel file, and
+// the limits both sides size their buffers by -- declared ONCE.  Every file that defines a launcher includes this header, so a
+// prototype that drifts from its definition fails to compile or link instead of failing at the first call.
+#pragma once
+#include "emap_device.h"
+#include <cstddef>
+
+// ---- kernel arguments built on the host (host files) and read by value in kernels (emap_semantic.hip) ----------------------------
+struct SemRaw { int op, stride, K, n_max; long size, cells; double alpha; };      // the semantic kernel factories on caller arrays (k_semraw_acc / k_semraw_fin)
+struct CamArgs { float P[12], K[9], D[5], center[3]; float x1, y1, z1, ih, iw; double tol; };      // tol = tolerance_z_collision (custom_image_kernels.py:9; 0.10 in the reference's call)
+struct CmaxSpec { int n; int chan[8]; int layer[8]; };      // pointcloud_class_max: the fusion's channels and layers
+
+// ---- limits shared by the host layer and emap_binned.hip -----------------------------------------------------------------------------
+#define BIN_MAX_T 16384   /* LDS histogram / cursor arrays are dynamic: 4 B per tile */
+#define BIN_MAX_B 2048
+#define SEM_SPLIT_SLOTS 128      /* heavy tiles whose semantic sums several workgroups may share (19 MB of scratch) */
+#ifndef EMAP_SPLIT_POOL_DEFAULT
+#define EMAP_SPLIT_POOL_DEFAULT 0       /* standing pool of extra tile workgroups (emap_count): off -- measured, see there */
+#endif
+
+// launchers (emap_kernels.hip)
+bool launch_count(hipStream_t, const KP&, const Pose&, const float*, long, int, Cells, AccF*, ErrSlot*, const GateArgs*, FrameDev*, unsigned int*);
+void launch_gate(hipStream_t, const GateArgs&, ErrSlot*, FrameDev*, int, double*, const double*);
+int small_frame_grid(const KP&, long);
+void launch_small_frame(hipStream_t, int, const KP&, const Pose&, const float*, long, int, Cells, AccF*, unsigned int*, const OverlapArgs&,
+                        const GateArgs&, FrameDev*, FrameDev*, ErrSlot*, unsigned int*, unsigned int*, unsigned int*, unsigned int*, unsigned int, unsigned int, int);
+void launch_fuse(hipStream_t, const KP&, const Pose&, const float*, long, int, Cells, AccF*, const FrameDev*);
+void launch_commit(hipStream_t, const KP&, Cells, const AccF*, const FrameDev*, unsigned long long*);
+void launch_rays(hipStream_t, const KP&, const Pose&, const RayTab&, const float*, long, int, Cells, const AccRView&, const float*, long, FrameDev*, bool, const unsigned long long*, const unsigned int*, int, const float*, const unsigned int*, const unsigned int*);
+void launch_win_pack(hipStream_t, const KP&, const Win&, Cells, const float*, long, const unsigned int*, const unsigned long long*, float);
+void launch_win_prepare(hipStream_t, const Win&, int);
+void launch_win_unpack(hipStream_t, const KP&, const Win&, AccR*);
+void launch_win_reduce(hipStream_t, long long*, unsigned int*, const long long*, const unsigned int*, int, long, long, long);
+void launch_ray_apply(hipStream_t, const KP&, Cells, AccR*, unsigned long long*, const OverlapArgs&, FrameDev*, unsigned int*, int);
+void launch_average(hipStream_t, const KP&, Cells, AccF*, AccR*, const FrameDev*, bool, bool, unsigned int*, const OverlapArgs&);
+void launch_overlap(hipStream_t, const KP&, Cells, int, int, float, float);
+void launch_var_time(hipStream_t, const KP&, Cells, int, int);
+int post_tile_rows(const KP&);
+void launch_post(hipStream_t, const KP&, const float*, const float*, const float*, const float*, Cells, float*, float*, long, int, int, const int*, const int*, int, int);
+void launch_get_plane(hipStream_t, const KP&, Cells, int, float*);
+void launch_publish(hipStream_t, const KP&, Cells, const float*, long, int, float, int, float*);
+void launch_set_plane(hipStream_t, const KP&, Cells, int, const float*);
+void launch_fill_cells(hipStream_t, Cells, long, const Cell&);
+void launch_point_index(hipStream_t, const KP&, const Pose&, const float*, long, int, int*, unsigned char*);
+void launch_plane_view(hipStream_t, const KP&, int, int, float*, float*, int);
+void launch_materialize(hipStream_t, const KP&, Cells);
+void launch_band_clear(hipStream_t, const KP&, float*, int, long, int, int);
+
+// semantic layers, camera path and publish-time plugins (emap_semantic.hip)
+void launch_sem_points(hipStream_t, const KP&, const Pose&, const SemSpec&, const float*, long, int, const ChanView&, double*, unsigned int*, long);
+void launch_sem_finalize(hipStream_t, const KP&, const SemSpec&, const unsigned int*, double*, unsigned int*, float*, float*, long);
+void launch_semraw_acc(hipStream_t, const SemRaw&, const float*, const int*, const int*, const float*, const int*, float*, unsigned int*);
+void launch_semraw_fin(hipStream_t, const SemRaw&, float*, const unsigned int*, const int*, const float*, const float*, float*);
+void launch_polygon_mask(hipStream_t, int, const int*, const int*, int, const int*, float*);
+void launch_dilate_planes(hipStream_t, int, int, const float*, const float*, float*, float*);
+void launch_cmax_ids(hipStream_t, const KP&, const CmaxSpec&, const ChanView&, long, const float*, long, unsigned char*, unsigned char*);
+void launch_cmax_sum(hipStream_t, const KP&, const Pose&, const CmaxSpec&, const float*, long, int, const ChanView&, const int*, long long*, long);
+void launch_cmax_select(hipStream_t, const KP&, const CmaxSpec&, int, const long long*, long, unsigned char*, unsigned char*, const unsigned int*, float*, float*, float*);
+void launch_image_corr(hipStream_t, const KP&, const CamArgs&, Cells, float*, unsigned char*);
+void launch_image_fuse(hipStream_t, const KP&, int, float*, const float*, const float*, const unsigned char*, float, float, double);
+void launch_inpaint_sweep(hipStream_t, int, const float*, const float*, float*, float*, const unsigned int*, unsigned int*);
+void launch_min_sweep(hipStream_t, int, int, const float*, const float*, const float*, float*, float*, const unsigned int*, unsigned int*, bool);
+void launch_box3(hipStream_t, int, const float*, float*);
+void launch_erode(hipStream_t, int, int, const float*, float*);
+
+// tile-binned scatter (emap_binned.hip)
+void launch_bin_hist(hipStream_t, const KP&, const Pose&, const BinGeo&, const float*, long, int, unsigned int*, BinStg*, unsigned int*);
+void launch_bin_scan(hipStream_t, const BinGeo&, unsigned int*, unsigned int*, unsigned int*, unsigned int*, const SplitView&);
+void launch_bin_scatter(hipStream_t, const KP&, const Pose&, const BinGeo&, const float*, long, int, const unsigned int*, const unsigned int*, BinRec*, const BinStg*, const unsigned int*, const ChanView&, const SemCarry&);
+void launch_tile_count(hipStream_t, const KP&, const BinGeo&, const BinRec*, int, const unsigned int*, Cells, ErrSlot*, const SplitView&, long);
+void launch_tile_semantic(hipStream_t, const KP&, const BinGeo&, const SemSpec&, const BinRec*, int, int, const unsigned int*, const ChanView&, long,
+                          const unsigned int*, float*, float*, long, const SplitView&, void*, int);
+size_t sem_split_bytes(int);
+bool sem_split_possible(const SemSpec&);
+void launch_bin_fuse(hipStream_t, const KP&, const BinGeo&, const BinRec*, int, const unsigned int*, Cells, AccF*, FrameDev*, bool, bool, unsigned int*, unsigned long long*, unsigned int*, float*, const OverlapArgs&, const GateFold&, const SplitView&, long, const SemMini*);
+bool bin_fuse_takes_semantics(const SplitView&, bool, bool, int);

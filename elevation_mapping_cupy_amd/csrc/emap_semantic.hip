@@ -5,7 +5,7 @@
 // The reference re-reads a float-encoded cell index from the clobbered xyz columns (custom_kernels.py:260-262, exact
 // only below 2^24); here the geometry is recomputed from xyz (a handful of VALU ops) and indices stay int32.
 // One point pass for ALL float channels (one xyz read, K atomics), one cell pass that finalises and re-arms.
-#include "emap_device.h"
+#include "emap_launch.h"
 
 
 template <int MODE>
@@ -257,9 +257,8 @@ void launch_inpaint_sweep(hipStream_t s, int C, const float* val, const float* m
 // (4) normalises the layers of a cell by their sum (:123-126).  The sums here are exact: a half is an integer multiple of 2^-24, so
 // 64-bit integers in units of 2^-24 hold every partial sum and the result does not depend on the order of the atomics (the
 // reference's float atomics round after every addition).  Host side (the set union, the whole-plane zeroing between layers):
-// emap_api.hip emap_semantic_class_max.
+// emap_api_semantic.hip emap_semantic_class_max.
 // ---------------------------------------------------------------------------------------------------------
-struct CmaxSpec { int n; int chan[8]; int layer[8]; };
 __global__ __launch_bounds__(EM_BLOCK) void k_cmax_ids(ChanView V, long n, CmaxSpec S,
                                                         unsigned char* __restrict__ seen) {
   const long i = (long)blockIdx.x * EM_BLOCK + threadIdx.x;
@@ -351,7 +350,6 @@ void launch_cmax_select(hipStream_t s, const KP& P, const CmaxSpec& S, int U, co
 // towards the camera cell rejects it when terrain in between rises above the line of sight.  Per cell, race free.
 // exponential_/color_correspondences_to_map_kernel (:195-271) then sample the image per cell.
 // ---------------------------------------------------------------------------------------------------------
-struct CamArgs { float P[12], K[9], D[5], center[3]; float x1, y1, z1, ih, iw; double tol; };      // tol = tolerance_z_collision (:9; 0.10 in the reference's call)
 
 __device__ __forceinline__ float l2_dist(int x0, int y0, int x1, int y1) { float dx = (float)(x0 - x1), dy = (float)(y0 - y1); return sqrtf(dx * dx + dy * dy); }
 
@@ -440,7 +438,7 @@ void launch_image_fuse(hipStream_t s, const KP& P, int kind, float* sem, const f
 // ---------------------------------------------------------------------------------------------------------
 // Safety-polygon service: polygon_mask_kernel (reference EM/kernels/custom_kernels.py:509-651).  The vertex and bounding-box
 // cell indices depend only on the polygon, so the host computes them once with the reference's arithmetic (float16 helper
-// parameters, fp32 division; emap_api.hip: emap_polygon_mask); the per-cell test below is the reference's integer
+// parameters, fp32 division; emap_api_plugins.hip: emap_polygon_mask); the per-cell test below is the reference's integer
 // ray-crossing test, literally.
 // ---------------------------------------------------------------------------------------------------------
 struct PtI { int x, y; };
@@ -543,7 +541,6 @@ void launch_erode(hipStream_t s, int C, int k, const float* in, float* out) {
 // (The per-frame path fuses accumulate + finalise per tile in LDS: k_tile_semantic.)  Float accumulation uses float atomics like the
 // reference (order dependent in the last bit there too).
 // ---------------------------------------------------------------------------------------------------------
-struct SemRaw { int op, stride, K, n_max; long size, cells; double alpha; };
 enum { SR_SUM = 0, SR_SUM_COMPACT, SR_SUM_MAX, SR_ALPHA, SR_ADD_COLOR };                   // accumulate ops (:9-51, :54-86, :89-123, :126-164, :270-318)
 enum { SF_AVERAGE = 0, SF_CLASS_AVERAGE, SF_BAYESIAN, SF_COLOR_AVERAGE };                  // finalise ops (:167-194, :233-267, :197-230, :320-375)
 __global__ __launch_bounds__(EM_BLOCK) void k_semraw_acc(SemRaw A, const float* __restrict__ p, const int* __restrict__ pcl_chan, const int* __restrict__ map_lay,

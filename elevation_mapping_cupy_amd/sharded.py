@@ -64,7 +64,7 @@ def ray_balanced_weights(cell_n: int, resolution: float, max_ray_length: float, 
 
 
 def frame_marches_by_ray(cell_n: int, n_points: int, world: int, comm_kind: str = "native", ray_mode: int = 0, scatter: str = "auto") -> bool:
-    """Will a sharded frame WITH the visibility pass march its rays by ray (csrc/emap_api.hip: rays_by_ray -- the same predicate, from
+    """Will a sharded frame WITH the visibility pass march its rays by ray (csrc/emap_api_comm.hip: rays_by_ray -- the same predicate, from
     the values every rank shares)?  Only the library's own frame (``emap_update_sharded`` over the native RCCL communicator) can; the
     stage-by-stage orchestration (ShardedElevationMap._update) always marches by row.  Strips of equal RAY work (ray_balanced_weights) are for
     frames that march by row; a by-ray frame wants equal heights (the decision must not hang on cell_n alone)."""

@@ -12,7 +12,7 @@ import _bin_variants as bv
 from oracle import emap_oracle as eo
 
 SPLIT_MAX_SLOTS = 1024            # emap_device.h, as literals
-SEM_SPLIT_SLOTS = 128             # emap_api.hip
+SEM_SPLIT_SLOTS = 128             # emap_launch.h
 
 
 @pytest.fixture(scope="module")

@@ -230,7 +230,7 @@ def test_strips_after_large_map_moves(world, ray_mode, stand_in, weights):
     elevation_mapping.py:200-214: normal_map stays), so after the move the visibility pass of the next frame reads, for every cell, the
     STALE normal at the cell's old index (custom_kernels.py:243-246) -- rows that a strip does not hold any more.  Until round 4 a
     strip read zeros there (a documented deviation); now every rank fetches the rows its cells belong to from whoever owns them
-    (emap_api.hip: normal_exchange): strips == single context, bit for bit, by row and by ray."""
+    (emap_api_comm.hip: normal_exchange): strips == single context, bit for bit, by row and by ray."""
     from oracle import emap_oracle as eo
     cfg = dict(eo.DEFAULTS); cfg.update(eo.YAML)
     cfg["enable_visibility_cleanup"] = True

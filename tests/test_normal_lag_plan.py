@@ -1,4 +1,4 @@
-"""CPU: the exchange plan of the un-shifted normal planes on row strips (emap_api.hip: lag_pieces / normal_exchange, exposed as
+"""CPU: the exchange plan of the un-shifted normal planes on row strips (emap_api_comm.hip: lag_pieces / normal_exchange, exposed as
 emap_normal_lag_plan).  After a row shift the normal of the cell in physical row p lives in physical row (p + lag) mod C of the planes
 (the reference does not shift normal_map: EM/elevation_mapping.py:200-214); every rank fetches the rows its cells belong to from whoever
 owns them.  Properties: every row of every rank's copy is written exactly once and from the right row; sources are owned rows; both

@@ -1,5 +1,5 @@
 """CPU: the two in-process RCCL stand-ins of the multi-rank GPU tests (tests/fake_rccl/) decode the data-type and reduction-operator
-arguments as plain integers.  Those integers must be the values of the REAL rccl.h the library is compiled against (csrc/emap_api.hip
+arguments as plain integers.  Those integers must be the values of the REAL rccl.h the library is compiled against (csrc/emap_api_comm.hip
 passes ncclFloat64 / ncclFloat32 / ncclInt64 / ncclUint32 / ncclChar, ncclSum / ncclMax): otherwise the stand-ins would test another
 protocol than the one RCCL sees on a multi-GPU node."""
 import os
@@ -30,8 +30,10 @@ def test_stand_in_constants_are_rccl_s(tmp_path):
         assert "op == %d" % sum_ in txt, f
         assert "char internal[128]" in txt, f
     # ... and the library asks only for what the stand-ins implement
-    api = open(os.path.join(ROOT, "elevation_mapping_cupy_amd", "csrc", "emap_api.hip")).read()
+    csrc = os.path.join(ROOT, "elevation_mapping_cupy_amd", "csrc")
+    api = "\n".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".cpp", ".h")))
     used_types = set(re.findall(r"\b(ncclFloat64|ncclFloat32|ncclFloat16|ncclInt64|ncclUint64|ncclInt32|ncclUint32|ncclInt8|ncclUint8|ncclChar|ncclBfloat16)\b", api))
     used_ops = set(re.findall(r"\b(ncclSum|ncclProd|ncclMax|ncclMin|ncclAvg)\b", api))
+    assert used_types and used_ops, "no RCCL call found under csrc/: this test reads the wrong files"
     assert used_types <= {"ncclFloat64", "ncclFloat32", "ncclInt64", "ncclUint32", "ncclChar"}, used_types
     assert used_ops <= {"ncclSum", "ncclMax"}, used_ops
