@@ -1124,6 +1124,8 @@ __global__ __launch_bounds__(SEM_BLK) void k_tile_semantic(KP P, BinGeo G, SemSp
           if (lrow >= P.nrows) break;
           const unsigned int cn = s_col[3][lc];
           if (cn == 0) continue;
+          // color_average_kernel's launch size (fusion/pointcloud_color.py:151): cell * K + layer < C * C, flat LOGICAL cell index
+          if (((long)logi_row(P, P.row0 + lrow) * P.C + logi_col(P, col)) * K + l >= (long)P.C * P.C) continue;
           const unsigned int rr = s_col[0][lc] / cn, gg = s_col[1][lc] / cn, bb = s_col[2][lc] / cn;
           sem[(long)S.col_layer[l] * plane + (long)(lrow + P.halo) * P.C + col] = __uint_as_float((rr << 16) + (gg << 8) + bb);
         }

@@ -31,7 +31,8 @@ __global__ __launch_bounds__(EM_BLOCK) void k_sem_sum(KP P, Pose T, SemSpec S, c
 
 // add_color_kernel (:270-317).  The reference launches it with size = N while decoding id = i / K, layer = i % K
 // (fusion/pointcloud_color.py:143): with K colour channels only the first N/K points contribute
-// and the shared counter is incremented once per (point, layer).  Reproduced literally.
+// and the shared counter is incremented once per (point, layer).  Reproduced literally (and k_sem_finalize reproduces the same
+// decode of color_average_kernel over the cells).
 template <int MODE>
 __global__ __launch_bounds__(EM_BLOCK) void k_sem_color(KP P, Pose T, SemSpec S, const float* __restrict__ pts, long n, int stride, ChanView V,
                                                          unsigned int* __restrict__ col, long plane) {
@@ -92,7 +93,12 @@ __global__ __launch_bounds__(EM_BLOCK) void k_sem_finalize(KP P, SemSpec S, cons
     const int K = S.n_col;
     const unsigned int k = col[(long)(K * 3) * plane + c];
     if (k > 0) {
+      // color_average_kernel decodes id = i / K, layer = i % K too and is launched with size = C * C (fusion/pointcloud_color.py:151):
+      // element (cell, layer) exists only while cell * K + layer < C * C, the reference's flat LOGICAL cell index
+      const int lrow_ = (int)(li / P.C);
+      const long gcell = (long)logi_row(P, P.row0 + lrow_) * P.C + logi_col(P, (int)(li - (long)lrow_ * P.C));
       for (int l = 0; l < K; ++l) {
+        if (gcell * K + l >= (long)P.C * P.C) continue;
         unsigned int r = col[(long)(l * 3) * plane + c] / k, g = col[(long)(l * 3 + 1) * plane + c] / k, b = col[(long)(l * 3 + 2) * plane + c] / k;
         sem[(long)S.col_layer[l] * plane + c] = __uint_as_float((r << 16) + (g << 8) + b);
       }

@@ -516,25 +516,34 @@ void eo_sem_bayesian_inference(const eo_params* P, const float* pts, long n, lon
   }
   free(sums);
 }
-/* colour: one packed 0x00RRGGBB channel; integer mean per component (truncating division) */
-void eo_sem_color(const eo_params* P, const float* pts, long n, long stride, const float* R, const float* t,
-                  int pcl_chan, int layer, float* smap) {
+/* colour (reference fusion/pointcloud_color.py:131-152; add_color_kernel + color_average_kernel, custom_semantic_kernels.py:270-375),
+ * K packed 0x00RRGGBB channels as the reference LAUNCHES them: both kernels decode id = i / K, layer = i % K, but add_color runs over
+ * size = N elements (not N * K) and color_average over size = C * C (not C * C * K).  So point id feeds layer l only while
+ * id * K + l < N, cell id gets layer l only while id * K + l < C * C (the flat cell index: with K = 2 the upper half of the rows),
+ * and ONE counter plane is incremented once per (point, layer) element -- the component sums of every layer are divided by the
+ * elements of ALL layers in the cell (truncating integer division).  K = 1: the plain per-cell integer mean. */
+void eo_sem_colors(const eo_params* P, const float* pts, long n, long stride, const float* R, const float* t,
+                   int K, const int32_t* pcl_chan, const int32_t* layer, float* smap) {
   const long L = (long)P->cell_n * P->cell_n;
-  uint32_t* acc = (uint32_t*)calloc((size_t)4 * L, 4);
+  uint32_t* acc = (uint32_t*)calloc((size_t)(3 * K + 1) * L, 4);
   for (long i = 0; i < n; ++i) {
-    pt_t g = point_geometry(P, pts + i * stride, R, t);
+    const long id = i / K; const int l = (int)(i % K);
+    pt_t g = point_geometry(P, pts + id * stride, R, t);
     if (!g.finite || !g.valid || !g.inside) continue;
-    uint32_t col = f2u(pts[i * stride + pcl_chan]);
-    acc[g.idx] += (col >> 16) & 0xff; acc[L + g.idx] += (col >> 8) & 0xff; acc[2 * L + g.idx] += col & 0xff;
-    acc[3 * L + g.idx] += 1;
+    uint32_t col = f2u(pts[id * stride + pcl_chan[l]]);
+    acc[(long)(3 * l) * L + g.idx] += (col >> 16) & 0xff; acc[(long)(3 * l + 1) * L + g.idx] += (col >> 8) & 0xff;
+    acc[(long)(3 * l + 2) * L + g.idx] += col & 0xff;
+    acc[(long)(3 * K) * L + g.idx] += 1;
   }
-  for (long c = 0; c < L; ++c) if (acc[3 * L + c]) {
-    uint32_t k = acc[3 * L + c], r = acc[c] / k, g = acc[L + c] / k, b = acc[2 * L + c] / k;
-    smap[(long)layer * L + c] = u2f((r << 16) + (g << 8) + b);
+  for (long i = 0; i < L; ++i) {
+    const long id = i / K; const int l = (int)(i % K);
+    const uint32_t k = acc[(long)(3 * K) * L + id];
+    if (!k) continue;
+    uint32_t r = acc[(long)(3 * l) * L + id] / k, g = acc[(long)(3 * l + 1) * L + id] / k, b = acc[(long)(3 * l + 2) * L + id] / k;
+    smap[(long)layer[l] * L + id] = u2f((r << 16) + (g << 8) + b);
   }
   free(acc);
 }
-
 /* ---- safety polygon: polygon_mask_kernel (reference kernels/custom_kernels.py:509-651).  get_idx of THIS kernel divides in
  * fp32 (`const float resolution`), rounds coordinates / centre / index through float16 like the other helpers. ---- */
 typedef struct { int x, y; } pt_i;

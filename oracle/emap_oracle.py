@@ -249,9 +249,10 @@ class OracleMap:
         if bayesian_inference:
             ch = np.array([c for c, _ in bayesian_inference], np.int32); ly = np.array([l for _, l in bayesian_inference], np.int32)
             lib().eo_sem_bayesian_inference(ct.byref(self.P), _p(pts), n, st, _p(R), _p(t), _p(cnt), ct.c_int(len(ch)), _p(ch), _p(ly), _p(sm))
-        assert len(color) <= 1, "oracle restates the single-colour-channel case (K>1 is a reference launch-size quirk)"
-        for c_, l_ in color:
-            lib().eo_sem_color(ct.byref(self.P), _p(pts), n, st, _p(R), _p(t), ct.c_int(c_), ct.c_int(l_), _p(sm))
+        if color:      # K channels in ONE call: the reference's launch sizes couple them (emap_oracle.c: eo_sem_colors)
+            assert len(color) <= 4, "at most four colour channels (include/emap_hip.h: emap_sem_spec)"
+            ch = np.array([c for c, _ in color], np.int32); ly = np.array([l for _, l in color], np.int32)
+            lib().eo_sem_colors(ct.byref(self.P), _p(pts), n, st, _p(R), _p(t), ct.c_int(len(ch)), _p(ch), _p(ly), _p(sm))
 
     # ---- map shift (reference elevation_mapping.py:139-226): host array code, restated in NumPy ----------------------------
     def move_to(self, position):

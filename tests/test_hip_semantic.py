@@ -79,11 +79,13 @@ def test_shift_moves_semantic_layers_with_the_map():
 
 def test_two_colour_channels_quirk_same_on_both_paths():
     """K = 2 colour channels: the reference launches add_color_kernel with size = N while decoding id = i / K
-    (SURVEY appendix B.12); both device paths must reproduce that identically, plus 6 averaged channels (> one LDS group)."""
+    (SURVEY appendix B.12), and color_average_kernel with size = C * C under the same decode; both device paths must reproduce that
+    identically and as the oracle restates it (pinned by the reference's compiled kernels: tests/test_oracle_vs_reference_source.py),
+    plus 6 averaged channels (> one LDS group)."""
     C, N = 130, 20000
     res = []
     for scatter in ("atomic", "binned"):
-        hip, _ = _hip(C)
+        hip, orc = _hip(C)
         hip.set_scatter_mode(scatter)
         hip.param.pointcloud_channel_fusions = {"rgb.*": "color", "default": "average"}
         R, t = fx.POSES["rotated"]
@@ -99,6 +101,11 @@ def test_two_colour_channels_quirk_same_on_both_paths():
     assert np.array_equal(res[0][:2].view(np.uint32), res[1][:2].view(np.uint32))
     assert np.allclose(res[0][2:], res[1][2:], atol=1e-6, rtol=1e-6)
     assert (res[0][0].view(np.uint32) != 0).sum() > 100
+    orc.update_map_with_kernel(p, R, t, 0.0, 0.0)
+    orc.semantic_update(p, R, t, average=[(5 + k, 2 + k) for k in range(6)], color=[(3, 0), (4, 1)])
+    for sm in res:
+        assert np.array_equal(sm[:2].view(np.uint32), orc.semantic_map[:2].view(np.uint32))
+        assert np.allclose(sm[2:], orc.semantic_map[2:8], atol=1e-6, rtol=1e-5)
 
 
 BAYES_CH = ["x", "y", "z", "p0", "p1", "b0", "rgb"]

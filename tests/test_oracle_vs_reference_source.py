@@ -472,6 +472,51 @@ def test_fuzz_semantic_point_fusions_vs_reference_source():
         assert np.array_equal(om.semantic_map[3].view(np.uint32), sem[3].view(np.uint32)), "case %d: packed colour" % case
 
 
+@pytest.mark.parametrize("K", [2, 3, 4])
+def test_fuzz_k_colour_channels_vs_reference_source(K):
+    """add_color_kernel + color_average_kernel with K = 2, 3, 4 colour channels, launched as fusion/pointcloud_color.py:135-152 launches
+    them: size = N points and size = C * C cells while both decode id = i / K, layer = i % K, one shared counter plane.  Clouds whose N
+    is and is not a multiple of K, channels and layers in no particular order, layers that hold something before: the packed layers bit
+    for bit.  (With K > 1 only the first C * C / K cells are ever written.)"""
+    rk = _ref("yaml66")
+    params = build_ref.PREBUILD["yaml66"]
+    C, cols = 66, 9
+    rng = np.random.default_rng(616 + K)
+    covered = 0
+    for case, N in enumerate((6000 + (-6000) % K, 6001 + (-6000) % K, 5999, 6007, 12 * K)):
+        R, t = _random_pose(rng)
+        t[:2] *= np.float32(0.3)
+        Rf = R.ravel().copy()
+        p = fx.cloud(C, N, 720 + case, extra=cols - 3)
+        for c in range(3, cols):
+            p[:, c] = rng.integers(0, 1 << 24, N, dtype=np.uint32).view(np.float32)
+        k = p[1::3].shape[0]
+        p[:3 * k:3, :2] = p[1::3, :2]
+        chans = rng.permutation(np.arange(3, cols))[:K].astype(np.int32)
+        layers = rng.permutation(5)[:K].astype(np.int32)
+        prev = rng.integers(0, 1 << 24, (5, C, C), dtype=np.uint32).view(np.float32)
+        m = np.zeros((7, C, C), np.float32); m[1] = params["initial_variance"]; m[3] = 1
+        nm = np.zeros((7, C, C), np.float32); nrm = np.zeros((3, C, C), np.float32)
+        err = np.zeros(1, np.float32); cnt = np.zeros(1, np.float32)
+        xyz = np.ascontiguousarray(p[:, :3])
+        rk.error_counting(m, xyz, Rf, t.copy(), nm, err, cnt); rk.add_points(Rf, t.copy(), nrm, xyz, m, nm)
+        pc = p.copy(); pc[:, :3] = xyz
+        sem = prev.copy()
+        color_map = np.zeros((3 * K + 1, C, C), np.uint32)
+        shape = np.array([cols, K], np.int32)
+        rk.sem_add_color(pc, Rf, t.copy(), chans, layers, shape, color_map, N)
+        rk.sem_color_average(color_map, chans, layers, shape, sem, C * C)
+        om = eo.OracleMap(eo.make_params(eo.YAML, cell_n=C))
+        om.count(p, R, t); om.gate(0, 0); om.fuse(p, R, t)
+        om.semantic_map = prev.copy()
+        om.semantic_update(p, R, t, color=list(zip(chans.tolist(), layers.tolist())))
+        assert np.array_equal(om.semantic_map.view(np.uint32), sem.view(np.uint32)), "K %d case %d (N %d): packed colour layers" % (K, case, N)
+        changed = (sem.view(np.uint32) != prev.view(np.uint32)).any(axis=0)
+        assert int(np.flatnonzero(changed).max()) < (C * C + K - 1) // K
+        covered += int(changed.sum())
+    assert N % K == 0 and covered > 200, "the sweep must colour the map"
+
+
 def test_fuzz_bayesian_point_fusions_vs_reference_source():
     """class_bayesian (alpha_kernel + renormalisation, the K = 2 launch-size quirk, negative theta ignored, persistent pseudo-counts)
     and bayesian_inference (sum_compact + bayesian_inference kernels) as the reference's fusions run them
