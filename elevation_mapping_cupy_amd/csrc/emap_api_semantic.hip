@@ -3,6 +3,7 @@
 // pointcloud_class_max and the camera path.
 #include "emap_host.h"
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -317,9 +318,14 @@ int emap_semantic_clear(emap_ctx* ctx) {
 }
 
 // ---- camera path (EM/elevation_mapping.py:468-562, EM/kernels/custom_image_kernels.py) -------------------------------
+static bool cam_cell_ok(float v) { return std::isfinite(v) && v == truncf(v) && fabsf(v) <= (float)EM_CAM_CELL_MAX; }
 int emap_image_correspondence(emap_ctx* ctx, float x1, float y1, float z1, const float P[12], const float K[9], const float D[5],
                               float image_height, float image_width, const float center[3]) {
-  CKARG(ctx && P && K && D && center, "null argument"); SF_CHECK();
+  CKARG(ctx && P && K && D && center, "null argument");
+  // the walk of k_image_corr terminates by reaching (x1, y1) exactly: refuse, before anything is launched, a camera cell it cannot reach
+  // (not finite, not integer valued) or would take too long to reach (EM_CAM_CELL_MAX).  The reference does not terminate there.
+  CKARG(cam_cell_ok(x1) && cam_cell_ok(y1), "camera cell (x1, y1) must be integer valued and within +-65536 cells");
+  SF_CHECK();
   CKARG(ctx->strip.halo_rows == 0 && ctx->strip.row_count == ctx->prm.cell_n, "camera path: single-strip contexts only");
   CK(hipSetDevice(ctx->device));
   FLUSH();

@@ -8,6 +8,10 @@
 // ---- kernel arguments built on the host (host files) and read by value in kernels (emap_semantic.hip) ----------------------------
 struct SemRaw { int op, stride, K, n_max; long size, cells; double alpha; };      // the semantic kernel factories on caller arrays (k_semraw_acc / k_semraw_fin)
 struct CamArgs { float P[12], K[9], D[5], center[3]; float x1, y1, z1, ih, iw; double tol; };      // tol = tolerance_z_collision (custom_image_kernels.py:9; 0.10 in the reference's call)
+// The occlusion walk of k_image_corr ends only when it REACHES the camera cell (x1, y1): the cell must be integer valued, and its
+// magnitude bounds the walk's length.  65536 cells is a cap, not a measurement: 2.6 km at 4 cm cells, far beyond any map, and it keeps
+// every walk short.  emap_image_correspondence refuses anything else before it launches (ElevationMap.camera_cell raises the same way).
+#define EM_CAM_CELL_MAX 65536
 struct CmaxSpec { int n; int chan[8]; int layer[8]; };      // pointcloud_class_max: the fusion's channels and layers
 
 // ---- limits shared by the host layer and emap_binned.hip -----------------------------------------------------------------------------

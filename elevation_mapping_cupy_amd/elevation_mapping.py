@@ -39,6 +39,35 @@ def _hull_ring(cells):
     return np.vstack([pts[v], pts[v[:1]]])
 
 
+CAM_CELL_MAX = 65536      # EM_CAM_CELL_MAX (csrc/emap_launch.h): a cap, not a measurement -- 2.6 km at 4 cm cells, far beyond any map
+
+
+def camera_cell(center, cell_n, resolution, R, t):
+    """``(x1, y1, z1)`` of ``input_image``: the camera's cell (float32, integer valued) and its height above the map centre.
+
+    The reference computes ``np.float32(np.uint32(cell_n / 2 + t_cam_map / resolution))`` (elevation_mapping.py:531-534).  For a camera
+    more than half a map width on the low side of the centre that cast wraps to about 2**32, and the occlusion walk, which ends only
+    by reaching the camera cell, never ends.  DEPARTURE: the index is a SIGNED integer truncated toward zero -- bit for bit the
+    reference's value wherever that one is non-negative, the negative index otherwise (the walk then behaves as it does for a camera
+    cell beyond the high side) -- and a pose whose index is not finite or exceeds ``CAM_CELL_MAX`` in magnitude raises ``ValueError``
+    instead of being launched."""
+    R = np.asarray(R, np.float32); t = np.asarray(t, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):      # a pose that is not finite is refused below, not warned about
+        t_cam_map = -R.T @ t - center
+    cell = []
+    for a in (0, 1):
+        v = (cell_n / 2) + (t_cam_map[a] / resolution)
+        if not np.isfinite(v):
+            raise ValueError("camera pose: cell index along axis %d is not finite (%r)" % (a, v))
+        i = int(v)                      # toward zero, like the C cast behind np.uint32(...)
+        if abs(i) > CAM_CELL_MAX:
+            raise ValueError("camera pose: cell index %d along axis %d is beyond +-%d cells" % (i, a, CAM_CELL_MAX))
+        cell.append(np.float32(i))
+    if not np.isfinite(t_cam_map[2]):
+        raise ValueError("camera pose: height is not finite (%r)" % (t_cam_map[2],))
+    return cell[0], cell[1], np.float32(t_cam_map[2])
+
+
 class LazyPlanes:
     """What a plugin receives as ``elevation_map`` / ``semantic_map``: behaves like the reference's ``(L, rows, C)`` array -- ``shape``,
     ``dtype``, ``ndim``, indexing, iteration, arithmetic, ``copy()`` and every other ndarray attribute work -- but a plane only crosses
@@ -476,10 +505,7 @@ class ElevationMap:
         if distortion_model != "radtan":
             D = D * 0            # equidistant / plumb_bob: "not implemented yet" in the reference -> no distortion
         P = (K @ np.concatenate([R, t[:, None]], 1)).astype(np.float32)
-        t_cam_map = -R.T @ t - self.center
-        x1 = np.float32(np.uint32((self.cell_n / 2) + (t_cam_map[0] / self.resolution)))
-        y1 = np.float32(np.uint32((self.cell_n / 2) + (t_cam_map[1] / self.resolution)))
-        z1 = np.float32(t_cam_map[2])
+        x1, y1, z1 = camera_cell(self.center, self.cell_n, self.resolution, R, t)
         with self.map_lock:
             self._chk(self._lib.emap_image_correspondence(
                 self._ctx, ct.c_float(x1), ct.c_float(y1), ct.c_float(z1), f32p(np.ascontiguousarray(P.reshape(-1))),

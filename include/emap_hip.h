@@ -280,12 +280,18 @@ int emap_inpaint_telea_fronts_u8(emap_inpainter* ip, const uint8_t* image, const
 
 /* ---- camera path: ElevationMap.input_image (EM/elevation_mapping.py:468-562).
  * emap_image_correspondence = image_to_map_correspondence_kernel (EM/kernels/custom_image_kernels.py:9-157): x1, y1 = camera
- * cell (uint32 valued), z1 = camera height above the map centre, P = K [R|t] row major, D = 5 radtan coefficients (all 0 =
+ * cell (integer valued, see GUARD), z1 = camera height above the map centre, P = K [R|t] row major, D = 5 radtan coefficients (all 0 =
  * none).  emap_image_fuse = exponential_ (kind 0, alpha 0.7 in the reference) / color_ (kind 1, planes 0..2 = r,g,b) / average_
  * (kind 2: the sample replaces the value, :160-192) correspondences_to_map_kernel applied to semantic layer `layer` with a host image
  * (n_planes, H, W) float32.  emap_image_set_tolerance = the factory parameter tolerance_z_collision of the occlusion walk (:9; the
  * reference's only call passes 0.10, the default).  emap_image_fuse_arrays = the same three kernels on caller arrays (one
- * (cell_n, cell_n) semantic plane in, one out, uv (2, cell_n, cell_n), valid (cell_n, cell_n) bytes): what the kernel factories bind. */
+ * (cell_n, cell_n) semantic plane in, one out, uv (2, cell_n, cell_n), valid (cell_n, cell_n) bytes): what the kernel factories bind.
+ * GUARD (a departure from the reference, whose kernel does not terminate there): the occlusion walk ends only by REACHING the camera
+ * cell, so emap_image_correspondence returns EMAP_ERR_INVALID, before anything is launched and with the previous correspondence
+ * untouched, when x1 or y1 is not finite, not integer valued, or beyond 65536 cells in magnitude (a cap, not a measurement: 2.6 km at
+ * 4 cm cells).  A NEGATIVE integer cell is valid: a camera on the low side of the map, walked like one beyond the high side.  The
+ * reference casts the cell through uint32, which wraps such a pose to about 2^32; ElevationMap.input_image computes a signed index
+ * instead (camera_cell) and raises ValueError beyond the same cap. */
 int emap_image_correspondence(emap_ctx* ctx, float x1, float y1, float z1, const float P[12], const float K[9], const float D[5],
                               float image_height, float image_width, const float center[3]);
 int emap_image_get_correspondence(emap_ctx* ctx, float* uv_host /* (2, cell_n, cell_n) */, uint8_t* valid_host);

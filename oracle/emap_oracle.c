@@ -598,10 +598,13 @@ void eo_polygon_mask(const eo_params* P, const float* polygon, int n, float cx, 
  * x1, y1 (camera cell, uint32 valued), z1, image_height, image_width arrive as float32 like in the reference call
  * (elevation_mapping.py:531-554). ---- */
 static inline float l2_distance(int x0, int y0, int x1, int y1) { float dx = x0 - x1, dy = y0 - y1; return sqrtf(dx * dx + dy * dy); }
-void eo_image_correspondence(const eo_params* P, const float* map, float x1, float y1, float z1, const float* Pm, const float* K,
-                             const float* D, float image_height, float image_width, const float* center, float* uv, uint8_t* valid) {
+/* tol = tolerance_z_collision, the factory parameter of the kernel (:9); the reference's only call passes 0.10.  The walk ends only by
+ * reaching (x1, y1): the Python wrapper refuses a camera cell that is not an integer within the library's cap, as the C ABI does. */
+void eo_image_correspondence_tol(const eo_params* P, const float* map, float x1, float y1, float z1, const float* Pm, const float* K,
+                                 const float* D, float image_height, float image_width, const float* center, double tol, float* uv,
+                                 uint8_t* valid) {
   const int W = P->cell_n; const long L = (long)W * W;
-  const double res = P->resolution, tol = 0.10;
+  const double res = P->resolution;
   for (long i = 0; i < L; ++i) {
     if (map[2 * L + i] != 1) continue;
     int y0 = (int)(i % W), x0 = (int)(i / W);
@@ -645,6 +648,10 @@ void eo_image_correspondence(const eo_params* P, const float* map, float x1, flo
     }
     uv[i] = u; uv[L + i] = v; valid[i] = (uint8_t)ok;
   }
+}
+void eo_image_correspondence(const eo_params* P, const float* map, float x1, float y1, float z1, const float* Pm, const float* K,
+                             const float* D, float image_height, float image_width, const float* center, float* uv, uint8_t* valid) {
+  eo_image_correspondence_tol(P, map, x1, y1, z1, Pm, K, D, image_height, image_width, center, 0.10, uv, valid);
 }
 /* kind 0: exponential (alpha), image = (H, W) plane; kind 1: colour, image = (3, H, W) planes; updates `sem` in place */
 void eo_image_fuse(const eo_params* P, int kind, float* sem, const float* image, const float* uv, const uint8_t* valid,

@@ -348,14 +348,23 @@ class OracleMap:
         return st
 
 
-def image_correspondence(P, emap, x1, y1, z1, Pm, K, D, image_height, image_width, center):
-    """reference image_to_map_correspondence_kernel; returns (uv (2,C,C) float32, valid (C,C) uint8)"""
+CAM_CELL_MAX = 65536      # EM_CAM_CELL_MAX of the library (csrc/emap_launch.h)
+
+
+def image_correspondence(P, emap, x1, y1, z1, Pm, K, D, image_height, image_width, center, tolerance_z_collision=0.10):
+    """reference image_to_map_correspondence_kernel; returns (uv (2,C,C) float32, valid (C,C) uint8).  The occlusion walk ends only
+    by reaching the camera cell, so a cell it cannot reach (not finite, not integer valued) or beyond the library's cap is refused
+    here, as emap_image_correspondence refuses it, instead of spinning."""
+    for v in (x1, y1):
+        v = float(np.float32(v))
+        if not (np.isfinite(v) and v == int(v) and abs(v) <= CAM_CELL_MAX):
+            raise ValueError("camera cell %r: must be integer valued and within +-%d cells" % (v, CAM_CELL_MAX))
     C = P.cell_n
     uv, valid = np.zeros((2, C, C), np.float32), np.zeros((C, C), np.uint8)
     f = ct.c_float
     a = lambda x: _p(np.ascontiguousarray(x, np.float32))  # noqa: E731
-    lib().eo_image_correspondence(ct.byref(P), a(emap), f(x1), f(y1), f(z1), a(Pm), a(K), a(D), f(image_height), f(image_width),
-                                  a(center), _p(uv), _p(valid))
+    lib().eo_image_correspondence_tol(ct.byref(P), a(emap), f(x1), f(y1), f(z1), a(Pm), a(K), a(D), f(image_height), f(image_width),
+                                      a(center), ct.c_double(tolerance_z_collision), _p(uv), _p(valid))
     return uv, valid
 
 

@@ -163,6 +163,20 @@ def test_image_correspondence_and_fusions(dist, weights):
         assert np.array_equal(mine_a, new_a[0]) and (mine_a != sem[0]).sum() == va_r.sum()
     else:
         pytest.fail("oracle/_ref was built before image_average was added: rebuild (python -m oracle.build_ref)")
+    # the low camera of the camera case table (tests/_cam_cases.py): 0.4 m above the terrain, horizontal axis -- half the map behind it
+    # (d <= 0), image borders left / right / bottom, a wall whose middle third is stored with is_valid = 0.5 (not projected, `!= 1`,
+    # yet occluding, `!= 0`).  The compiled kernel only ever gets a non-negative integer camera cell: elsewhere its walk does not end.
+    import _cam_cases as cc
+    c = dict(cc.by_name("low_wall_radtan" if dist else "low_wall"))
+    assert c["C"] == C and c["tol"] is None
+    wall = cc.camera_map(C)
+    uv_w, va_w, (Pm_w, x1, y1, z1, K_w, D_w, center_w) = cc.oracle_run(eo, om.P, c, wall)
+    assert float(x1) == int(x1) >= 0 and float(y1) == int(y1) >= 0
+    uv_r = np.zeros((2, C, C), np.float32); va_r = np.zeros((C, C), np.bool_)
+    rk.image_correspondence(wall.copy(), x1, y1, z1, Pm_w.ravel().copy(), K_w.ravel().copy(), D_w.copy(), c["H"], c["W"], center_w, uv_r, va_r)
+    _, counts = cc.classify(c, wall, uv_w, va_w, (Pm_w, x1, y1, z1, K_w, D_w, center_w))
+    assert min(counts[k] for k in ("unknown", "behind", "off-left", "off-right", "off-bottom", "occluded", "visible")) >= 100
+    assert np.array_equal(va_w.astype(bool), va_r) and np.array_equal(uv_w, uv_r)
 
 
 @pytest.mark.parametrize("center", [(0.0, 0.0), (0.52, -0.28)])
