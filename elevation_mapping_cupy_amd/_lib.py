@@ -47,6 +47,12 @@ class EmapSemSpec(ct.Structure):
                 ("n_col", ct.c_int32), ("col_chan", ct.c_int32 * 4), ("col_layer", ct.c_int32 * 4), ("alpha", ct.c_double)]
 
 
+class EmapDepthDesc(ct.Structure):
+    """struct emap_depth_desc (include/emap_hip.h: emap_bind_depth_image)."""
+    _fields_ = ([(n, ct.c_int32) for n in ("height", "width", "depth_dtype", "step", "has_rgb", "n_features")] +
+                [(n, ct.c_float) for n in ("fx", "fy", "cx", "cy", "depth_scale", "min_depth", "max_depth", "confidence_threshold")])
+
+
 MODE = {"reference_fp16": 0, "fp32": 1}
 PLANES = {"elevation": 0, "variance": 1, "is_valid": 2, "traversability": 3, "time": 4, "upper_bound": 5,
           "is_upper_bound": 6, "normal_x": 7, "normal_y": 8, "normal_z": 9, "traversability_input": 10}
@@ -55,7 +61,7 @@ STAGES = ["hist", "scan", "scatter", "gate", "fuse", "commit", "rays", "average"
 # every symbol include/emap_hip.h declares (checked by tests/test_abi.py without a GPU)
 SYMBOLS = [
     "emap_abi_version", "emap_create", "emap_destroy", "emap_set_params", "emap_last_error", "emap_sync", "emap_clear",
-    "emap_upload_points", "emap_upload_points_strip", "emap_strip_point_mask", "emap_declare_points_bucketed", "emap_set_points_device", "emap_set_points_device_split", "emap_point_index", "emap_update", "emap_count",
+    "emap_upload_points", "emap_upload_points_strip", "emap_strip_point_mask", "emap_declare_points_bucketed", "emap_set_points_device", "emap_set_points_device_split", "emap_bind_depth_image", "emap_get_bound_points", "emap_point_index", "emap_update", "emap_count",
     "emap_set_drift_inputs", "emap_drift_sums_to_device", "emap_set_drift_inputs_device",
     "emap_local_drift_sums", "emap_set_scatter_mode", "emap_fuse", "emap_fuse_average", "emap_commit", "emap_rays", "emap_average", "emap_overlap_clear",
     "emap_dilate", "emap_traversability_normals", "emap_post", "emap_post_part", "emap_update_variance", "emap_update_time", "emap_get_stats",
@@ -102,6 +108,9 @@ def load():
         lib.emap_inpainter_destroy.argtypes = [ct.c_void_p]
         lib.emap_inpainter_set_steps.argtypes = [ct.c_void_p, ct.c_int32]
         lib.emap_inpaint_telea_fronts_u8.argtypes = [ct.c_void_p, u8p, u8p, ct.c_int32, ct.c_int32, ct.c_int32, u8p, ct.POINTER(ct.c_int32)]
+    if hasattr(lib, "emap_bind_depth_image"):
+        lib.emap_bind_depth_image.argtypes = [ct.c_void_p, ct.POINTER(EmapDepthDesc), ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.POINTER(ct.c_int64)]
+        lib.emap_get_bound_points.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p]
     got = int(lib.emap_abi_version())
     if got != ABI_VERSION and not os.environ.get("EMAP_HIP_LIB"):
         raise EmapError("%s speaks ABI version %d, this binding expects %d (include/emap_hip.h: EMAP_ABI_VERSION) -- rebuild with "

@@ -1,0 +1,113 @@
+// C ABI of the MI355X elevation-map fusion core, host side of the depth-image input (kernel: emap_depth.hip): a depth camera's frame
+// is uploaded as IMAGES and back-projected on the device into a cloud the context owns and binds -- the reference back-projects on
+// the host (sensor_processing/semantic_sensor/.../pointcloud_node.py:205-250, 261-269) and hands the float cloud to
+// input_pointcloud.  Also the read-back of whatever cloud is bound (emap_get_bound_points).
+#include "emap_host.h"
+#include <cmath>
+#include <cstring>
+
+using namespace emap_host;
+
+static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+extern "C" {
+
+int emap_bind_depth_image(emap_ctx* ctx, const emap_depth_desc* d, const void* depth, const uint8_t* rgb_or_null, const float* features_or_null,
+                          const float* confidence_or_null, int64_t* n_points_out) {
+  CKARG(ctx, "null ctx");
+  // everything is refused BEFORE any launch or copy: the previous binding stays as it is
+  CKARG(d && depth, "emap_bind_depth_image: null argument");
+  CKARG(d->height >= 1 && d->height <= EM_DEPTH_MAX_SIDE && d->width >= 1 && d->width <= EM_DEPTH_MAX_SIDE, "emap_bind_depth_image: image sides must lie in 1 .. 8192");
+  CKARG(d->step >= 1 && d->step <= EM_DEPTH_MAX_STEP, "emap_bind_depth_image: step must lie in 1 .. 64");
+  CKARG(d->depth_dtype == 0 || d->depth_dtype == 1, "emap_bind_depth_image: depth_dtype must be 0 (float32 metres) or 1 (uint16 units)");
+  CKARG(std::isfinite(d->fx) && std::isfinite(d->fy) && d->fx != 0.f && d->fy != 0.f, "emap_bind_depth_image: fx, fy must be finite and non-zero");
+  CKARG(std::isfinite(d->cx) && std::isfinite(d->cy) && std::isfinite(d->min_depth) && std::isfinite(d->max_depth), "emap_bind_depth_image: cx, cy, min_depth, max_depth must be finite");
+  CKARG(d->min_depth >= 0.f && d->max_depth > d->min_depth, "emap_bind_depth_image: 0 <= min_depth < max_depth required");
+  CKARG(d->depth_dtype == 0 || (std::isfinite(d->depth_scale) && d->depth_scale > 0.f), "emap_bind_depth_image: uint16 depth needs a finite depth_scale > 0");
+  CKARG(d->n_features >= 0 && d->n_features <= EM_DEPTH_MAX_CHAN && (d->has_rgb ? 1 : 0) + d->n_features <= EM_DEPTH_MAX_CHAN,
+        "emap_bind_depth_image: at most 16 channels (colour + features)");
+  CKARG((!d->has_rgb || rgb_or_null) && (d->n_features == 0 || features_or_null), "emap_bind_depth_image: null channel image");
+  // the small frames in flight keep raw pointers to the cloud they read and may be re-run after an abort: settled before the owned
+  // buffer is overwritten (as upload_impl does)
+  SF_CHECK();
+  CK(hipSetDevice(ctx->device));
+
+  DepthArgs A; memset(&A, 0, sizeof A);
+  A.H = d->height; A.W = d->width; A.step = d->step; A.Hs = (A.H + A.step - 1) / A.step; A.Ws = (A.W + A.step - 1) / A.step;
+  A.n = (long)A.Hs * A.Ws; A.plane = (long)A.H * A.W; A.has_rgb = d->has_rgb ? 1 : 0; A.n_feat = d->n_features;
+  A.fx = d->fx; A.fy = d->fy; A.cx = d->cx; A.cy = d->cy; A.depth_scale = d->depth_scale; A.min_depth = d->min_depth; A.max_depth = d->max_depth; A.conf_thr = d->confidence_threshold;
+  const int Kc = A.has_rgb + A.n_feat;
+  const size_t px = (size_t)A.plane;
+  // the images in one block, every one at a 256-byte boundary: depth | confidence | features | rgb
+  const size_t b_depth = px * (d->depth_dtype == 0 ? 4 : 2), b_conf = confidence_or_null ? px * 4 : 0, b_feat = px * 4 * (size_t)A.n_feat, b_rgb = A.has_rgb ? px * 3 : 0;
+  const size_t o_conf = up256(b_depth), o_feat = o_conf + up256(b_conf), o_rgb = o_feat + up256(b_feat), img_bytes = o_rgb + up256(b_rgb);
+  // the cloud as upload_impl lays it out: xyz (n, 3), the channel matrix behind it at a 256-byte boundary
+  const long chan_off = Kc ? ((3 * A.n + 63) & ~63L) : 0, tot = Kc ? chan_off + (long)Kc * A.n : 3 * A.n;
+
+  const int sl = ctx->depth_slot ^= 1;
+  if (!ctx->depth_ev[sl]) CK(hipEventCreateWithFlags(&ctx->depth_ev[sl], hipEventDisableTiming));
+  if (ctx->depth_ev_on[sl]) CK(hipEventSynchronize(ctx->depth_ev[sl]));      // the copy out of this slot two calls ago (long done in a running stream)
+  if (img_bytes > ctx->depth_pin_cap[sl]) {
+    if (ctx->depth_pin[sl]) CK(hipHostFree(ctx->depth_pin[sl]));
+    ctx->depth_pin[sl] = nullptr; ctx->depth_pin_cap[sl] = 0; ctx->depth_ev_on[sl] = false;
+    CK(hipHostMalloc((void**)&ctx->depth_pin[sl], img_bytes, hipHostMallocDefault));
+    ctx->depth_pin_cap[sl] = img_bytes;
+  }
+  if (img_bytes > ctx->depth_img_cap || tot > ctx->depth_cloud_cap) {
+    // growing: kernels in flight may still read either buffer, and the cloud may be the bound one -- drain, unbind, then replace
+    CK(hipStreamSynchronize(ctx->stream));
+    if (img_bytes > ctx->depth_img_cap) {
+      if (ctx->depth_img) CK(hipFree(ctx->depth_img));
+      ctx->depth_img = nullptr; ctx->depth_img_cap = 0;
+      CK(hipMalloc((void**)&ctx->depth_img, img_bytes));
+      ctx->depth_img_cap = img_bytes;
+    }
+    if (tot > ctx->depth_cloud_cap) {
+      if (ctx->depth_cloud && ctx->pts == ctx->depth_cloud) { ctx->pts = nullptr; ctx->n_pts = 0; ctx->n_pts_all = 0; ctx->pts_bucketed = false; }
+      if (ctx->depth_cloud) CK(hipFree(ctx->depth_cloud));
+      ctx->depth_cloud = nullptr; ctx->depth_cloud_cap = 0;
+      CK(hipMalloc((void**)&ctx->depth_cloud, sizeof(float) * (size_t)tot));
+      ctx->depth_cloud_cap = tot;
+    }
+  }
+  unsigned char* pin = ctx->depth_pin[sl];
+  memcpy(pin, depth, b_depth);
+  if (b_conf) memcpy(pin + o_conf, confidence_or_null, b_conf);
+  if (b_feat) memcpy(pin + o_feat, features_or_null, b_feat);
+  if (b_rgb) memcpy(pin + o_rgb, rgb_or_null, b_rgb);
+  // one block when the images fill it (the gaps are < 256 bytes each), stream-ordered behind the kernel that read the block before
+  CK(hipMemcpyAsync(ctx->depth_img, pin, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+  CK(hipEventRecord(ctx->depth_ev[sl], ctx->stream));
+  ctx->depth_ev_on[sl] = true;
+  A.depth = ctx->depth_img; A.conf = b_conf ? reinterpret_cast<const float*>(ctx->depth_img + o_conf) : nullptr;
+  A.feat = b_feat ? reinterpret_cast<const float*>(ctx->depth_img + o_feat) : nullptr; A.rgb = b_rgb ? ctx->depth_img + o_rgb : nullptr;
+  A.xyz = ctx->depth_cloud; A.chan = Kc ? ctx->depth_cloud + chan_off : nullptr;
+  launch_depth_cloud(ctx->stream, A, d->depth_dtype);
+  CK(hipGetLastError());
+  // bound exactly as emap_set_points_device_split binds a caller's de-interleaved cloud (a row-strip context: whole and unbucketed)
+  ctx->pts = ctx->depth_cloud; ctx->n_pts = A.n; ctx->stride = 3; ctx->n_cols = 3 + Kc; ctx->pts_bucketed = false; ctx->n_pts_all = A.n;
+  ctx->chan.p = Kc ? ctx->depth_cloud + chan_off : ctx->depth_cloud; ctx->chan.stride = Kc ? Kc : 3; ctx->chan.col0 = Kc ? 3 : 0;
+  if (n_points_out) *n_points_out = A.n;
+  return EMAP_OK;
+}
+
+int emap_get_bound_points(emap_ctx* ctx, float* xyz_host, float* chan_host_or_null) {
+  CKARG(ctx && xyz_host, "null argument"); SF_CHECK();
+  if (!ctx->pts) { ctx->err = "no point cloud bound"; return EMAP_ERR_NO_POINTS; }
+  CK(hipSetDevice(ctx->device));
+  const size_t n = (size_t)ctx->n_pts, K = (size_t)(ctx->n_cols - 3);
+  if (n) {
+    // rows of `stride` floats (xyz) / of chan.stride floats with the caller's column 3 at chan.p + 3 - col0 (emap_device.h: ChanView)
+    if (ctx->stride == 3) CK(hipMemcpyAsync(xyz_host, ctx->pts, 12 * n, hipMemcpyDeviceToHost, ctx->stream));
+    else CK(hipMemcpy2DAsync(xyz_host, 12, ctx->pts, sizeof(float) * (size_t)ctx->stride, 12, n, hipMemcpyDeviceToHost, ctx->stream));
+    if (chan_host_or_null && K) {
+      const float* src = ctx->chan.p + (3 - ctx->chan.col0);
+      if ((size_t)ctx->chan.stride == K) CK(hipMemcpyAsync(chan_host_or_null, src, sizeof(float) * K * n, hipMemcpyDeviceToHost, ctx->stream));
+      else CK(hipMemcpy2DAsync(chan_host_or_null, sizeof(float) * K, src, sizeof(float) * (size_t)ctx->chan.stride, sizeof(float) * K, n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+  }
+  CK(hipStreamSynchronize(ctx->stream));
+  return EMAP_OK;
+}
+
+}  // extern "C"

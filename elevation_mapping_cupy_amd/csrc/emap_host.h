@@ -136,6 +136,11 @@ struct emap_ctx {
   bool pts_bucketed; float bucket_R[9], bucket_t[3]; int bucket_org_r;   // the bound cloud only holds the points that can land in this strip's rows under this pose (emap_upload_points_strip)
   ChanView chan; int n_cols;                        // its extra channels (emap_device.h: ChanView); n_cols = columns of the caller's matrix (3 + K)
   int* tail_idx; unsigned char* tail_flags; long tail_cap;
+  // depth-image input (emap_api_depth.hip): the cloud k_depth_cloud writes lives in ONE owned buffer (stream order: the kernels of the
+  // frame before precede the overwrite); the caller's images pass through two pinned slots into one device buffer
+  float* depth_cloud; long depth_cloud_cap;                   // floats
+  unsigned char* depth_img; size_t depth_img_cap;             // bytes
+  unsigned char* depth_pin[2]; size_t depth_pin_cap[2]; hipEvent_t depth_ev[2]; bool depth_ev_on[2]; int depth_slot;   // depth_ev: the slot's H2D copies are done
   // frame state
   bool use_override; double sum_override; unsigned int cnt_override;
   bool committed;

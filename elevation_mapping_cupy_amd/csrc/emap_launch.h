@@ -13,6 +13,12 @@ struct CamArgs { float P[12], K[9], D[5], center[3]; float x1, y1, z1, ih, iw; d
 // every walk short.  emap_image_correspondence refuses anything else before it launches (ElevationMap.camera_cell raises the same way).
 #define EM_CAM_CELL_MAX 65536
 struct CmaxSpec { int n; int chan[8]; int layer[8]; };      // pointcloud_class_max: the fusion's channels and layers
+// k_depth_cloud (emap_depth.hip): the images on the device, the sampled grid (Hs x Ws = n rows) and the cloud it writes; plane = H W
+struct DepthArgs { int H, W, step, Hs, Ws, has_rgb, n_feat; long n, plane; float fx, fy, cx, cy, depth_scale, min_depth, max_depth, conf_thr;
+                   const void* depth; const float* conf; const unsigned char* rgb; const float* feat; float* xyz; float* chan; };
+#define EM_DEPTH_MAX_SIDE 8192      /* emap_bind_depth_image: image sides, step and channel count it accepts */
+#define EM_DEPTH_MAX_STEP 64
+#define EM_DEPTH_MAX_CHAN 16
 
 // ---- limits shared by the host layer and emap_binned.hip -----------------------------------------------------------------------------
 #define BIN_MAX_T 16384   /* LDS histogram / cursor arrays are dynamic: 4 B per tile */
@@ -78,3 +84,6 @@ size_t sem_split_bytes(int);
 bool sem_split_possible(const SemSpec&);
 void launch_bin_fuse(hipStream_t, const KP&, const BinGeo&, const BinRec*, int, const unsigned int*, Cells, AccF*, FrameDev*, bool, bool, unsigned int*, unsigned long long*, unsigned int*, float*, const OverlapArgs&, const GateFold&, const SplitView&, long, const SemMini*);
 bool bin_fuse_takes_semantics(const SplitView&, bool, bool, int);
+
+// depth-image input (emap_depth.hip)
+void launch_depth_cloud(hipStream_t, const DepthArgs&, int);

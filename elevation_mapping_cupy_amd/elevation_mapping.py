@@ -15,7 +15,7 @@ from typing import List
 import numpy as np
 
 from . import _lib
-from ._lib import EmapError, EmapParams, EmapStats, EmapStrip, PLANES, f32p
+from ._lib import EmapDepthDesc, EmapError, EmapParams, EmapStats, EmapStrip, PLANES, f32p
 from .parameter import Parameter
 
 
@@ -373,12 +373,12 @@ class ElevationMap:
             kept = ct.c_int64(0)
             self._chk(self._lib.emap_upload_points_strip(self._ctx, ct.c_void_p(pts.ctypes.data), ct.c_int64(pts.shape[0]),
                                                          ct.c_int64(pts.shape[1]), dtype, f32p(R), f32p(t), ct.byref(kept)))
-            self._n_bound = int(kept.value)
+            self._n_bound, self._k_bound = int(kept.value), pts.shape[1] - 3
             self._bound_host = None                 # (the bound cloud is a subset: nothing indexes the host copy by point)
             return self._n_bound
         self._chk(self._lib.emap_upload_points(self._ctx, ct.c_void_p(pts.ctypes.data), ct.c_int64(pts.shape[0]),
                                                ct.c_int64(pts.shape[1]), dtype))
-        self._n_bound = pts.shape[0]
+        self._n_bound, self._k_bound = pts.shape[0], pts.shape[1] - 3
         self._bound_host = pts
         return self._n_bound
 
@@ -396,15 +396,72 @@ class ElevationMap:
     def bind_points_device(self, dev_ptr, n, stride):
         """Bind a device-resident float32 cloud (raw pointer) without copying."""
         self._chk(self._lib.emap_set_points_device(self._ctx, ct.c_void_p(dev_ptr), ct.c_int64(n), ct.c_int64(stride)))
-        self._n_bound = n
+        self._n_bound, self._k_bound = n, stride - 3
         self._bound_host = None
 
     def bind_points_device_split(self, xyz_ptr, chan_ptr, n, n_chan):
         """Bind a device-resident cloud that is already de-interleaved: xyz ``(n, 3)`` and the extra channels ``(n, n_chan)``, both
         row-major float32 (the layout ``bind_points`` / ``input_pointcloud`` give an uploaded cloud)."""
         self._chk(self._lib.emap_set_points_device_split(self._ctx, ct.c_void_p(xyz_ptr), ct.c_void_p(chan_ptr), ct.c_int64(n), ct.c_int64(n_chan)))
-        self._n_bound = n
+        self._n_bound, self._k_bound = n, n_chan
         self._bound_host = None
+
+    def bind_depth_image(self, depth, K, *, depth_scale=None, rgb=None, features=None, confidence=None, confidence_threshold=0.0,
+                         min_depth=0.0, max_depth=8.0, step=1):
+        """Upload a depth camera's frame as IMAGES and bind the cloud the device back-projects from them (include/emap_hip.h:
+        emap_bind_depth_image; the reference does this on the host, pointcloud_node.py:205-250).  ``depth``: (H, W) float32 metres, or
+        uint16 units of ``depth_scale`` metres; ``K``: the 3 x 3 intrinsics; ``rgb``: (H, W, 3) uint8; ``features``: (k, H, W) float32;
+        ``confidence``: (H, W) float32.  Every ``step``-th row and column becomes one row of the cloud (NaN where the pixel is not
+        valid), its channels colour-then-features; returns the number of rows."""
+        depth = np.asarray(depth)
+        if depth.dtype == np.uint16:
+            if depth_scale is None:
+                raise ValueError("a uint16 depth image needs depth_scale (metres per unit)")
+            dtype = 1
+        else:
+            depth, dtype = np.asarray(depth, np.float32), 0
+        depth = np.ascontiguousarray(depth)
+        if depth.ndim != 2:
+            raise ValueError("depth must be an (H, W) image")
+        H, W = depth.shape
+        Km = np.asarray(K, np.float64).reshape(3, 3)
+        d = EmapDepthDesc(H, W, dtype, int(step), int(rgb is not None), 0, Km[0, 0], Km[1, 1], Km[0, 2], Km[1, 2],
+                          1.0 if depth_scale is None else depth_scale, min_depth, max_depth, confidence_threshold)
+        ptr = [None, None, None]
+        keep = []
+        for k, (img, dt, shape) in enumerate(((rgb, np.uint8, (H, W, 3)), (features, np.float32, None), (confidence, np.float32, (H, W)))):
+            if img is None:
+                continue
+            img = np.ascontiguousarray(img, dt)
+            if k == 1:
+                if img.ndim == 2:
+                    img = img[None]
+                shape = (img.shape[0], H, W)
+                d.n_features = img.shape[0]
+            if img.shape != shape:
+                raise ValueError("image of shape %r where %r is expected" % (img.shape, shape))
+            keep.append(img)
+            ptr[k] = ct.c_void_p(img.ctypes.data)
+        n = ct.c_int64(0)
+        self._chk(self._lib.emap_bind_depth_image(self._ctx, ct.byref(d), ct.c_void_p(depth.ctypes.data), ptr[0], ptr[1], ptr[2], ct.byref(n)))
+        self._n_bound, self._k_bound = int(n.value), int(d.has_rgb) + int(d.n_features)
+        self._bound_host = None
+        return self._n_bound
+
+    def input_depth_image(self, depth, K, channels: List[str], R, t, position_noise: float, orientation_noise: float, **keywords):
+        """``input_pointcloud`` for a depth camera's frame: back-projected on the device (``bind_depth_image``, same keywords) and fused.
+        ``channels``: the names of the extra channels, colour then features -- what ``input_pointcloud`` receives as ``channels[3:]``."""
+        self.bind_depth_image(depth, K, **keywords)
+        self.update_map_with_kernel(None, list(channels), np.asarray(R, np.float32), np.asarray(t, np.float32).copy(),
+                                    position_noise, orientation_noise, want_stats=False)
+
+    def bound_points(self):
+        """the cloud bound now, read back from the device: ``(xyz (n, 3), chan (n, K))`` float32 (include/emap_hip.h:
+        emap_get_bound_points; waits for the stream)"""
+        n, k = int(getattr(self, "_n_bound", 0)), int(getattr(self, "_k_bound", 0))
+        xyz, chan = np.empty((n, 3), np.float32), np.empty((n, k), np.float32)
+        self._chk(self._lib.emap_get_bound_points(self._ctx, ct.c_void_p(xyz.ctypes.data), ct.c_void_p(chan.ctypes.data) if k else None))
+        return xyz, chan
 
     @staticmethod
     def _rt(R, t):

@@ -116,6 +116,32 @@ int emap_set_points_device(emap_ctx* ctx, const float* dev, int64_t n, int64_t s
  * extra channels (n, n_chan), both row-major float32; channel column c of the caller's (n, 3 + n_chan) numbering is column
  * c - 3 of chan_dev */
 int emap_set_points_device_split(emap_ctx* ctx, const float* xyz_dev, const float* chan_dev, int64_t n, int64_t n_chan);
+/* Depth-image input.  The reference back-projects a depth camera's frame on the HOST and hands the float cloud to input_pointcloud
+ * (sensor_processing/semantic_sensor/.../pointcloud_node.py:205-250 create_pcl_from_image, :261-269 process_image); here the images
+ * are uploaded (2-4 bytes a pixel instead of 12-24 a point) and the cloud is produced on the device, into a buffer the context owns,
+ * and bound like a caller's de-interleaved device cloud.  depth: height x width row-major, float32 metres (depth_dtype 0) or uint16
+ * units of depth_scale metres (depth_dtype 1).  Every step-th row and column is sampled: Hs = ceil(height / step), Ws = ceil(width /
+ * step), n = Hs Ws rows in the reference's nonzero order (row i = (v / step) Ws + u / step), NOT compacted: a pixel that is not
+ * valid -- valid = isfinite(z) && z > min_depth && z < max_depth && (no confidence image || confidence >= confidence_threshold), the
+ * reference's rule with min 0, max 8 -- becomes a row of NaNs (bits 0x7FC00000), which every kernel skips.  A valid pixel:
+ * x = (((float)u - cx) * z) / fx, y = (((float)v - cy) * z) / fy, z, in float32, round to nearest, never contracted.  Channels (written
+ * for every row): the colour first if has_rgb (rgb: height x width x 3 uint8; a float with the BITS r << 16 | g << 8 | b, the wire
+ * format of process_image), then features[k][v][u], k < n_features (planar float32); at most 16 in all.  confidence: height x width
+ * float32 or NULL.  Refused with EMAP_ERR_INVALID before anything is copied or launched, the previous binding untouched: a NULL
+ * required pointer, sides outside 1 .. 8192, step outside 1 .. 64, fx or fy zero or not finite, cx / cy / min_depth / max_depth not
+ * finite, min_depth < 0, max_depth <= min_depth, uint16 depth with a depth_scale that is not finite and > 0, more than 16 channels, an
+ * unknown depth_dtype.  The caller's images are only borrowed (copied before the call returns); nothing waits for the device.
+ * n_points_out (may be NULL): n.  Row-strip contexts: the cloud is bound whole and unbucketed. */
+typedef struct emap_depth_desc {
+  int32_t height, width, depth_dtype, step, has_rgb, n_features;
+  float fx, fy, cx, cy, depth_scale, min_depth, max_depth, confidence_threshold;
+} emap_depth_desc;
+int emap_bind_depth_image(emap_ctx* ctx, const emap_depth_desc* desc, const void* depth, const uint8_t* rgb_or_null, const float* features_or_null,
+                          const float* confidence_or_null, int64_t* n_points_out);
+/* the cloud bound now, whoever bound it (uploaded, a caller's device cloud interleaved or split, a back-projected depth image -- what
+ * pointcloud_node.py:205-250, 261-269 would have published): xyz_host (n, 3), chan_host_or_null (n, n_cols - 3), float32.  Waits for
+ * the stream.  EMAP_ERR_NO_POINTS when nothing is bound. */
+int emap_get_bound_points(emap_ctx* ctx, float* xyz_host, float* chan_host_or_null);
 /* tail of add_points_kernel (custom_kernels.py:260-262): per point cell idx, is_valid, is_inside */
 int emap_point_index(emap_ctx* ctx, const float R[9], const float t[3], int32_t* idx, uint8_t* valid, uint8_t* inside);
 
