@@ -1043,6 +1043,10 @@ struct TravW { float w[3][9][4]; float wo[3][4]; };   // weights of the traversa
 // because it is a readable attribute of the reference class.
 // ---------------------------------------------------------------------------------------------------------
 #define PT_C 64
+#ifndef POST_STAGE_ONE_TRIP
+#define POST_STAGE_ONE_TRIP 1   /* k_post: a thread requests its region rows AND its share of the column walk before it consumes either (A/B knob) */
+#endif
+#define POST_KW 2               /* (row, column) pairs of the walk per thread whose loads are in flight together, next to the rows' */
 #ifndef POST_T32
 #define POST_T32 512   /* threads of a 32-row stencil tile: 8 waves, four output rows per thread, two workgroups per CU */
 #endif
@@ -1369,6 +1373,45 @@ __global__ __launch_bounds__(PT_R >= 32 ? POST_T32 : 512) void k_post(KP P, Trav
     if (interior) {
       constexpr int U = PT_R >= 32 ? 6 : (PT_R >= 16 ? 4 : 2);               // region rows per wave with their loads in flight together
       const unsigned int pc0 = (unsigned int)phys_col(P, c0 + tc);
+      auto put = [&](int r, int cc, const float4& q1) {
+        const float m = q1.w + q1.z;
+        float3 o; o.x = q1.y; o.y = m; o.z = q1.w;
+        *reinterpret_cast<float3*>(reg + (r * rp + cc) * 3) = o;
+        if (m < 0.5f && (unsigned int)(r - d) < (unsigned int)DH && (unsigned int)(cc - d) < (unsigned int)DW) holes[atomicAdd(&n_holes, 1u)] = (unsigned short)((r - d) * DW + (cc - d));
+      };
+#if POST_STAGE_ONE_TRIP
+      // One loop for both: a turn requests the wave's next U rows and the thread's next POST_KW pairs of the walk over the remaining
+      // 6 + 2d columns (a linear walk over (row, column) pairs, full lanes), then consumes them -- the 44 x 76 region of a 32-row tile at
+      // d = 3 is ONE trip to memory (its walk is 528 pairs for 512 threads: the rows, the pair and sixteen lanes' second pair used to be
+      // three trips behind each other); large radii take max(row turns, walk turns) trips instead of their sum.  Uniform trip count.
+      // No branch stands around a load: a slot past the last row / pair reads the last one again and is dropped.  Behind a skipped load the
+      // compiler cannot count what is outstanding, and it re-uses the destination of a load that MAY be pending for the next address:
+      // either way it waits for everything (vmcnt(0)) between the loads -- the six rows of a wave were three to five trips, not one.
+      const int wturns = (etotal + PT_THREADS * POST_KW - 1) / (PT_THREADS * POST_KW);
+      int rb = wv, eb0 = threadIdx.x;
+      for (int turn = 0; rb < RH || turn < wturns; ++turn, rb += PT_WAVES * U, eb0 += PT_THREADS * POST_KW) {
+        float4 q[U], qe[POST_KW];
+        int er[POST_KW], ec[POST_KW];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int r = min(rb + u * PT_WAVES, RH - 1);                       // scalar
+          q[u] = cells.cold[(long)(__umul24((unsigned int)rtab[r + 1], (unsigned int)C) + pc0)];
+        }
+#pragma unroll
+        for (int j = 0; j < POST_KW; ++j) {
+          const int eb = min(eb0 + j * PT_THREADS, etotal - 1);
+          er[j] = (int)__umulhi((unsigned int)eb, S.emagic); ec[j] = 64 + eb - er[j] * EC;
+          qe[j] = cells.cold[(long)(__umul24((unsigned int)rtab[er[j] + 1], (unsigned int)C) + (unsigned int)phys_col(P, c0 + ec[j]))];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int r = rb + u * PT_WAVES;
+          if (r < RH) put(r, tc, q[u]);
+        }
+#pragma unroll
+        for (int j = 0; j < POST_KW; ++j) if (eb0 + j * PT_THREADS < etotal) put(er[j], ec[j], qe[j]);
+      }
+#else
       for (int rb = wv; rb < RH; rb += PT_WAVES * U) {
         float4 q[U];
 #pragma unroll
@@ -1379,22 +1422,15 @@ __global__ __launch_bounds__(PT_R >= 32 ? POST_T32 : 512) void k_post(KP P, Trav
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int r = rb + u * PT_WAVES;
-          if (r >= RH) continue;
-          const float m = q[u].w + q[u].z;
-          float3 o; o.x = q[u].y; o.y = m; o.z = q[u].w;
-          *reinterpret_cast<float3*>(reg + (r * rp + tc) * 3) = o;
-          if (m < 0.5f && (unsigned int)(r - d) < (unsigned int)DH && (unsigned int)(tc - d) < (unsigned int)DW) holes[atomicAdd(&n_holes, 1u)] = (unsigned short)((r - d) * DW + (tc - d));
+          if (r < RH) put(r, tc, q[u]);
         }
       }
       // the remaining 6 + 2d columns: a linear walk over (row, column) pairs, full lanes
       for (int eb = threadIdx.x; eb < etotal; eb += PT_THREADS) {
         const int r = (int)__umulhi((unsigned int)eb, S.emagic), cc = 64 + eb - r * EC;
-        const float4 q1 = cells.cold[(long)(__umul24((unsigned int)rtab[r + 1], (unsigned int)C) + (unsigned int)phys_col(P, c0 + cc))];
-        const float m = q1.w + q1.z;
-        float3 o; o.x = q1.y; o.y = m; o.z = q1.w;
-        *reinterpret_cast<float3*>(reg + (r * rp + cc) * 3) = o;
-        if (m < 0.5f && (unsigned int)(r - d) < (unsigned int)DH && (unsigned int)(cc - d) < (unsigned int)DW) holes[atomicAdd(&n_holes, 1u)] = (unsigned short)((r - d) * DW + (cc - d));
+        put(r, cc, cells.cold[(long)(__umul24((unsigned int)rtab[r + 1], (unsigned int)C) + (unsigned int)phys_col(P, c0 + cc))]);
       }
+#endif
     } else {
       // Tiles along the map's edges (or next to rows a strip does not hold): the same walk with the flag bits of the row table (bit 31:
       // no such row, bit 30: border row) and of the column (the same two bits + the flat-index row carry dr of the reference's
@@ -1421,6 +1457,34 @@ __global__ __launch_bounds__(PT_R >= 32 ? POST_T32 : 512) void k_post(KP P, Trav
       col_terms(tc, ldr, lpc, lfl);
       const int* ltab = rtab + 1 + ldr;                              // the lane's view of the row table
       constexpr int U = PT_R >= 32 ? 6 : (PT_R >= 16 ? 4 : 2);
+#if POST_STAGE_ONE_TRIP
+      const int wturns = (etotal + PT_THREADS * POST_KW - 1) / (PT_THREADS * POST_KW);      // (rows and walk in one loop: see the interior path)
+      int rb = wv, eb0 = threadIdx.x;
+      for (int turn = 0; rb < RH || turn < wturns; ++turn, rb += PT_WAVES * U, eb0 += PT_THREADS * POST_KW) {
+        float4 q[U], qe[POST_KW]; int tq[U], te[POST_KW], er[POST_KW], ec[POST_KW];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int r = min(rb + u * PT_WAVES, RH - 1);              // scalar
+          const int T = ltab[r]; tq[u] = T | lfl; q[u] = cells.cold[(long)(__umul24((unsigned int)T & 0xffffffu, (unsigned int)C) + (unsigned int)lpc)];
+        }
+#pragma unroll
+        for (int j = 0; j < POST_KW; ++j) {
+          const int eb = min(eb0 + j * PT_THREADS, etotal - 1);
+          er[j] = (int)__umulhi((unsigned int)eb, S.emagic); ec[j] = 64 + eb - er[j] * EC;
+          int dr, pc, fl;
+          col_terms(ec[j], dr, pc, fl);
+          const int T = rtab[er[j] + 1 + dr];
+          te[j] = T | fl; qe[j] = cells.cold[(long)(__umul24((unsigned int)T & 0xffffffu, (unsigned int)C) + (unsigned int)pc)];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int r = rb + u * PT_WAVES;
+          if (r < RH) put(r, tc, tq[u], q[u]);
+        }
+#pragma unroll
+        for (int j = 0; j < POST_KW; ++j) if (eb0 + j * PT_THREADS < etotal) put(er[j], ec[j], te[j], qe[j]);
+      }
+#else
       for (int rb = wv; rb < RH; rb += PT_WAVES * U) {
         float4 q[U]; int tq[U];
 #pragma unroll
@@ -1441,6 +1505,7 @@ __global__ __launch_bounds__(PT_R >= 32 ? POST_T32 : 512) void k_post(KP P, Trav
         const int T = rtab[r + 1 + dr];
         put(r, cc, T | fl, cells.cold[(long)(__umul24((unsigned int)T & 0xffffffu, (unsigned int)C) + (unsigned int)pc)]);
       }
+#endif
     }
   }
   // The holes of the DW x DH region were COMPACTED into an LDS list by the staging loop and are searched one hole per lane -- a
