@@ -73,17 +73,11 @@ struct __attribute__((aligned(16))) BinStg { unsigned int key; float z, v; unsig
 // the workgroups of one residue class mod 8 to CONSECUTIVE chunks: neighbouring runs of a tile then meet in one L2.  A bijection on
 // [0, B) for every B (B = 8 q + r: class x holds q + (x < r) workgroups and starts at chunk x q + min(x, r); B < 8 is the identity);
 // rows stay indexed by chunk, so the scan, the record order and every byte of the sorted records are what they were -- only who
-// writes them changes, and nothing depends on the placement for correctness.  -DBIN_XCD_ORDER=0: the identity (A/B builds).
-#ifndef BIN_XCD_ORDER
-#define BIN_XCD_ORDER 1
-#endif
+// writes them changes, and nothing depends on the placement for correctness.  The identity order (chunk = b) was the other side of the
+// measurement and lost: k_bin_scatter 12.2 -> 11.0 us, 30.0 -> 27.2 MB written at 1 M points.
 __device__ __forceinline__ unsigned int bin_chunk_of_block() {
-#if BIN_XCD_ORDER
   const unsigned int b = blockIdx.x, B = gridDim.x, q = B >> 3, r = B & 7u, x = b & 7u, j = b >> 3;
   return x * q + min(x, r) + j;
-#else
-  return blockIdx.x;
-#endif
 }
 
 // STRIP: the context owns a row strip and no visibility pass follows (see the header).  The staged records of block b are
@@ -408,9 +402,6 @@ __device__ __forceinline__ bool drift_inlier(const KP& P, const float4 m, float 
 #ifndef SPLIT_U_FUSE
 #define SPLIT_U_FUSE 1
 #endif
-#ifndef TILE_PREFETCH
-#define TILE_PREFETCH 1   /* tile kernels: first records requested before the staging barrier (A/B knob) */
-#endif
 // The hot halves (h, v, valid, trav) of one 16 x 64 tile -> LDS, one wave per tile row.  Without pending map moves this is a pure
 // copy of 1 KB per row: gfx950's LDS-DMA (no VGPR round trip, no ds_write); cells beyond the map / strip read as zero.  With pending
 // moves the cells pass through cell_now() in registers.  The caller's next __syncthreads() publishes the tile.
@@ -447,20 +438,17 @@ __device__ __forceinline__ void tile_count_body(const KP& P, const BinGeo& G, co
   // trips of load -> LDS, each a full memory round trip when only one load per thread is outstanding
   constexpr int U = SPLIT ? SPLIT_U : 1;
   // (round 5) the first batch of records is requested BEFORE the tile's cells are staged: the two round trips overlap instead of
-  // following each other behind the barrier -- the tile kernels are chains of dependent trips, 128 rounds of them at 8192^2
+  // following each other behind the barrier -- the tile kernels are chains of dependent trips, 128 rounds of them at 8192^2.  Against a
+  // build without the prefetch (tried, slower, not kept): k_tile_count 358 -> 322 us, k_tile_fuse 837 -> 823 us at 8192^2, 16.25 -> 15.85 us at 1024^2
   BinRec rr[U];
-#if TILE_PREFETCH
 #pragma unroll
   for (int u = 0; u < U; ++u) { const unsigned int k = r0 + u * TF_BLOCK + threadIdx.x; if (k < r1) rr[u] = recs[(size_t)k * RS]; }
-#endif
   stage_hot_tile(P, cells, s_cell, row_base, tx);
   if (split) { s_pts[threadIdx.x] = 0u; s_inl[threadIdx.x] = 0u; }
   __syncthreads();
   const unsigned int sel = (unsigned int)sb;
   for (unsigned int kb = r0; kb < r1; kb += TF_BLOCK * U) {     // uniform trip count: the wave reductions need all lanes
-#if TILE_PREFETCH
-    if (kb != r0)
-#endif
+    if (kb != r0)                                                 // (the first batch is already in flight)
 #pragma unroll
     for (int u = 0; u < U; ++u) { const unsigned int k = kb + u * TF_BLOCK + threadIdx.x; if (k < r1) rr[u] = recs[(size_t)k * RS]; }
     long long e_fix = 0; unsigned long long cnt = 0;
@@ -552,7 +540,7 @@ __device__ __forceinline__ void tile_fuse_body(const KP& P, const BinGeo& G, con
     const unsigned int k_first = r0 + threadIdx.x;
     BinRec first; first.lc_inl = 0u; first.z = 0.f; first.v = 0.f; first.i = 0u;
     float4 first_ch = make_float4(0.f, 0.f, 0.f, 0.f);      // (SEM: the record's channels, for the third pass)
-    const bool have_first = TILE_PREFETCH && !SPLIT && k_first < r1;
+    const bool have_first = !SPLIT && k_first < r1;
     if (have_first) { first = recs[(size_t)k_first * RS]; if (SEM) first_ch = reinterpret_cast<const float4*>(recs)[(size_t)k_first * RS + 1]; }
     stage_hot_tile(P, cells, s_cell, row_base, tx);
     for (int k = threadIdx.x; k < NC; k += TF_BLOCK) { s_pts[k] = 0u; s_inl[k] = 0u; s_cnt[k] = 0u; s_out[k] = 0u; s_h[k] = 0ull; s_v[k] = 0ull; s_latest[k] = 0ull; }
@@ -611,12 +599,9 @@ __device__ __forceinline__ void tile_fuse_body(const KP& P, const BinGeo& G, con
       }
       // Order: the atomics above are performed at the memory side (device scope); s_waitcnt 0 waits for their acknowledgements, the
       // barrier collects the workgroup, then the ticket -- the hand-off k_bin_scan uses (last_block_ticket).  A release FENCE here
-      // writes back the XCD's whole L2 for every part: 1.6 us per part, measured (fuse 76 -> 163 us going from 19 to 73 parts).
-#ifdef SPLIT_FENCE
-      __threadfence();
-#else
+      // writes back the XCD's whole L2 for every part: 1.6 us per part, measured (fuse 76 -> 163 us going from 19 to 73 parts) -- the
+      // __threadfence() here and a second one behind the ticket were that build; it lost and is not kept.
       __builtin_amdgcn_s_waitcnt(0);
-#endif
       __syncthreads();
       if (threadIdx.x == 0) {
         const unsigned int arrived = __hip_atomic_fetch_add(&SV.tick[w.slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -625,9 +610,6 @@ __device__ __forceinline__ void tile_fuse_body(const KP& P, const BinGeo& G, con
       }
       __syncthreads();
       if (!s_final) return;                                  // (uniform)
-#ifdef SPLIT_FENCE
-      __threadfence();
-#endif
       s_h[threadIdx.x] = __hip_atomic_load(&SV.h[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       s_v[threadIdx.x] = __hip_atomic_load(&SV.v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       s_latest[threadIdx.x] = __hip_atomic_load(&SV.latest[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

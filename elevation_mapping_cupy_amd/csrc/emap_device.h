@@ -590,18 +590,12 @@ __device__ __forceinline__ void lds_dma16_at(const void* gsrc_lane, unsigned int
 // the largest maps pass 4 GB.  The compiler does not count the store -- nothing waits for it, and as memory operations return in order
 // it can only make the compiler's later waits conservative -- and pads nothing behind it: the s_nop keeps the next instruction off
 // the data registers.  Meant for launches whose stores all fit in L2: a launch of many rounds has its lines evicted under its own body
-// and only the last 32 MB are left at its end, so there is little to gain (launch_bin_fuse decides).  -DEMAP_WT_STORES=0: plain stores (A/B builds).
-#ifndef EMAP_WT_STORES
-#define EMAP_WT_STORES 1
-#endif
+// and only the last 32 MB are left at its end, so there is little to gain (launch_bin_fuse decides).
+// Against a build with plain stores here (tried, lost, not kept): k_tile_fuse 13.0-13.3 -> 11.0-11.1 us at 1024^2.
 __device__ __forceinline__ void st16_wt(float4* p, const float4 v) {
-#if EMAP_WT_STORES
   typedef float em_f4v __attribute__((ext_vector_type(4)));
   const em_f4v x = {v.x, v.y, v.z, v.w};
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(x) : "memory");
-#else
-  *p = v;
-#endif
 }
 
 // ---- host: raising a kernel's dynamic LDS limit beyond the default 64 KB ---------------------------------------------------

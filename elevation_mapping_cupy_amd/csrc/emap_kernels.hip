@@ -154,14 +154,12 @@ __global__ __launch_bounds__(64) void k_commit(KP P, Cells cells, const AccF* __
 // ~44 ns/Mop whatever the address pattern, so test first with a plain (possibly stale => conservative) load: the key
 // only grows, a stale smaller value can only cause a redundant atomic, never a missed one.
 __device__ __forceinline__ unsigned int ray_key_load(const unsigned int* key_ptr) {
-#ifdef RAY_KEY_NT_LOAD
-  return __builtin_nontemporal_load(key_ptr);
-#else
   // a DEVICE-COHERENT load (sc1): the atomics execute at the memory side, so a plain / nt load keeps seeing the value its own XCD's L2
   // cached before the other seven XCDs raised the key -- and every visit below that stale value issues another atomic (the first
-  // frame after clear(), where every visit of the 39 % unknown cells comes here: measured in round 4)
+  // frame after clear(), where every visit of the 39 % unknown cells comes here: measured in round 4).  The non-temporal load
+  // (__builtin_nontemporal_load) was the other side of that measurement and lost -- first frame after clear() 1.52-1.63 ms against
+  // 1.02 ms at 1024^2, 6.46 against 4.17 ms at 4096^2, steady state equal -- and is no longer kept as a build.
   return __hip_atomic_load(key_ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 __device__ __forceinline__ void ray_upper_min(unsigned int* key_ptr, float nz) {
   const unsigned int key = ~float_ord(nz);
@@ -247,9 +245,7 @@ __global__ __launch_bounds__(BLOCK, LMAP ? 4 : RAY_OCC) void k_rays(KP P, Pose T
   if (order) {
     const unsigned int nbs = (unsigned int)(((long)*n_sorted * LPR + BLOCK - 1) / BLOCK);
     if (blockIdx.x >= nbs) return;
-#ifndef RAY_TILE_ORDER
-    chunk = (blockIdx.x & 1u) ? nbs - 1u - (blockIdx.x >> 1) : (blockIdx.x >> 1);
-#endif
+    chunk = (blockIdx.x & 1u) ? nbs - 1u - (blockIdx.x >> 1) : (blockIdx.x >> 1);      // (plain tile order, chunk = blockIdx.x, is the side that lost those measurements: 221 and 310 us)
   }
   const unsigned int* __restrict__ inert = reinterpret_cast<const unsigned int*>(inert64);   // 32-bit words: cheaper shifts
   const unsigned int wpr32 = (unsigned int)((P.pitch + 63) / 64) * 2u;                       // 32-bit words per bitmap row (pitch = C; a ray window: its width)
@@ -1043,9 +1039,6 @@ struct TravW { float w[3][9][4]; float wo[3][4]; };   // weights of the traversa
 // because it is a readable attribute of the reference class.
 // ---------------------------------------------------------------------------------------------------------
 #define PT_C 64
-#ifndef POST_STAGE_ONE_TRIP
-#define POST_STAGE_ONE_TRIP 1   /* k_post: a thread requests its region rows AND its share of the column walk before it consumes either (A/B knob) */
-#endif
 #define POST_KW 2               /* (row, column) pairs of the walk per thread whose loads are in flight together, next to the rows' */
 #ifndef POST_T32
 #define POST_T32 512   /* threads of a 32-row stencil tile: 8 waves, four output rows per thread, two workgroups per CU */
@@ -1164,6 +1157,46 @@ __device__ __forceinline__ void post_source_masks(unsigned int* __restrict__ sm,
     if (tc == 0) { sm[5 * r] = (unsigned int)lo; sm[5 * r + 1] = (unsigned int)(lo >> 32); sm[5 * r + 2] = (unsigned int)hi; sm[5 * r + 3] = (unsigned int)(hi >> 32); sm[5 * r + 4] = 0u; }
   }
   __syncthreads();
+}
+// k_post's staging loop, once for interior and edge tiles.  The first 64 columns of the RH x (64 + EC) region go row-wise (one wave per
+// region row, lane = column), the remaining EC = 6 + 2d columns as a linear walk over (row, column) pairs, full lanes.  A turn requests
+// the wave's next U rows AND the thread's next POST_KW pairs, then consumes them -- the 44 x 76 region of a 32-row tile at d = 3 is ONE
+// trip to memory (its walk is 528 pairs for 512 threads: the rows, the pair and sixteen lanes' second pair used to be three trips behind
+// each other); large radii take max(row turns, walk turns) trips instead of their sum.  Uniform trip count.
+// No branch stands around a load: a slot past the last row / pair reads the last one again and is dropped.  Behind a skipped load the
+// compiler cannot count what is outstanding, and it re-uses the destination of a load that MAY be pending for the next address:
+// either way it waits for everything (vmcnt(0)) between the loads -- the six rows of a wave were three to five trips, not one.  (The
+// loops that did that -- rows with `if (r < RH)` around each load, then the walk -- were kept for one comparison and lost it:
+// k_post<32, 0> 18.6-18.7 -> 17.7-17.8 us, frame 68.6 -> 67.6 us)
+// load_row(r) / load_pair(r, cc): the lane's cell of region row r / the cell (r, cc), with a tag that travels into put(r, cc, cell)
+// (edge tiles: the flag word; interior tiles pass a constant, which costs nothing).  wv, tc: the caller's wave (scalar) and lane;
+// emagic = ceil(2^32 / EC).
+struct PostLd { float4 q; int tag; };
+template <int U, int PT_THREADS, class RowFn, class PairFn, class PutFn>
+__device__ __forceinline__ void post_stage_trips(int wv, int tc, int RH, int EC, unsigned int emagic, RowFn load_row, PairFn load_pair, PutFn put) {
+  constexpr int PT_WAVES = PT_THREADS / 64;
+  const int etotal = RH * EC;
+  const int wturns = (etotal + PT_THREADS * POST_KW - 1) / (PT_THREADS * POST_KW);
+  int rb = wv, eb0 = threadIdx.x;
+  for (int turn = 0; rb < RH || turn < wturns; ++turn, rb += PT_WAVES * U, eb0 += PT_THREADS * POST_KW) {
+    PostLd q[U], qe[POST_KW];
+    int er[POST_KW], ec[POST_KW];
+#pragma unroll
+    for (int u = 0; u < U; ++u) q[u] = load_row(min(rb + u * PT_WAVES, RH - 1));      // (scalar row)
+#pragma unroll
+    for (int j = 0; j < POST_KW; ++j) {
+      const int eb = min(eb0 + j * PT_THREADS, etotal - 1);
+      er[j] = (int)__umulhi((unsigned int)eb, emagic); ec[j] = 64 + eb - er[j] * EC;
+      qe[j] = load_pair(er[j], ec[j]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int r = rb + u * PT_WAVES;
+      if (r < RH) put(r, tc, q[u]);
+    }
+#pragma unroll
+    for (int j = 0; j < POST_KW; ++j) if (eb0 + j * PT_THREADS < etotal) put(er[j], ec[j], qe[j]);
+  }
 }
 // first source of the hole at region (R0, C0) in the reference's scan order: true + its offsets, false: none within reach
 __device__ __forceinline__ bool post_first_source(const unsigned int* __restrict__ sm, int R0, int C0, int d, int& dy_out, int& dx_out) {
@@ -1343,15 +1376,13 @@ __global__ __launch_bounds__(PT_R >= 32 ? POST_T32 : 512) void k_post(KP P, Trav
   const int C = P.C;
   const int tile_r = seg_b + ty * PT_R, tile_c = blockIdx.x * PT_C;      // logical row / column of the tile origin
   const int tc = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // wave index in an SGPR
-  // staging.  The first 64 columns of the region go row-wise: one wave per region row, lane = column, up to six rows' loads in flight
-  // per wave (a 44 x 76 region -- 32-row tile, d = 3 -- is one memory round trip); the remaining 6 + 2d columns go as a linear walk over
-  // (row, column) pairs so that their lanes are full too.  Everything that depends on the row (circular origin, strip ownership,
-  // border) is computed ONCE per tile into a small LDS table.  Two forms of the walk (round 4): INTERIOR tiles need nothing else;
+  // staging (post_stage_trips: rows and column walk, up to six rows' and two pairs' loads in flight per thread).  Everything that
+  // depends on the row (circular origin, strip ownership, border) is computed ONCE per tile into a small LDS table.  Two forms of the walk (round 4): INTERIOR tiles need nothing else;
   // tiles along the map's edges carry the row table's and the column's flag bits (bit 31: no such cell, bit 30: border cell) and the
   // reference's flat-index row wrap (:403-407: column -1 of row r is column C - 1 of row r - 1).
   {
     const int r0 = tile_r - 3 - d, c0 = tile_c - 3 - d, EC = RW - 64;
-    const int etotal = RH * EC;
+    constexpr int U = PT_R >= 32 ? 6 : (PT_R >= 16 ? 4 : 2);                 // region rows per wave with their loads in flight together (post_stage_trips)
     // row table: region row j - 1 (one extra row on both sides for the flat-index carry) -> local row of the arrays (bits 0..23;
     // 0 with bit 31 set: not in the map / strip), bit 30: a border row (never a dilation source)
     for (int j = threadIdx.x; j < RH + 2; j += PT_THREADS) {
@@ -1370,67 +1401,19 @@ __global__ __launch_bounds__(PT_R >= 32 ? POST_T32 : 512) void k_post(KP P, Trav
     // the general path, which was 40 % of this kernel's instructions (round 4; the kernel is issue bound at every map size:
     // tools/exp_post_pitch.py).  The LDS contents are the same bit for bit.
     const bool interior = s_special == 0u && c0 >= 1 && c0 + RW - 1 <= C - 2;      // (uniform)
+    auto cold_at = [&](int T, unsigned int pc) { return cells.cold[(long)(__umul24((unsigned int)T & 0xffffffu, (unsigned int)C) + pc)]; };      // row term (without its flag bits) x pitch + physical column
     if (interior) {
-      constexpr int U = PT_R >= 32 ? 6 : (PT_R >= 16 ? 4 : 2);               // region rows per wave with their loads in flight together
       const unsigned int pc0 = (unsigned int)phys_col(P, c0 + tc);
-      auto put = [&](int r, int cc, const float4& q1) {
-        const float m = q1.w + q1.z;
-        float3 o; o.x = q1.y; o.y = m; o.z = q1.w;
-        *reinterpret_cast<float3*>(reg + (r * rp + cc) * 3) = o;
-        if (m < 0.5f && (unsigned int)(r - d) < (unsigned int)DH && (unsigned int)(cc - d) < (unsigned int)DW) holes[atomicAdd(&n_holes, 1u)] = (unsigned short)((r - d) * DW + (cc - d));
-      };
-#if POST_STAGE_ONE_TRIP
-      // One loop for both: a turn requests the wave's next U rows and the thread's next POST_KW pairs of the walk over the remaining
-      // 6 + 2d columns (a linear walk over (row, column) pairs, full lanes), then consumes them -- the 44 x 76 region of a 32-row tile at
-      // d = 3 is ONE trip to memory (its walk is 528 pairs for 512 threads: the rows, the pair and sixteen lanes' second pair used to be
-      // three trips behind each other); large radii take max(row turns, walk turns) trips instead of their sum.  Uniform trip count.
-      // No branch stands around a load: a slot past the last row / pair reads the last one again and is dropped.  Behind a skipped load the
-      // compiler cannot count what is outstanding, and it re-uses the destination of a load that MAY be pending for the next address:
-      // either way it waits for everything (vmcnt(0)) between the loads -- the six rows of a wave were three to five trips, not one.
-      const int wturns = (etotal + PT_THREADS * POST_KW - 1) / (PT_THREADS * POST_KW);
-      int rb = wv, eb0 = threadIdx.x;
-      for (int turn = 0; rb < RH || turn < wturns; ++turn, rb += PT_WAVES * U, eb0 += PT_THREADS * POST_KW) {
-        float4 q[U], qe[POST_KW];
-        int er[POST_KW], ec[POST_KW];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int r = min(rb + u * PT_WAVES, RH - 1);                       // scalar
-          q[u] = cells.cold[(long)(__umul24((unsigned int)rtab[r + 1], (unsigned int)C) + pc0)];
-        }
-#pragma unroll
-        for (int j = 0; j < POST_KW; ++j) {
-          const int eb = min(eb0 + j * PT_THREADS, etotal - 1);
-          er[j] = (int)__umulhi((unsigned int)eb, S.emagic); ec[j] = 64 + eb - er[j] * EC;
-          qe[j] = cells.cold[(long)(__umul24((unsigned int)rtab[er[j] + 1], (unsigned int)C) + (unsigned int)phys_col(P, c0 + ec[j]))];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int r = rb + u * PT_WAVES;
-          if (r < RH) put(r, tc, q[u]);
-        }
-#pragma unroll
-        for (int j = 0; j < POST_KW; ++j) if (eb0 + j * PT_THREADS < etotal) put(er[j], ec[j], qe[j]);
-      }
-#else
-      for (int rb = wv; rb < RH; rb += PT_WAVES * U) {
-        float4 q[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int r = rb + u * PT_WAVES;                                    // scalar
-          if (r < RH) q[u] = cells.cold[(long)(__umul24((unsigned int)rtab[r + 1], (unsigned int)C) + pc0)];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int r = rb + u * PT_WAVES;
-          if (r < RH) put(r, tc, q[u]);
-        }
-      }
-      // the remaining 6 + 2d columns: a linear walk over (row, column) pairs, full lanes
-      for (int eb = threadIdx.x; eb < etotal; eb += PT_THREADS) {
-        const int r = (int)__umulhi((unsigned int)eb, S.emagic), cc = 64 + eb - r * EC;
-        put(r, cc, cells.cold[(long)(__umul24((unsigned int)rtab[r + 1], (unsigned int)C) + (unsigned int)phys_col(P, c0 + cc))]);
-      }
-#endif
+      post_stage_trips<U, PT_THREADS>(wv, tc, RH, EC, S.emagic,
+        [&](int r) { return PostLd{cold_at(rtab[r + 1], pc0), 0}; },
+        [&](int r, int cc) { return PostLd{cold_at(rtab[r + 1], (unsigned int)phys_col(P, c0 + cc)), 0}; },
+        [&](int r, int cc, const PostLd& l) {
+          const float4& q1 = l.q;
+          const float m = q1.w + q1.z;
+          float3 o; o.x = q1.y; o.y = m; o.z = q1.w;
+          *reinterpret_cast<float3*>(reg + (r * rp + cc) * 3) = o;
+          if (m < 0.5f && (unsigned int)(r - d) < (unsigned int)DH && (unsigned int)(cc - d) < (unsigned int)DW) holes[atomicAdd(&n_holes, 1u)] = (unsigned short)((r - d) * DW + (cc - d));
+        });
     } else {
       // Tiles along the map's edges (or next to rows a strip does not hold): the same walk with the flag bits of the row table (bit 31:
       // no such row, bit 30: border row) and of the column (the same two bits + the flat-index row carry dr of the reference's
@@ -1442,70 +1425,29 @@ __global__ __launch_bounds__(PT_R >= 32 ? POST_T32 : 512) void k_post(KP P, Trav
         flags = ((cl >= 1 && cl <= C - 2) ? 0 : 0x40000000) | (cl < C ? 0 : (int)0x80000000);      // (a region wider than the map: columns past the wrap are unused)
         pc = cl < C ? phys_col(P, cl) : 0;
       };
-      auto put = [&](int r, int cc, int tqv, const float4& q1) {
-        const bool ok = tqv >= 0, inside = (tqv & 0x40000000) == 0;
-        const float m = q1.w + q1.z;
-        float3 o;
-        o.x = ok ? q1.y : 0.f;
-        o.y = ok ? (inside ? m : -m - 1.f) : -1.f;                  // mask >= 0; stored as -(mask) - 1 when the cell is not is_inside: never a source
-        o.z = ok ? q1.w : 0.f;
-        *reinterpret_cast<float3*>(reg + (r * rp + cc) * 3) = o;
-        // a hole of the region whose dilated value is needed (cells outside the map are never sources and never outputs: not listed)
-        if (ok && m < 0.5f && (unsigned int)(r - d) < (unsigned int)DH && (unsigned int)(cc - d) < (unsigned int)DW) holes[atomicAdd(&n_holes, 1u)] = (unsigned short)((r - d) * DW + (cc - d));
-      };
       int ldr, lpc, lfl;
       col_terms(tc, ldr, lpc, lfl);
       const int* ltab = rtab + 1 + ldr;                              // the lane's view of the row table
-      constexpr int U = PT_R >= 32 ? 6 : (PT_R >= 16 ? 4 : 2);
-#if POST_STAGE_ONE_TRIP
-      const int wturns = (etotal + PT_THREADS * POST_KW - 1) / (PT_THREADS * POST_KW);      // (rows and walk in one loop: see the interior path)
-      int rb = wv, eb0 = threadIdx.x;
-      for (int turn = 0; rb < RH || turn < wturns; ++turn, rb += PT_WAVES * U, eb0 += PT_THREADS * POST_KW) {
-        float4 q[U], qe[POST_KW]; int tq[U], te[POST_KW], er[POST_KW], ec[POST_KW];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int r = min(rb + u * PT_WAVES, RH - 1);              // scalar
-          const int T = ltab[r]; tq[u] = T | lfl; q[u] = cells.cold[(long)(__umul24((unsigned int)T & 0xffffffu, (unsigned int)C) + (unsigned int)lpc)];
-        }
-#pragma unroll
-        for (int j = 0; j < POST_KW; ++j) {
-          const int eb = min(eb0 + j * PT_THREADS, etotal - 1);
-          er[j] = (int)__umulhi((unsigned int)eb, S.emagic); ec[j] = 64 + eb - er[j] * EC;
+      post_stage_trips<U, PT_THREADS>(wv, tc, RH, EC, S.emagic,
+        [&](int r) { const int T = ltab[r]; return PostLd{cold_at(T, (unsigned int)lpc), T | lfl}; },
+        [&](int r, int cc) {
           int dr, pc, fl;
-          col_terms(ec[j], dr, pc, fl);
-          const int T = rtab[er[j] + 1 + dr];
-          te[j] = T | fl; qe[j] = cells.cold[(long)(__umul24((unsigned int)T & 0xffffffu, (unsigned int)C) + (unsigned int)pc)];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int r = rb + u * PT_WAVES;
-          if (r < RH) put(r, tc, tq[u], q[u]);
-        }
-#pragma unroll
-        for (int j = 0; j < POST_KW; ++j) if (eb0 + j * PT_THREADS < etotal) put(er[j], ec[j], te[j], qe[j]);
-      }
-#else
-      for (int rb = wv; rb < RH; rb += PT_WAVES * U) {
-        float4 q[U]; int tq[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int r = rb + u * PT_WAVES;                            // scalar
-          if (r < RH) { const int T = ltab[r]; tq[u] = T | lfl; q[u] = cells.cold[(long)(__umul24((unsigned int)T & 0xffffffu, (unsigned int)C) + (unsigned int)lpc)]; }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int r = rb + u * PT_WAVES;
-          if (r < RH) put(r, tc, tq[u], q[u]);
-        }
-      }
-      for (int eb = threadIdx.x; eb < etotal; eb += PT_THREADS) {
-        const int r = (int)__umulhi((unsigned int)eb, S.emagic), cc = 64 + eb - r * EC;
-        int dr, pc, fl;
-        col_terms(cc, dr, pc, fl);
-        const int T = rtab[r + 1 + dr];
-        put(r, cc, T | fl, cells.cold[(long)(__umul24((unsigned int)T & 0xffffffu, (unsigned int)C) + (unsigned int)pc)]);
-      }
-#endif
+          col_terms(cc, dr, pc, fl);
+          const int T = rtab[r + 1 + dr];
+          return PostLd{cold_at(T, (unsigned int)pc), T | fl};
+        },
+        [&](int r, int cc, const PostLd& l) {
+          const float4& q1 = l.q;
+          const bool ok = l.tag >= 0, inside = (l.tag & 0x40000000) == 0;
+          const float m = q1.w + q1.z;
+          float3 o;
+          o.x = ok ? q1.y : 0.f;
+          o.y = ok ? (inside ? m : -m - 1.f) : -1.f;                  // mask >= 0; stored as -(mask) - 1 when the cell is not is_inside: never a source
+          o.z = ok ? q1.w : 0.f;
+          *reinterpret_cast<float3*>(reg + (r * rp + cc) * 3) = o;
+          // a hole of the region whose dilated value is needed (cells outside the map are never sources and never outputs: not listed)
+          if (ok && m < 0.5f && (unsigned int)(r - d) < (unsigned int)DH && (unsigned int)(cc - d) < (unsigned int)DW) holes[atomicAdd(&n_holes, 1u)] = (unsigned short)((r - d) * DW + (cc - d));
+        });
     }
   }
   // The holes of the DW x DH region were COMPACTED into an LDS list by the staging loop and are searched one hole per lane -- a

@@ -14,7 +14,11 @@ stencil pass (emap_kernels.hip) on either side of the depth of their load batche
     walk of a tile of R rows at radius d has (R + 6 + 2 d)(6 + 2 d) pairs for 512 threads.  tests/_post_variants.py's radii give 1, 2 and
     3 pairs per thread for R = 4 (d = 1, 10, 13), R = 8 (d = 3, 10, 12) and R = 32 (d = 1, 3, 10) but only 1 and 3 for R = 16
     (d = 3: 336 pairs, d = 10: 1092); POST_CASES adds d = 5 (32 x 16 = 512 pairs: exactly one per thread) and d = 6 (34 x 18 = 612:
-    two for some), run with EMAP_POST_R=16 through tests/_post_variants.py as a child program.
+    two for some), run with EMAP_POST_R=16 through tests/_post_variants.py as a child program.  The ROWS of the same loop go U per wave
+    and turn, 8 waves: 32 per turn for R = 16 (U = 4), where the two radii give 16 + 6 + 2 d = 32 and 34 region rows, and 48 per turn for
+    R = 32 (U = 6), where a second child with EMAP_POST_R=32 gives 48 (exactly one turn) and 50 (rows 48 and 49 in the second turn: one row for
+    each of two waves, every other slot of that turn clamped to the last row and dropped).  There the boundary bands of context B (d + 4 = 9 and 10 rows high)
+    run 16-row tiles by the host's own rule (emap_post_part), as in tests/test_hip_post_variants.py's table.
 
 Inputs are numpy only.  Run as a program it is the stencil child: python tests/_trip_cases.py <out.npz>."""
 import sys
@@ -61,8 +65,12 @@ SCATTER = [dict(key="n%d%s" % (n, "_ch" if ch else ""), N=n, sem=ch, mode="refer
 SCATTER_FRAMES = 2
 
 POST_CASES = [(202, 5), (202, 6)]
-POST_ENV = {"EMAP_POST_R": "16", "EMAP_POST_DMA": "0"}
-POST_KERNEL = "k_post<16"
+# child -> the hooks it runs under, and the kernel of each case's five launches: A dilate, A post, B dilate, B part 1, B part 2
+POST_CHILDREN = {
+    "r16_walk": dict(env={"EMAP_POST_R": "16", "EMAP_POST_DMA": "0"}, kernels=("k_post<16",) * 5),
+    "r32_rows": dict(env={"EMAP_POST_R": "32", "EMAP_POST_DMA": "0"}, kernels=("k_post<32",) * 4 + ("k_post<16",)),
+}
+POST_ROWS_PER_TURN = {16: 8 * 4, 32: 8 * 6}          # waves x U of k_post's staging
 
 
 def layout(name):

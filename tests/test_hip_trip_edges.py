@@ -3,6 +3,8 @@ tiles of exactly 0 ... 4097 records for k_tile_count / k_tile_fuse (1024 threads
 1024 records per further trip; 4097 is the first heavy tile), clouds of 1 ... 6145 points for k_bin_scatter (batches of four points
 per thread, a partial last chunk) with and without carried channel columns, and the two radii at which the column walk of
 k_post<16, .>'s staging has exactly one and just over one pair per thread (it requests two per thread and turn, next to the rows).
+The same two radii give 32 and 34 region rows there against 32 rows per turn, and 48 and 50 against the 48 per turn of k_post<32, .>
+(8 waves x 6 rows), which a second child runs: exactly one row turn, and two rows into a second one whose other slots are clamped.
 
 Every case runs its frames once on a fresh context with the binned scatter forced; all seven planes, the normal planes, the
 traversability input, the semantic layers and the additive mean error of the drift compensation must equal the oracle's."""
@@ -75,15 +77,19 @@ def test_clouds_at_the_edges_of_the_scatter_batches(case, weights):
     _compare(case, weights)
 
 
-# ---- stencil staging: one child (the EMAP_POST_R hook is read once per process), tests/_post_variants.py's program on POST_CASES ----
+# ---- stencil staging: one child per tile height (the EMAP_POST_R hook is read once per process), tests/_post_variants.py's program on POST_CASES ----
 CHILD_TIMEOUT_S = 300
 
 
 @pytest.fixture(scope="module")
 def post_child(tmp_path_factory):
-    run = vc.lazy_children(lambda v: vc.run_child(os.path.abspath(tc.__file__), v, tc.POST_ENV, lambda k: k.startswith("EMAP_POST_"),
-                                                  str(tmp_path_factory.mktemp("trip_post")), CHILD_TIMEOUT_S))
-    return lambda: run("r16_walk")
+    return vc.lazy_children(lambda v: vc.run_child(os.path.abspath(tc.__file__), v, tc.POST_CHILDREN[v]["env"], lambda k: k.startswith("EMAP_POST_"),
+                                                   str(tmp_path_factory.mktemp("trip_post_" + v)), CHILD_TIMEOUT_S))
+
+
+@pytest.fixture(scope="module")
+def oracle_post(weights):
+    return vc.cached_oracle(lambda case: _oracle_post(case[0], case[1], weights))
 
 
 def _oracle_post(C, d, weights):
@@ -95,18 +101,24 @@ def _oracle_post(C, d, weights):
     return [np.array(a, np.float32) for a in (dil, orc.elevation_map, orc.normal_map, orc.traversability_input)]
 
 
-@pytest.mark.parametrize("case", tc.POST_CASES, ids=[pv.case_key(*c) for c in tc.POST_CASES])
-def test_stencil_walks_of_one_and_two_pairs_per_thread(case, post_child, weights):
-    got, trace = post_child()
+def _check_post_child(child, case, post_child, oracle_post):
+    got, trace = post_child(child)
     names = [n for n, _ in kernel_trace_rows(trace) if "k_post" in n]
-    assert names and all(tc.POST_KERNEL + "," in n for n in names[:10]), names[:10]      # both cases: dilate, post, dilate, part 1, part 2
+    want_names = tc.POST_CHILDREN[child]["kernels"] * len(tc.POST_CASES)                  # per case: dilate, post, dilate, part 1, part 2
+    assert len(names) >= len(want_names) and all(k + "," in n for k, n in zip(want_names, names)), names[:len(want_names)]
     key = pv.case_key(*case)
-    eo.set_threads(8)
-    try:
-        want = _oracle_post(case[0], case[1], weights)
-    finally:
-        eo.set_threads(1)
+    want = oracle_post(case)
     for ctx in ("A", "B"):
         what = "%s context %s" % (key, ctx)
         assert np.array_equal(got["%s_%s_dilate" % (key, ctx)].view(np.uint32), want[0].view(np.uint32)), what + ": stage-1 dilation"
         vc.assert_case_planes(got, "%s_%s" % (key, ctx), want[1], want[2], want[3], what)
+
+
+@pytest.mark.parametrize("case", tc.POST_CASES, ids=[pv.case_key(*c) for c in tc.POST_CASES])
+def test_stencil_walks_of_one_and_two_pairs_per_thread(case, post_child, oracle_post):
+    _check_post_child("r16_walk", case, post_child, oracle_post)
+
+
+@pytest.mark.parametrize("case", tc.POST_CASES, ids=[pv.case_key(*c) for c in tc.POST_CASES])
+def test_stencil_rows_of_one_turn_and_two_rows_more_in_the_tallest_tile(case, post_child, oracle_post):
+    _check_post_child("r32_rows", case, post_child, oracle_post)

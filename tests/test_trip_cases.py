@@ -62,3 +62,12 @@ def test_stencil_radii_give_one_and_two_pairs_per_thread():
     pairs = {d: (16 + 6 + 2 * d) * (6 + 2 * d) for _, d in tc.POST_CASES}
     assert pairs == {5: 512, 6: 612}
     assert [-(-n // 512) for n in pairs.values()] == [1, 2]
+
+
+def test_stencil_radii_give_one_row_turn_and_one_row_more():
+    rows = {R: [R + 6 + 2 * d for _, d in tc.POST_CASES] for R in (16, 32)}
+    assert rows == {16: [32, 34], 32: [48, 50]}
+    assert tc.POST_ROWS_PER_TURN == {16: 32, 32: 48}
+    for R in (16, 32):                   # exactly one turn, and one row / two rows into the second
+        assert [divmod(n, tc.POST_ROWS_PER_TURN[R]) for n in rows[R]] == [(1, 0), (1, 2)]
+    assert [k for k, v in tc.POST_CHILDREN.items() if v["kernels"][1] == "k_post<32"] == ["r32_rows"]

@@ -2,7 +2,7 @@
 # Build a VARIANT of libemap_hip.so into tools/ab/<name>.so: one translation unit recompiled with extra -D flags, the other objects
 # taken from the in-tree build (csrc/_obj, built first if stale).  For same-box A/B runs with EMAP_HIP_LIB (tools/ab.sh):
 #   tools/mk_variant.sh c8 emap_binned.hip -DSPLIT_CAP=8192u
-#   tools/mk_variant.sh tileorder emap_kernels.hip -DRAY_TILE_ORDER
+#   tools/mk_variant.sh occ4 emap_kernels.hip -DRAY_OCC=4
 # Several variants can be built in parallel (each ~40-60 s): run the script in the background and `wait`.
 set -e
 name=$1; unit=$2; shift 2
