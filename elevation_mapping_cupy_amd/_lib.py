@@ -53,6 +53,12 @@ class EmapDepthDesc(ct.Structure):
                 [(n, ct.c_float) for n in ("fx", "fy", "cx", "cy", "depth_scale", "min_depth", "max_depth", "confidence_threshold")])
 
 
+class EmapCloudMsgDesc(ct.Structure):
+    """struct emap_cloud_msg_desc (include/emap_hip.h: emap_bind_cloud_message)."""
+    _fields_ = ([(n, ct.c_int32) for n in ("height", "width", "point_step", "row_step", "is_bigendian", "n_cols")] +
+                [("offset", ct.c_int32 * 19), ("conv", ct.c_int32 * 19)])
+
+
 MODE = {"reference_fp16": 0, "fp32": 1}
 PLANES = {"elevation": 0, "variance": 1, "is_valid": 2, "traversability": 3, "time": 4, "upper_bound": 5,
           "is_upper_bound": 6, "normal_x": 7, "normal_y": 8, "normal_z": 9, "traversability_input": 10}
@@ -61,7 +67,7 @@ STAGES = ["hist", "scan", "scatter", "gate", "fuse", "commit", "rays", "average"
 # every symbol include/emap_hip.h declares (checked by tests/test_abi.py without a GPU)
 SYMBOLS = [
     "emap_abi_version", "emap_create", "emap_destroy", "emap_set_params", "emap_last_error", "emap_sync", "emap_clear",
-    "emap_upload_points", "emap_upload_points_strip", "emap_strip_point_mask", "emap_declare_points_bucketed", "emap_set_points_device", "emap_set_points_device_split", "emap_bind_depth_image", "emap_get_bound_points", "emap_point_index", "emap_update", "emap_count",
+    "emap_upload_points", "emap_upload_points_strip", "emap_strip_point_mask", "emap_declare_points_bucketed", "emap_set_points_device", "emap_set_points_device_split", "emap_bind_depth_image", "emap_bind_cloud_message", "emap_get_bound_points", "emap_point_index", "emap_update", "emap_count",
     "emap_set_drift_inputs", "emap_drift_sums_to_device", "emap_set_drift_inputs_device",
     "emap_local_drift_sums", "emap_set_scatter_mode", "emap_fuse", "emap_fuse_average", "emap_commit", "emap_rays", "emap_average", "emap_overlap_clear",
     "emap_dilate", "emap_traversability_normals", "emap_post", "emap_post_part", "emap_update_variance", "emap_update_time", "emap_get_stats",
@@ -111,6 +117,8 @@ def load():
     if hasattr(lib, "emap_bind_depth_image"):
         lib.emap_bind_depth_image.argtypes = [ct.c_void_p, ct.POINTER(EmapDepthDesc), ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.POINTER(ct.c_int64)]
         lib.emap_get_bound_points.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_void_p]
+    if hasattr(lib, "emap_bind_cloud_message"):
+        lib.emap_bind_cloud_message.argtypes = [ct.c_void_p, ct.POINTER(EmapCloudMsgDesc), ct.c_void_p, ct.POINTER(ct.c_int64)]
     got = int(lib.emap_abi_version())
     if got != ABI_VERSION and not os.environ.get("EMAP_HIP_LIB"):
         raise EmapError("%s speaks ABI version %d, this binding expects %d (include/emap_hip.h: EMAP_ABI_VERSION) -- rebuild with "

@@ -255,6 +255,17 @@ static int validate(const emap_params* p, const emap_strip* s, std::string* why)
   return 1;
 }
 
+// the copy stream, its events and the host worker threads of the upload paths, made at the first upload (emap_api_cloudmsg.hip: the workers)
+int emap_host::upload_setup(emap_ctx* ctx) {
+  if (ctx->copy_stream) return EMAP_OK;
+  CK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+  for (int k = 0; k < 2; ++k) { CK(hipEventCreateWithFlags(&ctx->ev_copied[k], hipEventDisableTiming)); CK(hipEventCreateWithFlags(&ctx->ev_used[k], hipEventDisableTiming)); }
+  int nt = (int)std::thread::hardware_concurrency() / 2; if (nt > 8) nt = 8; if (nt < 1) nt = 1;
+  if (const char* e = getenv("EMAP_UPLOAD_THREADS")) { int v = atoi(e); if (v >= 1 && v <= 64) nt = v; }
+  ctx->workers = new Workers(nt);
+  return EMAP_OK;
+}
+
 extern "C" {
 
 int emap_abi_version(void) { return EMAP_ABI_VERSION; }
@@ -406,13 +417,7 @@ struct StripKeep {
 static int upload_impl(emap_ctx* ctx, const void* host, int64_t n, int64_t stride, int dtype, const StripKeep* keep, int64_t* n_kept) { SF_CHECK();
   CK(hipSetDevice(ctx->device));
   const long tot = (long)n * stride + (stride > 3 ? 64 : 0);      // (+ the padding in front of the channel matrix)
-  if (!ctx->copy_stream) {
-    CK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    for (int k = 0; k < 2; ++k) { CK(hipEventCreateWithFlags(&ctx->ev_copied[k], hipEventDisableTiming)); CK(hipEventCreateWithFlags(&ctx->ev_used[k], hipEventDisableTiming)); }
-    int nt = (int)std::thread::hardware_concurrency() / 2; if (nt > 8) nt = 8; if (nt < 1) nt = 1;
-    if (const char* e = getenv("EMAP_UPLOAD_THREADS")) { int v = atoi(e); if (v >= 1 && v <= 64) nt = v; }
-    ctx->workers = new Workers(nt);
-  }
+  { const int rc = upload_setup(ctx); if (rc) return rc; }
   // everything enqueued so far may read the buffer of the previous upload: mark the point after which that buffer is free again
   if (ctx->up_used[ctx->up_slot]) CK(hipEventRecord(ctx->ev_used[ctx->up_slot], ctx->stream));
   const int sl = ctx->up_slot ^= 1;

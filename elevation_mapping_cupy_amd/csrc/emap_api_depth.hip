@@ -10,6 +10,40 @@ using namespace emap_host;
 
 static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// The buffers behind a cloud the context produces itself (depth image, PointCloud2 message): the next pinned slot (its copy of two calls
+// ago done), the device copy of the caller's bytes and the owned cloud, each grown on demand.  Only one cloud is bound at a time, so
+// both doors share them.
+int emap_host::owned_cloud_prepare(emap_ctx* ctx, size_t pin_bytes, size_t img_bytes, long tot, int* slot) {
+  const int sl = ctx->depth_slot ^= 1;
+  if (!ctx->depth_ev[sl]) CK(hipEventCreateWithFlags(&ctx->depth_ev[sl], hipEventDisableTiming));
+  if (ctx->depth_ev_on[sl]) CK(hipEventSynchronize(ctx->depth_ev[sl]));      // the copy out of this slot two calls ago (long done in a running stream)
+  if (pin_bytes > ctx->depth_pin_cap[sl]) {
+    if (ctx->depth_pin[sl]) CK(hipHostFree(ctx->depth_pin[sl]));
+    ctx->depth_pin[sl] = nullptr; ctx->depth_pin_cap[sl] = 0; ctx->depth_ev_on[sl] = false;
+    CK(hipHostMalloc((void**)&ctx->depth_pin[sl], pin_bytes, hipHostMallocDefault));
+    ctx->depth_pin_cap[sl] = pin_bytes;
+  }
+  if (img_bytes > ctx->depth_img_cap || tot > ctx->depth_cloud_cap) {
+    // growing: kernels in flight may still read either buffer, and the cloud may be the bound one -- drain, unbind, then replace
+    CK(hipStreamSynchronize(ctx->stream));
+    if (img_bytes > ctx->depth_img_cap) {
+      if (ctx->depth_img) CK(hipFree(ctx->depth_img));
+      ctx->depth_img = nullptr; ctx->depth_img_cap = 0;
+      CK(hipMalloc((void**)&ctx->depth_img, img_bytes));
+      ctx->depth_img_cap = img_bytes;
+    }
+    if (tot > ctx->depth_cloud_cap) {
+      if (ctx->depth_cloud && ctx->pts == ctx->depth_cloud) { ctx->pts = nullptr; ctx->n_pts = 0; ctx->n_pts_all = 0; ctx->pts_bucketed = false; }
+      if (ctx->depth_cloud) CK(hipFree(ctx->depth_cloud));
+      ctx->depth_cloud = nullptr; ctx->depth_cloud_cap = 0;
+      CK(hipMalloc((void**)&ctx->depth_cloud, sizeof(float) * (size_t)tot));
+      ctx->depth_cloud_cap = tot;
+    }
+  }
+  *slot = sl;
+  return EMAP_OK;
+}
+
 extern "C" {
 
 int emap_bind_depth_image(emap_ctx* ctx, const emap_depth_desc* d, const void* depth, const uint8_t* rgb_or_null, const float* features_or_null,
@@ -44,32 +78,8 @@ int emap_bind_depth_image(emap_ctx* ctx, const emap_depth_desc* d, const void* d
   // the cloud as upload_impl lays it out: xyz (n, 3), the channel matrix behind it at a 256-byte boundary
   const long chan_off = Kc ? ((3 * A.n + 63) & ~63L) : 0, tot = Kc ? chan_off + (long)Kc * A.n : 3 * A.n;
 
-  const int sl = ctx->depth_slot ^= 1;
-  if (!ctx->depth_ev[sl]) CK(hipEventCreateWithFlags(&ctx->depth_ev[sl], hipEventDisableTiming));
-  if (ctx->depth_ev_on[sl]) CK(hipEventSynchronize(ctx->depth_ev[sl]));      // the copy out of this slot two calls ago (long done in a running stream)
-  if (img_bytes > ctx->depth_pin_cap[sl]) {
-    if (ctx->depth_pin[sl]) CK(hipHostFree(ctx->depth_pin[sl]));
-    ctx->depth_pin[sl] = nullptr; ctx->depth_pin_cap[sl] = 0; ctx->depth_ev_on[sl] = false;
-    CK(hipHostMalloc((void**)&ctx->depth_pin[sl], img_bytes, hipHostMallocDefault));
-    ctx->depth_pin_cap[sl] = img_bytes;
-  }
-  if (img_bytes > ctx->depth_img_cap || tot > ctx->depth_cloud_cap) {
-    // growing: kernels in flight may still read either buffer, and the cloud may be the bound one -- drain, unbind, then replace
-    CK(hipStreamSynchronize(ctx->stream));
-    if (img_bytes > ctx->depth_img_cap) {
-      if (ctx->depth_img) CK(hipFree(ctx->depth_img));
-      ctx->depth_img = nullptr; ctx->depth_img_cap = 0;
-      CK(hipMalloc((void**)&ctx->depth_img, img_bytes));
-      ctx->depth_img_cap = img_bytes;
-    }
-    if (tot > ctx->depth_cloud_cap) {
-      if (ctx->depth_cloud && ctx->pts == ctx->depth_cloud) { ctx->pts = nullptr; ctx->n_pts = 0; ctx->n_pts_all = 0; ctx->pts_bucketed = false; }
-      if (ctx->depth_cloud) CK(hipFree(ctx->depth_cloud));
-      ctx->depth_cloud = nullptr; ctx->depth_cloud_cap = 0;
-      CK(hipMalloc((void**)&ctx->depth_cloud, sizeof(float) * (size_t)tot));
-      ctx->depth_cloud_cap = tot;
-    }
-  }
+  int sl;
+  { const int rc = owned_cloud_prepare(ctx, img_bytes, img_bytes, tot, &sl); if (rc) return rc; }
   unsigned char* pin = ctx->depth_pin[sl];
   memcpy(pin, depth, b_depth);
   if (b_conf) memcpy(pin + o_conf, confidence_or_null, b_conf);

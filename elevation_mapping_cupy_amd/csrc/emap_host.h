@@ -192,6 +192,7 @@ namespace emap_host {
 // emap_api.hip
 float q16(float x);
 int sf_settle(emap_ctx* ctx);
+int upload_setup(emap_ctx* ctx);
 Pose make_pose(const emap_ctx* ctx, const float R[9], const float t[3]);
 int flush_moves(emap_ctx* ctx);
 int normal_row_lag(const emap_ctx* ctx);
@@ -206,6 +207,8 @@ int halo_exchange_start(emap_ctx* ctx);
 int normal_exchange(emap_ctx* ctx);
 bool rays_by_ray(const emap_ctx* ctx);
 int rays_by_ray_pass(emap_ctx* ctx, const float R[9], const float t[3], const Frame* f);
+// emap_api_depth.hip: pinned slot, device copy of the caller's bytes (img_bytes) and owned cloud (tot floats) of the doors that produce their cloud
+int owned_cloud_prepare(emap_ctx* ctx, size_t pin_bytes, size_t img_bytes, long tot, int* slot);
 }  // namespace emap_host
 
 // Every entry point that reads or changes the map, the drift record or a cloud buffer settles the small frames in flight first

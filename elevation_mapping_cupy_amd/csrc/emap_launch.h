@@ -19,6 +19,20 @@ struct DepthArgs { int H, W, step, Hs, Ws, has_rgb, n_feat; long n, plane; float
 #define EM_DEPTH_MAX_SIDE 8192      /* emap_bind_depth_image: image sides, step and channel count it accepts */
 #define EM_DEPTH_MAX_STEP 64
 #define EM_DEPTH_MAX_CHAN 16
+// k_cloud_unpack (emap_cloudmsg.hip): the message on the device (`rows` rows of `width` points, row r at byte r * row_step; a message
+// with tight rows travels as ONE row of n points), the column table (byte offset inside the point | conv << 16) and the cloud it writes
+#define EM_CLOUDMSG_MAX_COLS 19
+#define EM_CLOUDMSG_MAX_STEP 256
+#define EM_CLOUDMSG_MAX_POINTS (1L << 26)
+#define EM_CLOUDMSG_STAGE_BYTES 16384      /* message bytes a workgroup stages in LDS (+ 32 of alignment head and look-ahead) */
+struct CloudMsgArgs { const unsigned char* msg; float* xyz; float* chan; long row_step; int rows, width, point_step, n_cols, tile, tiles_per_row;
+                      unsigned int col[EM_CLOUDMSG_MAX_COLS]; };
+// points per workgroup: the largest power of two in 64 .. 1024 whose bytes fit the stage (point_step 1 .. 256: 64 * 256 = the stage)
+static inline int cloud_unpack_tile(int point_step) {
+  int t = 1024;
+  while (t > 64 && (long)t * point_step > EM_CLOUDMSG_STAGE_BYTES) t >>= 1;
+  return t;
+}
 
 // ---- limits shared by the host layer and emap_binned.hip -----------------------------------------------------------------------------
 #define BIN_MAX_T 16384   /* LDS histogram / cursor arrays are dynamic: 4 B per tile */
@@ -87,3 +101,6 @@ bool bin_fuse_takes_semantics(const SplitView&, bool, bool, int);
 
 // depth-image input (emap_depth.hip)
 void launch_depth_cloud(hipStream_t, const DepthArgs&, int);
+
+// PointCloud2 input (emap_cloudmsg.hip); aligned4: every field read is one aligned dword of the message
+void launch_cloud_unpack(hipStream_t, const CloudMsgArgs&, bool aligned4);

@@ -15,7 +15,7 @@ from typing import List
 import numpy as np
 
 from . import _lib
-from ._lib import EmapDepthDesc, EmapError, EmapParams, EmapStats, EmapStrip, PLANES, f32p
+from ._lib import EmapCloudMsgDesc, EmapDepthDesc, EmapError, EmapParams, EmapStats, EmapStrip, PLANES, f32p
 from .parameter import Parameter
 
 
@@ -37,6 +37,51 @@ def _hull_ring(cells):
     except QhullError:              # collinear cells
         return None
     return np.vstack([pts[v], pts[v[:1]]])
+
+
+def _field(f):
+    """(name, offset, datatype, count) of a sensor_msgs/PointField-like object or of such a tuple"""
+    if isinstance(f, (tuple, list)):
+        name, offset, datatype, count = f
+    else:
+        name, offset, datatype, count = f.name, f.offset, f.datatype, f.count
+    return str(name), int(offset), int(datatype), int(count)
+
+
+def pointcloud2_descriptor(fields, width, height, point_step, row_step=None, is_bigendian=False, channels=None, typed=False):
+    """``(EmapCloudMsgDesc, names)`` of a PointCloud2 layout for ``emap_bind_cloud_message`` (include/emap_hip.h); needs no context.
+
+    ``fields``: sensor_msgs/PointField-like objects or ``(name, offset, datatype, count)`` tuples.  ``channels=None``: every field in
+    message order becomes a column and the first three are x, y, z whatever they are called (the node's rule,
+    elevation_mapping_ros.cpp:309-313, 333-337); ``channels`` given: the fields named x, y, z and then the named ones.  ``typed=False``:
+    every column is the node's 4-byte memcpy (conv 0); ``typed=True``: converted from the field's datatype, except FLOAT32 fields and
+    the packed colours ``rgb`` / ``rgba``, which are moved.  ``names``: the columns' names."""
+    fs = [_field(f) for f in fields]
+    if channels is None:
+        cols = fs
+    else:
+        by_name = {}
+        for f in fs:
+            by_name.setdefault(f[0], f)
+        missing = [n for n in ["x", "y", "z"] + list(channels) if n not in by_name]
+        if missing:
+            raise ValueError("the message has no field named %s" % ", ".join(map(repr, missing)))
+        cols = [by_name[n] for n in ["x", "y", "z"] + list(channels)]
+    if not 3 <= len(cols) <= 19:
+        raise ValueError("a cloud has x, y, z and at most 16 channels; %d columns selected" % len(cols))
+    for name, _, _, count in cols:
+        if count != 1:
+            raise ValueError("field %r has count %d; only fields of one element can become a column" % (name, count))
+    if point_step is None:
+        raise ValueError("point_step is required")
+    d = EmapCloudMsgDesc()
+    d.height, d.width, d.point_step = int(height), int(width), int(point_step)
+    d.row_step = int(width) * int(point_step) if row_step is None else int(row_step)
+    d.is_bigendian, d.n_cols = int(bool(is_bigendian)), len(cols)
+    for c, (name, offset, datatype, _) in enumerate(cols):
+        d.offset[c] = offset
+        d.conv[c] = datatype if typed and datatype != 7 and name not in ("rgb", "rgba") else 0
+    return d, [c[0] for c in cols]
 
 
 CAM_CELL_MAX = 65536      # EM_CAM_CELL_MAX (csrc/emap_launch.h): a cap, not a measurement -- 2.6 km at 4 cm cells, far beyond any map
@@ -453,6 +498,45 @@ class ElevationMap:
         ``channels``: the names of the extra channels, colour then features -- what ``input_pointcloud`` receives as ``channels[3:]``."""
         self.bind_depth_image(depth, K, **keywords)
         self.update_map_with_kernel(None, list(channels), np.asarray(R, np.float32), np.asarray(t, np.float32).copy(),
+                                    position_noise, orientation_noise, want_stats=False)
+
+    def bind_pointcloud2(self, cloud, *, fields=None, width=None, height=1, point_step=None, row_step=None, is_bigendian=False,
+                         channels=None, typed=False):
+        """Upload the BYTES of a sensor_msgs/PointCloud2 message and bind the cloud the device unpacks from them (include/emap_hip.h:
+        emap_bind_cloud_message; the reference's node gathers the fields on the host, elevation_mapping_ros.cpp:319-338).  ``cloud``: a
+        message-like object (``.data .fields .width .height .point_step .row_step .is_bigendian``; duck-typed, no ROS import) or a
+        bytes-like / uint8 array described by the keywords (``width`` defaults to what ``row_step``, or else one of ``height`` equal shares of the data, holds).  ``channels``
+        and ``typed``: see ``pointcloud2_descriptor``.  Returns the number of rows; ``bound_channels`` then names the channel columns."""
+        if hasattr(cloud, "data") and hasattr(cloud, "fields") and hasattr(cloud, "point_step"):
+            data, fields, width, height = cloud.data, cloud.fields, cloud.width, cloud.height
+            point_step, row_step, is_bigendian = cloud.point_step, cloud.row_step, cloud.is_bigendian
+        else:
+            data = cloud
+        if fields is None:
+            raise ValueError("fields are required with raw message bytes")
+        try:
+            data = np.frombuffer(data, np.uint8)
+        except (TypeError, ValueError):
+            data = np.ascontiguousarray(data, np.uint8).reshape(-1)
+        if width is None:
+            if point_step is None or int(point_step) < 1 or int(height) < 1:
+                raise ValueError("point_step and height are required to derive width")
+            width = (int(row_step) if row_step is not None else data.size // int(height)) // int(point_step)
+        d, names = pointcloud2_descriptor(fields, width, height, point_step, row_step, is_bigendian, channels, typed)
+        if d.height >= 1 and d.row_step >= 0 and data.size < d.height * d.row_step:
+            raise ValueError("the message holds %d bytes where height * row_step = %d are described" % (data.size, d.height * d.row_step))
+        n = ct.c_int64(0)
+        self._chk(self._lib.emap_bind_cloud_message(self._ctx, ct.byref(d), ct.c_void_p(data.ctypes.data), ct.byref(n)))
+        self._n_bound, self._k_bound = int(n.value), d.n_cols - 3
+        self._bound_host = None
+        self.bound_channels = names[3:]
+        return self._n_bound
+
+    def input_pointcloud2(self, cloud, R, t, position_noise: float, orientation_noise: float, **keywords):
+        """``input_pointcloud`` for a PointCloud2 message: unpacked on the device (``bind_pointcloud2``, same keywords) and fused; the
+        channel names are the selected fields' names."""
+        self.bind_pointcloud2(cloud, **keywords)
+        self.update_map_with_kernel(None, list(self.bound_channels), np.asarray(R, np.float32), np.asarray(t, np.float32).copy(),
                                     position_noise, orientation_noise, want_stats=False)
 
     def bound_points(self):

@@ -138,6 +138,38 @@ typedef struct emap_depth_desc {
 } emap_depth_desc;
 int emap_bind_depth_image(emap_ctx* ctx, const emap_depth_desc* desc, const void* depth, const uint8_t* rgb_or_null, const float* features_or_null,
                           const float* confidence_or_null, int64_t* n_points_out);
+/* PointCloud2 input.  The reference's node walks a sensor_msgs/PointCloud2 message on the HOST, one point and one field at a time
+ * (elevation_mapping_cupy/src/elevation_mapping_ros.cpp:319-338: memcpy(&temp, &data[i * point_step + fields[j].offset], 4), widened
+ * into an (n, fields) float64 matrix), and input_pointcloud casts the matrix back to float32 and uploads it; here the message's BYTES
+ * are uploaded (point_step a point) and unpacked on the device, into the buffer the depth-image input owns, and bound exactly as that
+ * input binds its cloud.  data: height * row_step bytes.
+ * Rows: n = height * width; output row i = r * width + c reads its point at byte r * row_step + c * point_step.  The reference
+ * ignores row_step (:335, i * point_step); with row_step == width * point_step the two agree.  Nothing is compacted: a row whose x, y
+ * or z is NaN is skipped by every kernel, as for any bound cloud; no range filter is applied.
+ * Columns: n_cols = 3 + channels; column c is read at offset[c] inside the point; columns 0, 1, 2 are x, y, z.
+ *   conv[c] == 0 (pure move, the node's memcpy): the output float has the four message bytes at the offset as its bits (little
+ *   endian), moved with integer operations only -- NaN payloads and subnormal patterns such as the packed rgb colour arrive untouched.
+ *   conv[c] == 1 .. 8 (typed; the sensor_msgs/PointField datatype: 1 INT8 2 UINT8 3 INT16 4 UINT16 5 INT32 6 UINT32 7 FLOAT32 8 FLOAT64):
+ *   the value is loaded little-endian at the field's width and converted to float32 with ONE C conversion, round to nearest even,
+ *   subnormals kept; a float64 too large for float32 becomes +-inf; a float64 NaN stays a NaN (its payload bits are not part of the
+ *   contract); conv 7 produces the bits of conv 0.
+ * Output: the layout emap_set_points_device_split takes -- xyz (n, 3), the channels (n, n_cols - 3) at a 256-byte boundary behind it
+ * -- read back by emap_get_bound_points.  Row-strip contexts: the cloud is bound whole and unbucketed.
+ * Refused with EMAP_ERR_INVALID before anything is copied or launched, the previous binding untouched and *n_points_out not written:
+ * a NULL ctx, desc or data; is_bigendian != 0; height or width < 1; n > 2^26; point_step outside 1 .. 256; row_step < width *
+ * point_step; height * row_step >= 2^31; n_cols outside 3 .. 19; an unknown conv; an offset < 0; a column whose bytes (4 for conv 0,
+ * the datatype's size otherwise) do not lie inside the point -- a departure: the reference would read into the next point there.
+ * The caller's bytes are only borrowed (copied into a pinned slot before the call returns; a message of more than 2 MB by the
+ * upload's worker threads, chunk by chunk, each chunk's DMA behind it); nothing waits for the device on the success path.
+ * n_points_out (may be NULL): n. */
+typedef struct emap_cloud_msg_desc {
+  int32_t height, width, point_step, row_step, is_bigendian, n_cols;   /* n_cols = 3 + channels, 3 .. 19 */
+  int32_t offset[19];    /* byte offset of column c inside a point; columns 0, 1, 2 are x, y, z */
+  int32_t conv[19];      /* 0: the 4 bytes at the offset ARE the float32 (pure move, the node's memcpy);
+                            1..8: convert from that sensor_msgs/PointField datatype
+                            (1 INT8 2 UINT8 3 INT16 4 UINT16 5 INT32 6 UINT32 7 FLOAT32 8 FLOAT64) to float32 */
+} emap_cloud_msg_desc;
+int emap_bind_cloud_message(emap_ctx* ctx, const emap_cloud_msg_desc* desc, const uint8_t* data, int64_t* n_points_out);
 /* the cloud bound now, whoever bound it (uploaded, a caller's device cloud interleaved or split, a back-projected depth image -- what
  * pointcloud_node.py:205-250, 261-269 would have published): xyz_host (n, 3), chan_host_or_null (n, n_cols - 3), float32.  Waits for
  * the stream.  EMAP_ERR_NO_POINTS when nothing is bound. */
