@@ -141,6 +141,11 @@ struct emap_ctx {
   float* depth_cloud; long depth_cloud_cap;                   // floats
   unsigned char* depth_img; size_t depth_img_cap;             // bytes
   unsigned char* depth_pin[2]; size_t depth_pin_cap[2]; hipEvent_t depth_ev[2]; bool depth_ev_on[2]; int depth_slot;   // depth_ev: the slot's H2D copies are done
+  // image message input (emap_api_image_msg.hip): the message bytes pass through two pinned slots of the camera path's OWN into one
+  // device buffer (stream order: the kernel of the frame before precedes the overwrite) -- never the owned-cloud buffers above, whose
+  // cloud stays bound while a camera frame runs
+  unsigned char* imsg_dev; size_t imsg_cap;                   // bytes (EM_IMGMSG_SLACK included)
+  unsigned char* imsg_pin[2]; size_t imsg_pin_cap[2]; hipEvent_t imsg_ev[2]; bool imsg_ev_on[2]; int imsg_slot;   // imsg_ev: the slot's H2D copies are done
   // frame state
   bool use_override; double sum_override; unsigned int cnt_override;
   bool committed;

@@ -33,6 +33,16 @@ static inline int cloud_unpack_tile(int point_step) {
   while (t > 64 && (long)t * point_step > EM_CLOUDMSG_STAGE_BYTES) t >>= 1;
   return t;
 }
+// k_image_frame (emap_image_msg.hip): a sensor_msgs/Image message on the device (pixel (v, u) at byte v * step + u * n_chan * esize,
+// esize = the element's bytes) and the table of fusion entries a visible cell walks in order (emap_hip.h: emap_image_spec).  elem: the
+// OpenCV depth code 0 .. 6 (8U 8S 16U 16S 32S 32F 64F).  The device copy of the message carries EM_IMGMSG_SLACK bytes behind its end:
+// an element of 2 .. 8 bytes is read as the two or three aligned dwords around it.
+#define EM_IMGMSG_MAX_SIDE 8192
+#define EM_IMGMSG_MAX_SPECS 4
+#define EM_IMGMSG_MAX_INDEX (1L << 24)      /* H W (x 3 with a colour entry): beyond it the reference's float index arithmetic is not exact */
+#define EM_IMGMSG_SLACK 16
+struct ImgMsgEntry { int kind, layer, plane, pad; double alpha; };
+struct ImgMsgArgs { const unsigned char* msg; int H, W, step, elem, esize, n_chan, big, swap, n_specs, pad; ImgMsgEntry e[EM_IMGMSG_MAX_SPECS]; };
 
 // ---- limits shared by the host layer and emap_binned.hip -----------------------------------------------------------------------------
 #define BIN_MAX_T 16384   /* LDS histogram / cursor arrays are dynamic: 4 B per tile */
@@ -104,3 +114,8 @@ void launch_depth_cloud(hipStream_t, const DepthArgs&, int);
 
 // PointCloud2 input (emap_cloudmsg.hip); aligned4: every field read is one aligned dword of the message
 void launch_cloud_unpack(hipStream_t, const CloudMsgArgs&, bool aligned4);
+
+// Image message input (emap_image_msg.hip): correspondence + sampling of the message bytes + fusion, one launch; the instantiation is
+// chosen by the element's size (image_frame_variant: 0 .. 3 for 1, 2, 4, 8 bytes)
+static inline int image_frame_variant(int esize) { return esize == 1 ? 0 : esize == 2 ? 1 : esize == 4 ? 2 : 3; }
+void launch_image_frame(hipStream_t, const KP&, const CamArgs&, Cells, float*, unsigned char*, const ImgMsgArgs&, float*, long);

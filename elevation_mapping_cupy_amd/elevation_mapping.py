@@ -15,7 +15,7 @@ from typing import List
 import numpy as np
 
 from . import _lib
-from ._lib import EmapCloudMsgDesc, EmapDepthDesc, EmapError, EmapParams, EmapStats, EmapStrip, PLANES, f32p
+from ._lib import EmapCloudMsgDesc, EmapDepthDesc, EmapError, EmapImageMsgDesc, EmapImageSpec, EmapParams, EmapStats, EmapStrip, PLANES, f32p
 from .parameter import Parameter
 
 
@@ -82,6 +82,53 @@ def pointcloud2_descriptor(fields, width, height, point_step, row_step=None, is_
         d.offset[c] = offset
         d.conv[c] = datatype if typed and datatype != 7 and name not in ("rgb", "rgba") else 0
     return d, [c[0] for c in cols]
+
+
+IMAGE_ELEMS = ("8U", "8S", "16U", "16S", "32S", "32F", "64F")      # the OpenCV depth codes 0 .. 6 (emap_image_msg_desc.elem)
+IMAGE_ELEM_SIZE = (1, 1, 2, 2, 4, 4, 8)
+_NAMED_ENCODINGS = {      # sensor_msgs/image_encodings.h: (element, channels, R <-> B swap -- the node's cvtColor, bgr8 / bgra8 ONLY)
+    "mono8": ("8U", 1, False), "mono16": ("16U", 1, False),
+    "rgb8": ("8U", 3, False), "rgba8": ("8U", 4, False), "bgr8": ("8U", 3, True), "bgra8": ("8U", 4, True),
+    "rgb16": ("16U", 3, False), "rgba16": ("16U", 4, False), "bgr16": ("16U", 3, False), "bgra16": ("16U", 4, False),
+}
+IMAGE_MAX_SIDE = 8192             # EM_IMGMSG_MAX_SIDE (csrc/emap_launch.h)
+IMAGE_MAX_INDEX = 1 << 24         # EM_IMGMSG_MAX_INDEX: H W (x 3 with a colour entry); the reference's float index arithmetic is exact up to here
+
+
+def image_encoding(encoding):
+    """``(elem code, n_chan, swap_rb)`` of a sensor_msgs/Image encoding string: the generic ``8UC1 .. 64FC4`` (a bare ``8UC`` means one
+    channel), ``mono8/16`` and the ``rgb / rgba / bgr / bgra`` encodings of 8 and 16 bits.  Only ``bgr8`` / ``bgra8`` are swapped to RGB,
+    as the node does (elevation_mapping_ros.cpp:382-386); ``bgr16`` / ``bgra16`` pass as they are.  Anything else (bayer, yuv, unknown
+    strings) raises ``ValueError``."""
+    enc = str(encoding)
+    if enc in _NAMED_ENCODINGS:
+        e, n, swap = _NAMED_ENCODINGS[enc]
+        return IMAGE_ELEMS.index(e), n, swap
+    for code, e in enumerate(IMAGE_ELEMS):
+        if enc.startswith(e + "C") and enc[len(e) + 1:] in ("", "1", "2", "3", "4"):
+            return code, int(enc[len(e) + 1:] or 1), False
+    raise ValueError("image encoding %r is not supported (8UC1 .. 64FC4, mono8/16, rgb/rgba/bgr/bgra 8/16)" % (encoding,))
+
+
+def image_message_descriptor(encoding, height, width, step=None, is_bigendian=False):
+    """``EmapImageMsgDesc`` of a sensor_msgs/Image layout for ``emap_input_image_message`` (include/emap_hip.h); needs no context.
+    ``step=None``: tight rows.  Raises ``ValueError`` for everything the entry point would refuse that can be seen here."""
+    elem, n_chan, swap = image_encoding(encoding)
+    height, width = int(height), int(width)
+    if not (1 <= height <= IMAGE_MAX_SIDE and 1 <= width <= IMAGE_MAX_SIDE):
+        raise ValueError("image sides must lie in 1 .. %d (%d x %d)" % (IMAGE_MAX_SIDE, height, width))
+    tight = width * n_chan * IMAGE_ELEM_SIZE[elem]
+    step = tight if step is None else int(step)
+    if step < tight:
+        raise ValueError("step %d is smaller than width * channels * element size = %d" % (step, tight))
+    if height * step >= 1 << 31:
+        raise ValueError("height * step must stay below 2^31 bytes")
+    if height * width > IMAGE_MAX_INDEX:
+        raise ValueError("height * width beyond 2^24 pixels: use input_image")
+    d = EmapImageMsgDesc()
+    d.height, d.width, d.step, d.elem, d.n_chan = height, width, step, elem, n_chan
+    d.is_bigendian, d.swap_rb = int(bool(is_bigendian)), int(swap)
+    return d
 
 
 CAM_CELL_MAX = 65536      # EM_CAM_CELL_MAX (csrc/emap_launch.h): a cap, not a measurement -- 2.6 km at 4 cm cells, far beyond any map
@@ -653,6 +700,71 @@ class ElevationMap:
                 f32p(np.ascontiguousarray(K.reshape(-1))), f32p(np.ascontiguousarray(D)), ct.c_float(float(image_height)),
                 ct.c_float(float(image_width)), f32p(np.ascontiguousarray(self.center, np.float32))))
             self.semantic_map.update_layers_image(self, image, list(channels), image_height, image_width)
+
+    def input_image_message(self, image, channels: List[str], R, t, K=None, D=None, distortion_model: str = "radtan", camera_info=None, **raw):
+        """``input_image`` for the BYTES of a sensor_msgs/Image: the message is uploaded as it is and one launch computes the
+        correspondence and fuses every channel (include/emap_hip.h: emap_input_image_message; the reference's node converts the message
+        to one float matrix per channel on the host, elevation_mapping_ros.cpp:375-446).  ``image``: a message-like object (``.height
+        .width .encoding .is_bigendian .step .data``; duck-typed, no ROS import) or a bytes-like / uint8 array described by the keywords
+        of the same names.  ``camera_info``: an object with ``.K .D .distortion_model`` used where ``K`` / ``D`` are not given.  The
+        planes are the node's: ``bgr8`` / ``bgra8`` arrive as RGB; channel ``j`` of the list samples plane ``j`` and ``rgb`` planes 0, 1, 2,
+        exactly as ``update_layers_image`` hands them over; a plane count that does not match the channel list (``rgb`` counts as 3)
+        raises ``ValueError`` where the node drops the frame (:428-441).  Returns without waiting for the device."""
+        if hasattr(image, "data") and hasattr(image, "encoding"):
+            data = image.data
+            raw = dict(height=image.height, width=image.width, encoding=image.encoding, is_bigendian=image.is_bigendian, step=image.step)
+        else:
+            data = image
+        unknown = set(raw) - {"height", "width", "encoding", "is_bigendian", "step"}
+        if unknown:
+            raise TypeError("unexpected keywords: %s" % ", ".join(sorted(unknown)))
+        if not all(k in raw for k in ("height", "width", "encoding")):
+            raise ValueError("height, width and encoding are required with raw message bytes")
+        d = image_message_descriptor(raw["encoding"], raw["height"], raw["width"], raw.get("step"), raw.get("is_bigendian", False))
+        try:
+            data = np.frombuffer(data, np.uint8)
+        except (TypeError, ValueError):
+            data = np.ascontiguousarray(data, np.uint8).reshape(-1)
+        if data.size < d.height * d.step:
+            raise ValueError("the message holds %d bytes where height * step = %d are described" % (data.size, d.height * d.step))
+        channels = list(channels)
+        planes = sum(3 if c == "rgb" else 1 for c in channels)
+        if planes != d.n_chan:
+            raise ValueError("the image has %d planes, the channels %s ask for %d" % (d.n_chan, channels, planes))
+        if camera_info is not None:
+            K = camera_info.K if K is None else K
+            D = camera_info.D if D is None else D
+            distortion_model = getattr(camera_info, "distortion_model", distortion_model) or distortion_model
+        if K is None:
+            raise ValueError("K or camera_info is required")
+        K = np.asarray(K, np.float32).reshape(3, 3); R = np.asarray(R, np.float32); t = np.asarray(t, np.float32)
+        D = np.asarray([] if D is None else D, np.float32).reshape(-1)
+        if len(D) < 4:
+            D = np.zeros(5, np.float32)
+        elif len(D) == 4:
+            D = np.concatenate([D, np.zeros(1, np.float32)])
+        else:
+            D = D[:5].copy()
+        if distortion_model != "radtan":
+            D = D * 0            # as input_image
+        P = (K @ np.concatenate([R, t[:, None]], 1)).astype(np.float32)
+        x1, y1, z1 = camera_cell(self.center, self.cell_n, self.resolution, R, t)
+        cam = (ct.c_float(x1), ct.c_float(y1), ct.c_float(z1), f32p(np.ascontiguousarray(P.reshape(-1))), f32p(np.ascontiguousarray(K.reshape(-1))),
+               f32p(np.ascontiguousarray(D)))
+        center = np.ascontiguousarray(self.center, np.float32)
+        with self.map_lock:
+            entries = self.semantic_map.image_entries(channels)
+            if any(e[0] == 1 for e in entries) and 3 * d.height * d.width > IMAGE_MAX_INDEX:
+                raise ValueError("3 * height * width beyond 2^24 with a colour channel: use input_image")
+            if len(entries) > 4:
+                raise ValueError("at most 4 fused channels per image message (%d asked for)" % len(entries))
+            if not entries:      # nothing to fuse: the correspondence alone, as input_image computes it
+                self._chk(self._lib.emap_image_correspondence(self._ctx, *cam, ct.c_float(float(d.height)), ct.c_float(float(d.width)), f32p(center)))
+                return
+            specs = (EmapImageSpec * len(entries))()
+            for s, (kind, layer, plane, alpha) in zip(specs, entries):
+                s.kind, s.layer, s.plane, s.alpha = kind, layer, plane, alpha
+            self._chk(self._lib.emap_input_image_message(self._ctx, ct.byref(d), ct.c_void_p(data.ctypes.data), *cam, f32p(center), specs, len(entries)))
 
     def get_image_correspondence(self):
         """(uv (2, C, C) float32, valid (C, C) bool) of the last input_image call"""

@@ -169,6 +169,25 @@ class SemanticMap:
             emap._chk(emap._lib.emap_image_fuse(emap._ctx, kind, idx, f32p(np.ascontiguousarray(img)), int(img.shape[0]),
                                                 int(image_height), int(image_width), ct.c_double(getattr(plug, "alpha", 0.7))))
 
+    def image_entries(self, channels):
+        """the calls ``update_layers_image`` would make for ``channels``, as the entry table of ``emap_input_image_message``:
+        ``(kind, layer, plane, alpha)`` per fused channel, in order; layers are added on the way exactly as there"""
+        process_channels, fusion_methods = self.get_fusion(channels, self.param.image_channel_fusions, self.layer_specs_image)
+        entries = []
+        for j, (fusion, channel) in enumerate(zip(fusion_methods, process_channels)):
+            if channel not in self.layer_names:
+                print(f"Layer {channel} not found, adding it to the semantic map", file=sys.stderr)
+                self.add_layer(channel)
+            plug = self.fusion_manager.get_plugin(fusion, "image")
+            if plug is None:
+                continue
+            idx = self.layer_names.index(channel)
+            if plug.kind == "color":      # planes 0 .. 2 of the stack
+                entries.append((1, idx, 0, float(getattr(plug, "alpha", 0.7))))
+            else:                         # plane j of the stack: the position in the channel list, as the reference's plugin call passes it
+                entries.append((0, idx, j, float(getattr(plug, "alpha", 0.7))))
+        return entries
+
     # ---- read-back -----------------------------------------------------------------------------------
     def _layer(self, idx):
         out = np.empty((self._emap.rows, self._emap.cell_n), np.float32)

@@ -358,6 +358,32 @@ int emap_image_fuse(emap_ctx* ctx, int32_t kind, int32_t layer, const float* hos
 int emap_image_set_tolerance(emap_ctx* ctx, double tolerance_z_collision);
 int emap_image_fuse_arrays(emap_ctx* ctx, int32_t kind, const float* sem_plane, const float* host_image, int32_t n_planes, int32_t height,
                            int32_t width, const float* uv, const uint8_t* valid, double alpha, float* out_plane);
+/* Image message input: one camera frame from the BYTES of a sensor_msgs/Image, in one launch.  The reference's node converts the
+ * message on the host (elevation_mapping_cupy/src/elevation_mapping_ros.cpp:375-446: cvtColor for bgr8 / bgra8, cv::split, cv2eigen
+ * into one float matrix per channel), input_image uploads the float stack and launches the correspondence kernel and one sampling
+ * kernel per channel; here the message's bytes are uploaded as they are and ONE kernel computes the correspondence (written where
+ * emap_image_get_correspondence reads it) and, per visible cell, walks the entry table in order, sampling the bytes on the device.
+ * The result is bit for bit what emap_image_correspondence + one emap_image_fuse per entry leave for the planes defined below.
+ * Message: height * step bytes; pixel (v, u) starts at byte v * step + u * n_chan * size(elem); padding bytes are never read.
+ * elem: the OpenCV depth code, 0 8U 1 8S 2 16U 3 16S 4 32S 5 32F 6 64F.  Plane p of pixel (v, u) is message channel c of that pixel,
+ * c = 2 - p if swap_rb and p is 0 or 2 (the node's BGR -> RGB for bgr8 / bgra8), else c = p; loaded at the element's width in the
+ * message's byte order (is_bigendian), alignment safe (step may be odd), and converted to float32 with ONE C conversion, round to
+ * nearest even, subnormals kept; a float64 beyond float32 becomes +-inf; a NaN stays a NaN (its payload is not part of the contract);
+ * a 32F element is moved.
+ * specs: 1 .. 4 entries, applied in order inside each visible cell: kind 0 exponential (alpha), 1 colour (planes 0, 1, 2 = r, g, b; plane
+ * is ignored), 2 average (the sample replaces the value); layer: the semantic layer; plane: the plane sampled (kinds 0, 2).
+ * Refused with EMAP_ERR_INVALID before anything is copied or launched, correspondence and layers untouched: a NULL pointer; a camera
+ * cell emap_image_correspondence refuses; a row-strip context; height or width outside 1 .. 8192; step < width * n_chan * size(elem);
+ * height * step >= 2^31; an unknown elem; n_chan outside 1 .. 4; n_specs outside 1 .. 4; a kind outside 0 .. 2; a layer that is not
+ * configured; plane < 0 or >= n_chan; a colour entry or swap_rb with n_chan < 3; height * width * (3 with a colour entry, else 1) > 2^24 (beyond
+ * it the reference's float index arithmetic is no longer exact: emap_image_fuse remains for such images).
+ * The caller's bytes are only borrowed (copied into a pinned slot of the camera path's own before the call returns; a message of more
+ * than 2 MB by the upload's worker threads, chunk by chunk); the bound cloud stays bound; nothing waits for the device. */
+typedef struct emap_image_msg_desc { int32_t height, width, step, elem, n_chan, is_bigendian, swap_rb; } emap_image_msg_desc;
+typedef struct emap_image_spec { int32_t kind, layer, plane, pad; double alpha; } emap_image_spec;
+int emap_input_image_message(emap_ctx* ctx, const emap_image_msg_desc* desc, const uint8_t* data, float x1, float y1, float z1,
+                             const float P[12], const float K[9], const float D[5], const float center[3],
+                             const emap_image_spec* specs, int32_t n_specs);
 
 /* ---- safety-polygon service: polygon_mask_kernel (EM/kernels/custom_kernels.py:509-651) as launched by
  * ElevationMap.get_polygon_traversability (EM/elevation_mapping.py:837-889).  `polygon_xy` = (n, 2) float32 world
