@@ -285,6 +285,26 @@ __device__ __forceinline__ void cell_now(const KP& P, float4& m, int prow, int p
   if (P.mv.n) { float time = 0.f, upper = 0.f, is_upper = 0.f; cell_now(P, m.x, m.y, m.z, m.w, time, upper, is_upper, prow, pcol); }
 }
 
+// What get_map_with_name_ref publishes of one cell (elevation_mapping.py:579-775) for the cell layers -- kind 0 elevation, 1 variance,
+// 2 traversability, 3 time, 4 upper_bound, 5 is_upper_bound: NaN for unknown cells, + center_z for heights.  (r, c): the cell's LOGICAL
+// row / column.  Shared by k_publish (one layer per launch) and k_grid_map (every layer of a message per launch): one set of rules.
+// Reads of m: kind 0 h valid; 1 v; 2 trav valid is_upper; 3 time; 4 upper is_upper valid; 5 is_upper upper valid.
+__device__ __forceinline__ float publish_value(int kind, const Cell& m, int r, int c, int C, float center_z, int only_above) {
+  const float nanv = __uint_as_float(0x7fc00000u);
+  float v;
+  switch (kind) {
+    case 0: v = m.valid > 0.5f ? m.h + center_z : nanv; break;
+    case 1: v = m.v; break;
+    case 2: v = (r >= 3 && r <= C - 4 && c >= 3 && c <= C - 4 && (m.valid + m.is_upper) > 0.5f) ? m.trav : nanv; break;
+    case 3: v = m.time; break;
+    default: {
+      const bool ok = only_above ? ((m.upper > 0.0f && m.is_upper > 0.5f) || m.valid > 0.5f) : (m.valid > 0.5f || m.is_upper > 0.5f);
+      v = ok ? (kind == 4 ? m.upper + center_z : m.is_upper) : nanv;
+    }
+  }
+  return v;
+}
+
 // effects of custom_kernels.py:174 and :189-192 on one cell (-> snapshot S1)
 __device__ __forceinline__ void commit_cell(const KP& P, Cell& c, const AccF& a) {
   unsigned int cnt = (unsigned int)(a.cnt_out & 0xffffffffull), n_out = (unsigned int)(a.cnt_out >> 32);

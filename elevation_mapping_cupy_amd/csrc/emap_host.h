@@ -146,6 +146,8 @@ struct emap_ctx {
   // cloud stays bound while a camera frame runs
   unsigned char* imsg_dev; size_t imsg_cap;                   // bytes (EM_IMGMSG_SLACK included)
   unsigned char* imsg_pin[2]; size_t imsg_pin_cap[2]; hipEvent_t imsg_ev[2]; bool imsg_ev_on[2]; int imsg_slot;   // imsg_ev: the slot's H2D copies are done
+  // GridMap message output (emap_api_gridmsg.hip): the planes k_grid_map writes, grown on demand (`scratch` stays the single plane it is)
+  float* grid_buf; size_t grid_cap;                           // floats
   // frame state
   bool use_override; double sum_override; unsigned int cnt_override;
   bool committed;

@@ -1533,21 +1533,11 @@ __global__ __launch_bounds__(EM_BLOCK) void k_publish(KP P, Cells cells, const f
   if (k >= (long)M * M) return;
   const int orow = (int)(k / M), ocol = (int)(k % M);
   const int r = M - orow, c = M - ocol;                 // flip of the [1:-1, 1:-1] view: source cell (r, c) in [1, C-2], logical
-  const float nanv = __uint_as_float(0x7fc00000u);
   float v;
   if (kind >= 6) v = normal[(long)(kind - 6) * plane_stride + (long)wrap_up(r + P.norg_r, C) * C + wrap_up(c + P.norg_c, C)];
   else {
     const Cell m = cells[(long)(phys_row(P, r) + P.halo) * C + phys_col(P, c)];
-    switch (kind) {
-      case 0: v = m.valid > 0.5f ? m.h + center_z : nanv; break;
-      case 1: v = m.v; break;
-      case 2: v = (r >= 3 && r <= C - 4 && c >= 3 && c <= C - 4 && (m.valid + m.is_upper) > 0.5f) ? m.trav : nanv; break;
-      case 3: v = m.time; break;
-      default: {
-        const bool ok = only_above ? ((m.upper > 0.0f && m.is_upper > 0.5f) || m.valid > 0.5f) : (m.valid > 0.5f || m.is_upper > 0.5f);
-        v = ok ? (kind == 4 ? m.upper + center_z : m.is_upper) : nanv;
-      }
-    }
+    v = publish_value(kind, m, r, c, C, center_z, only_above);      // (emap_device.h: shared with k_grid_map)
   }
   out[k] = v;
 }

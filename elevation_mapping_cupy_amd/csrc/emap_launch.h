@@ -43,6 +43,20 @@ static inline int cloud_unpack_tile(int point_step) {
 #define EM_IMGMSG_SLACK 16
 struct ImgMsgEntry { int kind, layer, plane, pad; double alpha; };
 struct ImgMsgArgs { const unsigned char* msg; int H, W, step, elem, esize, n_chan, big, swap, n_specs, pad; ImgMsgEntry e[EM_IMGMSG_MAX_SPECS]; };
+// k_grid_map (emap_gridmsg.hip): every device-resident layer of a grid_map message from one launch.  Layer l of the table is written to
+// plane pos[l] of `out` (planes of M * M floats, M = C - 2; the host packs the caller's slots in ascending order), element (i, j) at
+// i * M + j (order 0) or j * M + i (order 1: the message's column-major Float32MultiArray).  kind / index: emap_hip.h (EMAP_GRID_*).
+// need: what the table reads of a cell -- bit 0 the hot half, 1 the cold half, 2 .. 4 the normal planes x, y, z (set by grid_need).
+#define EM_GRID_MAX_LAYERS 32
+#define EM_GRID_TILE 32
+struct GridArgs { int n, order, only_above, need; float center_z; int pad_; long plane, sem_plane; const float* normal; const float* sem; float* out;
+                  unsigned char kind[EM_GRID_MAX_LAYERS], pos[EM_GRID_MAX_LAYERS]; int index[EM_GRID_MAX_LAYERS]; };
+static inline int grid_need(int kind, int index) {
+  if (kind == 1) return 0;                                              // semantic: its own plane
+  if (kind == 2) return 4 | 8 | 16;                                     // normal colour
+  if (index >= 6) return 4 << (index - 6);                              // normal_x / y / z
+  return index == 2 ? 3 : (index <= 1 ? 1 : 2);                         // traversability: both halves; elevation, variance: hot; time, upper_bound, is_upper_bound: cold (w = valid)
+}
 
 // ---- limits shared by the host layer and emap_binned.hip -----------------------------------------------------------------------------
 #define BIN_MAX_T 16384   /* LDS histogram / cursor arrays are dynamic: 4 B per tile */
@@ -119,3 +133,6 @@ void launch_cloud_unpack(hipStream_t, const CloudMsgArgs&, bool aligned4);
 // chosen by the element's size (image_frame_variant: 0 .. 3 for 1, 2, 4, 8 bytes)
 static inline int image_frame_variant(int esize) { return esize == 1 ? 0 : esize == 2 ? 1 : esize == 4 ? 2 : 3; }
 void launch_image_frame(hipStream_t, const KP&, const CamArgs&, Cells, float*, unsigned char*, const ImgMsgArgs&, float*, long);
+
+// GridMap message output (emap_gridmsg.hip): whole-map contexts only (the caller checks)
+void launch_grid_map(hipStream_t, const KP&, Cells, const GridArgs&);

@@ -10,12 +10,14 @@ from __future__ import annotations
 import ctypes as ct
 import os
 import threading
+import types
 from typing import List
 
 import numpy as np
 
 from . import _lib
-from ._lib import EmapCloudMsgDesc, EmapDepthDesc, EmapError, EmapImageMsgDesc, EmapImageSpec, EmapParams, EmapStats, EmapStrip, PLANES, f32p
+from ._lib import (EmapCloudMsgDesc, EmapDepthDesc, EmapError, EmapGridLayer, EmapImageMsgDesc, EmapImageSpec, EmapParams, EmapStats, EmapStrip,
+                   GRID_BUILTIN, GRID_MAX_LAYERS, GRID_NORMAL_COLOR, GRID_ORDERS, GRID_SEMANTIC, PLANES, f32p)
 from .parameter import Parameter
 
 
@@ -129,6 +131,51 @@ def image_message_descriptor(encoding, height, width, step=None, is_bigendian=Fa
     d.height, d.width, d.step, d.elem, d.n_chan = height, width, step, elem, n_chan
     d.is_bigendian, d.swap_rb = int(bool(is_bigendian)), int(swap)
     return d
+
+
+GRID_BUILTIN_LAYERS = ("elevation", "variance", "traversability", "time", "upper_bound", "is_upper_bound", "normal_x", "normal_y", "normal_z")      # emap_publish_layer's kinds 0 .. 8
+GRID_NORMAL_COLOR_LAYERS = ("normal_x", "normal_y", "normal_z", "color")      # what the wrapper appends with enable_normal_color (elevation_mapping_wrapper.cpp:239-251)
+
+
+def grid_map_descriptor(layers, semantic_layers=(), normal_color=False, slots=None):
+    """``(table, names)`` of a GridMap publisher's layer list for ``emap_publish_grid_map`` (include/emap_hip.h); needs no context.
+
+    ``layers``: names of device-resident layers in message order -- the nine built-ins (``GRID_BUILTIN_LAYERS``) and the names in
+    ``semantic_layers`` (position = the semantic layer's index).  ``normal_color``: ``normal_x``, ``normal_y``, ``normal_z`` and ``color`` are
+    appended as the wrapper appends them (a name already in the list is not added twice); only then is ``color`` a known name, and the
+    four names then mean the normal planes and their colour whatever else carries those names.  ``slots``: the plane of the output each
+    layer lands in (default: its position).  ``table``: an ``EmapGridLayer`` array.  Raises ``ValueError`` for what the entry point would
+    refuse that can be seen here: no layer, more than 32, an unknown name, a name or a slot given twice, a negative slot, a slot list of
+    another length."""
+    names = [str(n) for n in layers]
+    if len(set(names)) != len(names):
+        raise ValueError("a layer is named twice: %s" % ", ".join(sorted(n for n in set(names) if names.count(n) > 1)))
+    if normal_color:
+        names += [n for n in GRID_NORMAL_COLOR_LAYERS if n not in names]
+    if not names:
+        raise ValueError("no layer asked for")
+    if len(names) > GRID_MAX_LAYERS:
+        raise ValueError("at most %d layers per launch (%d asked for)" % (GRID_MAX_LAYERS, len(names)))
+    slots = list(range(len(names))) if slots is None else [int(x) for x in slots]
+    if len(slots) != len(names):
+        raise ValueError("%d slots for %d layers" % (len(slots), len(names)))
+    if any(x < 0 for x in slots):
+        raise ValueError("a slot is negative")
+    if len(set(slots)) != len(slots):
+        raise ValueError("a slot is named twice")
+    semantic_layers = list(semantic_layers)
+    table = (EmapGridLayer * len(names))()
+    for g, n, slot in zip(table, names, slots):
+        if normal_color and n == "color":
+            g.kind, g.index = GRID_NORMAL_COLOR, 0
+        elif n in GRID_BUILTIN_LAYERS and (n not in semantic_layers or (normal_color and n in GRID_NORMAL_COLOR_LAYERS)):
+            g.kind, g.index = GRID_BUILTIN, GRID_BUILTIN_LAYERS.index(n)
+        elif n in semantic_layers:
+            g.kind, g.index = GRID_SEMANTIC, semantic_layers.index(n)
+        else:
+            raise ValueError("layer %r is neither a built-in nor one of the semantic layers %s" % (n, semantic_layers))
+        g.slot = slot
+    return table, names
 
 
 CAM_CELL_MAX = 65536      # EM_CAM_CELL_MAX (csrc/emap_launch.h): a cap, not a measurement -- 2.6 km at 4 cm cells, far beyond any map
@@ -846,6 +893,100 @@ class ElevationMap:
             return
         m = np.flip(np.flip(m, 0), 1)
         data[...] = m.astype(np.float32)
+
+    # ---- GridMap message output (include/emap_hip.h: emap_publish_grid_map) -----------------------------------------------------------
+    def _grid_launch(self, entries, out, order):
+        """``entries``: ``(kind, index, slot)`` per device layer; ``out``: C-contiguous float32 ``(slots, M, M)``.  At most 32 layers per
+        launch: more go in groups of 32.  The caller holds ``map_lock``."""
+        entries = [(int(k), int(i), int(sl)) for k, i, sl in entries]
+        for a in range(0, len(entries), GRID_MAX_LAYERS):
+            group = entries[a:a + GRID_MAX_LAYERS]
+            table = (EmapGridLayer * len(group))()
+            for g, (kind, index, slot) in zip(table, group):
+                g.kind, g.index, g.slot = kind, index, slot
+            self._chk(self._lib.emap_publish_grid_map(self._ctx, table, len(group), GRID_ORDERS[order], ct.c_float(float(self.center[2])),
+                                                      int(bool(self.param.use_only_above_for_upper_bound)), f32p(out), int(out.shape[0])))
+
+    def publish_grid_layers(self, entries, out, order="rows"):
+        """the layer table as it is: ``entries`` = ``(kind, index, slot)`` tuples or an ``EmapGridLayer`` array (``grid_map_descriptor``),
+        written into ``out`` (float32, C-contiguous, ``(slots, cell_n - 2, cell_n - 2)``); slots the table does not name are not written"""
+        M = self.cell_n - 2
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.ndim == 3 and out.shape[1:] == (M, M)):
+            raise ValueError("out must be a C-contiguous float32 array of shape (slots, %d, %d)" % (M, M))
+        if order not in GRID_ORDERS:
+            raise ValueError("order must be 'rows' or 'message'")
+        entries = [(e.kind, e.index, e.slot) if isinstance(e, EmapGridLayer) else tuple(e) for e in entries]
+        with self.map_lock:
+            self._grid_launch(entries, out, order)
+
+    def get_grid_map_layers(self, layers, out=None, order="rows", normal_color=False):
+        """What the wrapper's ``get_grid_map`` gathers for a publisher (elevation_mapping_wrapper.cpp:213-252), in one call: ``(names,
+        array)`` with ``array`` float32 of shape ``(len(names), cell_n - 2, cell_n - 2)``.  ``layers`` keep their order; names for which
+        ``exists_layer`` is false are dropped, as there; with ``normal_color`` (the node's ``enable_normal_color``) ``normal_x``, ``normal_y``,
+        ``normal_z`` and ``color`` are appended (a name already kept is not added twice).  ``order="rows"``: plane ``k`` is what
+        ``get_map_with_name_ref(names[k], ...)`` leaves; ``order="message"``: its transpose stored C-contiguous, i.e. the column-major
+        ``Float32MultiArray`` of ``grid_map_msgs/GridMap``.  Every built-in and semantic layer comes from ONE device launch, one copy and one
+        wait (groups of 32 beyond 32 layers); plugin layers are computed as ``get_map_with_name_ref`` computes them and put into their
+        plane on the host.  The whole call runs under one ``map_lock``."""
+        if order not in GRID_ORDERS:
+            raise ValueError("order must be 'rows' or 'message'")
+        self._require_full_map("get_grid_map_layers")
+        M = self.cell_n - 2
+        with self.map_lock:
+            names = []
+            for n in layers:
+                if n not in names and self.exists_layer(n):
+                    names.append(n)
+            if normal_color:
+                names += [n for n in GRID_NORMAL_COLOR_LAYERS if n not in names]
+            sem = self.semantic_map.layer_names if self.semantic_map is not None else []
+            plug = self.plugin_manager.layer_names if self.plugin_manager is not None else []
+            plan = []                                   # (name, device entry or None)
+            for n in names:
+                if normal_color and n in GRID_NORMAL_COLOR_LAYERS:
+                    plan.append((n, (GRID_NORMAL_COLOR, 0) if n == "color" else (GRID_BUILTIN, GRID_BUILTIN_LAYERS.index(n))))
+                elif n in GRID_BUILTIN_LAYERS[:6]:
+                    plan.append((n, (GRID_BUILTIN, GRID_BUILTIN_LAYERS.index(n))))
+                elif n in sem:
+                    plan.append((n, (GRID_SEMANTIC, sem.index(n))))
+                elif n in plug:
+                    plan.append((n, None))
+                else:                                   # (is_valid: a layer of the map that get_map_with_name_ref does not publish either)
+                    print("Layer {} is not in the map".format(n))
+            names = [n for n, _ in plan]
+            if out is None:
+                out = np.empty((len(names), M, M), np.float32)
+            elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.shape == (len(names), M, M)):
+                raise ValueError("out must be a C-contiguous float32 array of shape (%d, %d, %d)" % (len(names), M, M))
+            device = [(e[0], e[1], slot) for slot, (_, e) in enumerate(plan) if e is not None]
+            if device:
+                self._grid_launch(device, out, order)
+            for slot, (n, e) in enumerate(plan):
+                if e is None:
+                    m = np.flip(np.flip(self._stripped_layer(n), 0), 1).astype(np.float32)
+                    out[slot][...] = m.T if order == "message" else m
+        return names, out
+
+    def get_grid_map_message(self, layers, basic_layers=None, frame_id="", stamp=None, normal_color=False, out=None):
+        """A duck-typed ``grid_map_msgs/GridMap`` of ``layers`` (``types.SimpleNamespace``, no ROS import): ``info.resolution``,
+        ``info.length_x = info.length_y = map_length``, ``info.pose`` at ``(center_x, center_y, 0)`` with the identity orientation, the header
+        both as ``msg.header`` (ROS 2) and ``msg.info.header`` (ROS 1), ``layers``, ``basic_layers`` (``None``: the wrapper's rule, ``["elevation"]``
+        if it was asked for), and per layer a ``Float32MultiArray`` whose ``data`` is a float32 VIEW into one contiguous buffer filled by
+        ``get_grid_map_layers(order="message")``: column-major, ``dim[0] = column_index (M, M * M)``, ``dim[1] = row_index (M, M)``.  ``out``: a
+        buffer of the caller's to fill instead of a new one (a publisher that keeps its buffer between ticks), as in ``get_grid_map_layers``."""
+        layers = list(layers)
+        names, buf = self.get_grid_map_layers(layers, out=out, order="message", normal_color=normal_color)
+        M = self.cell_n - 2
+        ns = types.SimpleNamespace
+        header = ns(frame_id=str(frame_id), stamp=stamp, seq=0)
+        pose = ns(position=ns(x=float(self.center[0]), y=float(self.center[1]), z=0.0), orientation=ns(x=0.0, y=0.0, z=0.0, w=1.0))
+        info = ns(header=header, resolution=float(self.resolution), length_x=float(self.map_length), length_y=float(self.map_length), pose=pose)
+        flat = buf.reshape(len(names), M * M)
+        data = [ns(layout=ns(dim=[ns(label="column_index", size=M, stride=M * M), ns(label="row_index", size=M, stride=M)], data_offset=0),
+                   data=flat[k]) for k in range(len(names))]
+        if basic_layers is None:
+            basic_layers = ["elevation"] if "elevation" in layers else []
+        return ns(header=header, info=info, layers=names, basic_layers=list(basic_layers), data=data, outer_start_index=0, inner_start_index=0)
 
     def _require_full_map(self, what):
         if self._strip is not None:

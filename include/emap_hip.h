@@ -216,6 +216,31 @@ int emap_set_layer(emap_ctx* ctx, int plane, const float* host_in);
  * (cell_n-2, cell_n-2) buffer: border stripped, both axes flipped, NaN for unknown cells, +center_z for heights.
  * kind: 0 elevation, 1 variance, 2 traversability, 3 time, 4 upper_bound, 5 is_upper_bound, 6..8 normal_x/y/z */
 int emap_publish_layer(emap_ctx* ctx, int32_t kind, float center_z, int32_t use_only_above_for_upper_bound, float* host_out);
+/* GridMap message output: every device-resident layer a grid_map_msgs/GridMap publisher asks for, from ONE launch, one device-to-host
+ * copy per run of adjacent slots and one wait (the reference's node: one get_map_with_name_ref per layer, a transposing copy in
+ * gridMap.add, a host loop for the normal colour, one more copy in toMessage -- elevation_mapping_wrapper.cpp:213-252, :296-314;
+ * elevation_mapping_ros.cpp:269-301).  host_out holds host_slots planes of M * M floats, M = cell_n - 2; layer k of the table lands in
+ * plane layers[k].slot; planes the table does not name are not written (the caller fills them, e.g. with plugin layers).  Element
+ * (i, j) of a plane -- border stripped, both axes flipped: logical source cell (M - i, M - j) -- lies at
+ *   order EMAP_GRID_ROWS     i * M + j   what emap_publish_layer / get_map_with_name_ref leave in a C-order buffer
+ *   order EMAP_GRID_MESSAGE  j * M + i   the column-major Float32MultiArray of grid_map_msgs/GridMap: dim[0] = {"column_index", M, M * M},
+ *                                        dim[1] = {"row_index", M, M}, data_offset 0, start indices 0
+ * kind EMAP_GRID_BUILTIN: index = emap_publish_layer's kind 0 .. 8, the same values bit for bit (center_z and
+ * use_only_above_for_upper_bound as there).  kind EMAP_GRID_SEMANTIC: index = the semantic layer; its 32-bit words are moved as they
+ * are (colour and class layers hold bit patterns): no NaN fill, no center_z, as SemanticMap.get_map_with_name.  kind
+ * EMAP_GRID_NORMAL_COLOR (index ignored): the wrapper's addNormalColorLayer on the normal planes -- cx = (float)((nx + 1.0) / 2.0), cy
+ * likewise, cz = nz; r, g, b = (int)(c * 255.0f), truncated; the value is the float whose bits are (r << 16) | (g << 8) | b.  A
+ * component that is not finite or beyond int is undefined in the reference; here the conversion saturates and NaN gives 0.
+ * A half of a cell and a normal plane are read at most once per launch however many layers need them, and not at all if none does.
+ * Refused with EMAP_ERR_INVALID before anything is launched or copied, host_out untouched: a NULL pointer; n_layers outside 1 .. 32;
+ * an unknown kind or order; a built-in index outside 0 .. 8; a semantic index that is not configured; a slot outside [0, host_slots);
+ * a slot named twice; a row-strip context.  Returns when host_out is filled. */
+enum { EMAP_GRID_ROWS = 0, EMAP_GRID_MESSAGE = 1 };
+enum { EMAP_GRID_BUILTIN = 0, EMAP_GRID_SEMANTIC = 1, EMAP_GRID_NORMAL_COLOR = 2 };
+#define EMAP_GRID_MAX_LAYERS 32
+typedef struct emap_grid_layer { int32_t kind, index, slot; } emap_grid_layer;
+int emap_publish_grid_map(emap_ctx* ctx, const emap_grid_layer* layers, int32_t n_layers, int32_t order,
+                          float center_z, int32_t use_only_above_for_upper_bound, float* host_out, int64_t host_slots);
 /* ElevationMap.shift_map_xy / shift_map_z (EM/elevation_mapping.py:200-226): roll by (dx rows, dy cols) with
  * padding (0; variance plane initial_variance), planes 0 and 5 += dz -- as a rotation of the map's circular origin plus a pending
  * entry that later kernels replay: no cell is moved, only the entering band of the semantic layers is cleared.  Works on strips

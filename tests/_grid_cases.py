@@ -1,0 +1,128 @@
+"""What the GridMap message output tests share (tests/test_grid_cases.py on the CPU, tests/test_hip_grid_map.py on the GPU): the NumPy
+restatement of the message layout and of the normal colour, the layer lists and the start state.
+
+grid_map is absent offline: the layout (grid_map_msgs/GridMap: one column-major Float32MultiArray per layer, dim[0] "column_index",
+dim[1] "row_index") and grid_map::colorVectorToValue are restated from their published definitions; the wrapper's addNormalColorLayer
+from elevation_mapping_wrapper.cpp:296-314."""
+import numpy as np
+
+import _fixtures as fx
+from _util import make_parameter
+
+SIZES = (10, 34, 67, 100)            # cell_n: M = 8 (less than a 32 x 32 tile), 32 (one tile), 65 (one past two tiles), 98
+ORDERS = ("rows", "message")
+BUILTINS = ("elevation", "variance", "traversability", "time", "upper_bound", "is_upper_bound", "normal_x", "normal_y", "normal_z")
+HOT_ONLY = ("variance", "elevation")                                  # the hot half of a cell alone
+COLD_ONLY = ("upper_bound", "time", "is_upper_bound")                 # the cold half alone (its w mirrors is_valid)
+BOTH_HALVES = ("time", "traversability", "variance")
+SEMANTIC = ("rgb", "s1")                                              # a colour layer (bit patterns) and a feature layer
+MIXED = ("s0", "elevation", "rgb", "upper_bound", "c0", "traversability")
+NAN_AND_FINITE = ("elevation", "traversability", "upper_bound")
+POISON = 0xA5A5A5A5
+MOVE = np.array([0.12, -0.2, 0.05], np.float32)        # 3 rows, -5 columns, 5 cm: a circular origin off zero and a pending shift
+CHANNELS = ["x", "y", "z", "s0", "s1", "c0", "rgb"]
+
+
+# ---- the message layout -------------------------------------------------------------------------------------------------------------
+def message_plane(rows):
+    """the (M, M) C-contiguous array whose flat data is the message's column-major Float32MultiArray of the layer ``rows`` (what
+    get_map_with_name_ref leaves): element (i, j) at j * M + i"""
+    return np.ascontiguousarray(np.asarray(rows).T)
+
+
+def message_plane_loop(rows):
+    M = rows.shape[0]
+    flat = np.empty(M * M, rows.dtype)
+    for i in range(M):
+        for j in range(M):
+            flat[j * M + i] = rows[i, j]
+    return flat.reshape(M, M)
+
+
+def message_layout(M):
+    """(label, size, stride) of dim[0], dim[1]"""
+    return [("column_index", M, M * M), ("row_index", M, M)]
+
+
+# ---- the normal colour ----------------------------------------------------------------------------------------------------------------
+def normal_color(nx, ny, nz):
+    """addNormalColorLayer + colorVectorToValue on finite components within int: float32 arrays in, float32 bit patterns out"""
+    nx, ny, nz = (np.asarray(a, np.float32) for a in (nx, ny, nz))
+    cx = ((nx.astype(np.float64) + 1.0) / 2.0).astype(np.float32)
+    cy = ((ny.astype(np.float64) + 1.0) / 2.0).astype(np.float32)
+    r, g, b = (np.trunc(c * np.float32(255.0)).astype(np.int32) for c in (cx, cy, nz))
+    return np.ascontiguousarray((r << 16) | (g << 8) | b).astype(np.int32).view(np.float32)
+
+
+def normal_pattern(C, seed=5):
+    """(3, C, C) normals covering -1, 0, 1 and, per component, the float32 values on both sides of integer values of c * 255"""
+    rng = np.random.default_rng(seed)
+    n = rng.uniform(-1.0, 1.0, (3, C, C)).astype(np.float32)
+    ks = np.array([1, 2, 64, 127, 128, 200, 254], np.float64)
+    xy = np.float32(2.0 * ks / 255.0 - 1.0); z = np.float32(ks / 255.0)
+    for a, base in ((0, xy), (1, xy), (2, np.concatenate([z, -z]))):
+        special = np.concatenate([np.float32([-1.0, 0.0, 1.0]), base, np.nextafter(base, np.float32(2.0)), np.nextafter(base, np.float32(-2.0))]).astype(np.float32)
+        flat = n[a].reshape(-1)
+        pos = rng.permutation(flat.size)[:special.size] if flat.size >= special.size else np.arange(flat.size)
+        flat[pos] = special[:pos.size]
+    return n
+
+
+# ---- the start state ------------------------------------------------------------------------------------------------------------------
+def config():
+    from oracle import emap_oracle as eo
+    return dict(eo.YAML, enable_visibility_cleanup=True)
+
+
+def relief(p):
+    """sensor-frame heights of a gentle relief with a step under the points p (the sensor stands 1 m above the map's plane)"""
+    return (0.2 * np.sin(p[:, 0] * 3.0) + 0.1 * np.cos(p[:, 1] * 2.0) - 1.0 + 0.3 * (p[:, 0] > 0.1)).astype(np.float32)
+
+
+def semantic_frame(C, N, seed):
+    """fx.semantic_cloud on the relief, so that its points are valid at every map size and agree with the terrain frame"""
+    p = fx.semantic_cloud(C, 3 * (N // 3), seed)
+    p[:, 2] = relief(p)
+    return p
+
+
+def start(C, plugin_file=None, strip=None):
+    """a terrain frame with visibility clean-up, several update_time calls, a semantic cloud (rgb: colour; s0 s1 c0: averages), then a
+    move that shifts both axes: the circular origin is off zero, a shift is pending, the normals lie at an older origin than the cells"""
+    from elevation_mapping_cupy_amd.elevation_mapping import ElevationMap
+    p = make_parameter(config(), C)
+    p.pointcloud_channel_fusions = {"rgb": "color", "default": "average"}
+    if plugin_file is not None:
+        p.plugin_config_file = str(plugin_file)
+    m = ElevationMap(p, strip=strip)
+    if strip is not None:
+        return m
+    R, t = fx.POSES["identity"]
+    N = max(40, C * C // 2)
+    terrain = fx.cloud(C, N, 0)
+    terrain[:, 2] = relief(terrain)
+    m.input_pointcloud(terrain, ["x", "y", "z"], R, t.copy(), 0.0, 0.0)
+    for _ in range(3):
+        m.update_time()
+    m.input_pointcloud(semantic_frame(C, 2 * N, 1), CHANNELS, R, t.copy(), 0.0, 0.0)
+    m.update_time()
+    m.move_to(MOVE, np.eye(3, dtype=np.float32))
+    return m
+
+
+MIN_FILTER_YAML = """
+min_filter:
+  enable: True
+  fill_nan: False
+  is_height_layer: True
+  layer_name: "min_filter"
+  extra_params:
+    dilation_size: 1
+    iteration_n: 30
+"""
+
+
+def same_bits(a, b):
+    """elementwise: the same 32 bits, or both NaN"""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
