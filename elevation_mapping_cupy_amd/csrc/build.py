@@ -12,10 +12,11 @@ LIB = os.path.join(os.path.dirname(HERE), "libemap_hip.so")
 OBJ = os.path.join(HERE, "_obj")
 SOURCES = ["emap_kernels.hip", "emap_binned.hip", "emap_semantic.hip", "emap_api.hip", "emap_api_semantic.hip", "emap_api_plugins.hip", "emap_api_comm.hip",
            "emap_depth.hip", "emap_api_depth.hip", "emap_cloudmsg.hip", "emap_api_cloudmsg.hip", "emap_image_msg.hip", "emap_api_image_msg.hip",
-           "emap_gridmsg.hip", "emap_api_gridmsg.hip",
+           "emap_gridmsg.hip", "emap_api_gridmsg.hip", "emap_plugchain.hip", "emap_api_plugchain.hip",
            "emap_inpaint_host.hip", "emap_inpaint_ns.cpp", "emap_inpaint_fronts.hip"]      # (.cpp: host-only C++)
 HEADERS = ["emap_device.h", "emap_launch.h", "emap_camera.h", "emap_host.h", os.path.join("..", "..", "include", "emap_hip.h")]
 DEPS = SOURCES + HEADERS
+MAX_WORKERS = 16      # compilers at once: one per source, but never more than the CPUs a build may use
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
@@ -50,7 +51,7 @@ def build(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
 
-    with ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), MAX_WORKERS)) as ex:
         list(ex.map(compile_one, zip(SOURCES, objs)))
     cmd = [hipcc, "--offload-arch=gfx950", "-fno-gpu-rdc", "-shared", "-fPIC", "-Wl,--no-undefined"] + objs + ["-o", LIB]      # (a launcher declared and defined nowhere fails the build, not the first call)
     if verbose:

@@ -1,0 +1,169 @@
+// C ABI of the MI355X elevation-map fusion core, host side of the publish-time plugins on device-resident planes (kernels:
+// emap_plugchain.hip, emap_semantic.hip).  The reference keeps the plugins' outputs in PluginManager.layers on its device
+// (EM/plugins/plugin_manager.py:130, :181-236); the host route here (emap_api_plugins.hip) moves every plane over PCIe twice per plugin.
+// A chain enqueues the plugins of a publisher on the context's stream into planes the context owns and does not wait: k_grid_map
+// (emap_api_gridmsg.hip, kind EMAP_GRID_PLUGIN) reads them next to the cells, so a publisher's tick has one wait.
+#include "emap_host.h"
+#include <cstring>
+
+using namespace emap_host;
+
+namespace {
+bool full_map(const emap_ctx* ctx) { return ctx->strip.halo_rows == 0 && ctx->strip.row_count == ctx->prm.cell_n; }
+size_t plane_len(const emap_ctx* ctx) { return (size_t)ctx->prm.cell_n * ctx->prm.cell_n; }
+
+// scratch planes / counters of one op (each op of a chain has its own: two filters in one chain must not share counters)
+size_t op_planes(const emap_plugin_op& o) {
+  switch (o.type) {
+    case EMAP_PLUGIN_MIN_FILTER: case EMAP_PLUGIN_MAX_FILTER: return 5;       // orig mask, two (value, mask) pairs
+    case EMAP_PLUGIN_SMOOTH: return o.src_kind == EMAP_PLUGIN_SRC_LAYER ? 1 : 0;
+    case EMAP_PLUGIN_EROSION: return 2 + (o.src_kind == EMAP_PLUGIN_SRC_LAYER ? 1 : 0);
+    default: return 2;                                                          // ROBOT_CENTRIC: elevation, is_valid
+  }
+}
+size_t op_counters(const emap_plugin_op& o) { return o.type <= EMAP_PLUGIN_MAX_FILTER ? (size_t)o.i1 + 1 : 0; }
+
+template <class T> int grow(emap_ctx* ctx, T** buf, size_t* cap, size_t need) {
+  if (need <= *cap) return EMAP_OK;
+  CK(hipStreamSynchronize(ctx->stream));      // a chain enqueued earlier may still read the old buffer
+  if (*buf) CK(hipFree(*buf));
+  *buf = nullptr; *cap = 0;
+  CK(hipMalloc((void**)buf, sizeof(T) * need));
+  *cap = need;
+  return EMAP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int emap_plugin_planes(emap_ctx* ctx, int32_t n_planes) {
+  CKARG(ctx, "null ctx");
+  CKARG(n_planes >= 0 && n_planes <= EMAP_PLUGIN_MAX_PLANES, "emap_plugin_planes: n_planes must lie in 0 .. 32");
+  CKARG(full_map(ctx), "emap_plugin_planes: single-strip contexts only");
+  CK(hipSetDevice(ctx->device));
+  const size_t L = plane_len(ctx);
+  if (n_planes > ctx->plane_cap) {
+    float* nb = nullptr;
+    CK(hipMalloc((void**)&nb, sizeof(float) * L * n_planes));
+    hipError_t e = hipSuccess;
+    if (ctx->plane_n) e = hipMemcpyAsync(nb, ctx->plane_buf, sizeof(float) * L * ctx->plane_n, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(nb + L * ctx->plane_n, 0, sizeof(float) * L * (n_planes - ctx->plane_n), ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // (whatever read or wrote the old planes is done before they are freed)
+    if (e != hipSuccess) { hipFree(nb); CK(e); }
+    if (ctx->plane_buf) CK(hipFree(ctx->plane_buf));
+    ctx->plane_buf = nb; ctx->plane_cap = n_planes;
+  } else if (n_planes > ctx->plane_n) {
+    CK(hipMemsetAsync(ctx->plane_buf + L * ctx->plane_n, 0, sizeof(float) * L * (n_planes - ctx->plane_n), ctx->stream));
+  }
+  ctx->plane_n = n_planes;
+  return EMAP_OK;
+}
+
+int emap_plugin_plane_write(emap_ctx* ctx, int32_t plane, const float* host_in) {
+  CKARG(ctx, "null ctx");
+  CKARG(host_in, "emap_plugin_plane_write: null argument");
+  CKARG(plane >= 0 && plane < ctx->plane_n, "emap_plugin_plane_write: plane outside the reservation (emap_plugin_planes)");
+  CK(hipSetDevice(ctx->device));
+  const size_t L = plane_len(ctx);
+  CK(hipMemcpyAsync(ctx->plane_buf + L * plane, host_in, sizeof(float) * L, hipMemcpyHostToDevice, ctx->stream));
+  return EMAP_OK;
+}
+
+int emap_plugin_plane_read(emap_ctx* ctx, int32_t plane, float* host_out) {
+  CKARG(ctx, "null ctx");
+  CKARG(host_out, "emap_plugin_plane_read: null argument");
+  CKARG(plane >= 0 && plane < ctx->plane_n, "emap_plugin_plane_read: plane outside the reservation (emap_plugin_planes)");
+  CK(hipSetDevice(ctx->device));
+  const size_t L = plane_len(ctx);
+  CK(hipMemcpyAsync(host_out, ctx->plane_buf + L * plane, sizeof(float) * L, hipMemcpyDeviceToHost, ctx->stream));
+  CK(hipStreamSynchronize(ctx->stream));
+  return EMAP_OK;
+}
+
+int emap_plugin_chain(emap_ctx* ctx, const emap_plugin_op* ops, int32_t n_ops, const float* rotation9) {
+  CKARG(ctx, "null ctx");
+  // everything is refused BEFORE anything is enqueued: the planes and the map stay as they are
+  CKARG(ops, "emap_plugin_chain: null argument");
+  CKARG(n_ops >= 1 && n_ops <= EMAP_PLUGIN_MAX_OPS, "emap_plugin_chain: n_ops must lie in 1 .. 32");
+  CKARG(full_map(ctx), "emap_plugin_chain: single-strip contexts only");
+  size_t planes = 0, counters = 0;
+  for (int k = 0; k < n_ops; ++k) {
+    const emap_plugin_op& o = ops[k];
+    CKARG(o.type >= EMAP_PLUGIN_MIN_FILTER && o.type <= EMAP_PLUGIN_ROBOT_CENTRIC, "emap_plugin_chain: unknown op type");
+    CKARG(o.dst_plane >= 0 && o.dst_plane < ctx->plane_n, "emap_plugin_chain: dst_plane outside the reservation (emap_plugin_planes)");
+    const bool reads_src = o.type == EMAP_PLUGIN_SMOOTH || o.type == EMAP_PLUGIN_EROSION;
+    if (reads_src) {
+      CKARG(o.src_kind == EMAP_PLUGIN_SRC_LAYER || o.src_kind == EMAP_PLUGIN_SRC_PLANE, "emap_plugin_chain: src_kind must be 0 (map layer) or 1 (resident plane)");
+      CKARG(o.src_kind != EMAP_PLUGIN_SRC_LAYER || (o.src_index >= 0 && o.src_index <= 6), "emap_plugin_chain: a map layer index must lie in 0 .. 6");
+      CKARG(o.src_kind != EMAP_PLUGIN_SRC_PLANE || (o.src_index >= 0 && o.src_index < ctx->plane_n), "emap_plugin_chain: source plane outside the reservation (emap_plugin_planes)");
+    }
+    if (o.type == EMAP_PLUGIN_SMOOTH)
+      CKARG(!(o.src_kind == EMAP_PLUGIN_SRC_PLANE && o.src_index == o.dst_plane), "emap_plugin_chain: a smooth filter cannot run in place (source plane = dst_plane)");
+    if (o.type <= EMAP_PLUGIN_MAX_FILTER)
+      CKARG(o.i0 >= 0 && o.i0 <= 32 && o.i1 >= 0 && o.i1 <= 4096, "emap_plugin_chain: bad filter size / iteration count");
+    if (o.type == EMAP_PLUGIN_EROSION)
+      CKARG(o.i0 >= 1 && o.i0 <= 63 && o.i1 >= 0 && o.i1 <= 256, "emap_plugin_chain: bad erosion kernel size / iteration count");
+    const int allowed = o.type == EMAP_PLUGIN_EROSION ? EMAP_PLUGIN_REVERSE : (o.type == EMAP_PLUGIN_ROBOT_CENTRIC ? EMAP_PLUGIN_THRESHOLD : 0);
+    CKARG((o.flags & ~allowed) == 0, "emap_plugin_chain: a flag the op does not know");
+    CKARG(o.type != EMAP_PLUGIN_ROBOT_CENTRIC || rotation9, "emap_plugin_chain: null argument (rotation9)");
+    planes += op_planes(o); counters += op_counters(o);
+  }
+
+  SF_CHECK();
+  CK(hipSetDevice(ctx->device));
+  FLUSH();
+  const int C = ctx->prm.cell_n; const size_t L = plane_len(ctx), bytes = L * sizeof(float);
+  int rc = grow(ctx, &ctx->chain_buf, &ctx->chain_cap, planes * L); if (rc) return rc;
+  rc = grow(ctx, &ctx->chain_cnt, &ctx->chain_cnt_cap, counters); if (rc) return rc;
+  rc = grow(ctx, &ctx->chain_red, &ctx->chain_red_cap, (size_t)n_ops * EM_RANGE_FLOATS); if (rc) return rc;
+  if (counters) CK(hipMemsetAsync(ctx->chain_cnt, 0, sizeof(unsigned int) * counters, ctx->stream));
+
+  float* buf = ctx->chain_buf; unsigned int* cnt = ctx->chain_cnt;
+  for (int k = 0; k < n_ops; ++k) {
+    const emap_plugin_op& o = ops[k];
+    float* dst = ctx->plane_buf + L * o.dst_plane;
+    float* scr = buf; buf += op_planes(o) * L;
+    const float* src = nullptr;      // SMOOTH / EROSION: the layer de-interleaved into the op's last scratch plane, or the resident plane
+    if (o.type == EMAP_PLUGIN_SMOOTH || o.type == EMAP_PLUGIN_EROSION) {
+      if (o.src_kind == EMAP_PLUGIN_SRC_LAYER) {
+        float* own = scr + (op_planes(o) - 1) * L;
+        launch_get_plane(ctx->stream, ctx->kp, ctx->cells, o.src_index, own);
+        src = own;
+      } else src = ctx->plane_buf + L * o.src_index;
+    }
+    switch (o.type) {
+      case EMAP_PLUGIN_MIN_FILTER: case EMAP_PLUGIN_MAX_FILTER: {
+        float *orig = scr, *v0 = scr + L, *m0 = scr + 2 * L, *v1 = scr + 3 * L, *m1 = scr + 4 * L;
+        launch_get_plane(ctx->stream, ctx->kp, ctx->cells, 2, orig);
+        launch_get_plane(ctx->stream, ctx->kp, ctx->cells, 0, v0);
+        CK(hipMemcpyAsync(m0, orig, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        for (int it = 0; it < o.i1; ++it)
+          launch_min_sweep(ctx->stream, C, o.i0, orig, (it & 1) ? v1 : v0, (it & 1) ? m1 : m0, (it & 1) ? v0 : v1, (it & 1) ? m0 : m1,
+                           it > 0 ? cnt + (it - 1) : nullptr, cnt + it, o.type == EMAP_PLUGIN_MAX_FILTER);
+        launch_mask_nan(ctx->stream, (long)L, (o.i1 & 1) ? v1 : v0, (o.i1 & 1) ? m1 : m0, dst);
+        cnt += op_counters(o);
+      } break;
+      case EMAP_PLUGIN_SMOOTH:
+        launch_smooth2(ctx->stream, C, src, dst);
+        break;
+      case EMAP_PLUGIN_EROSION: {
+        float* red = ctx->chain_red + (size_t)k * EM_RANGE_FLOATS;      // [0 .. 3): lo, hi, has-NaN; behind them the partial triples
+        const int rev = (o.flags & EMAP_PLUGIN_REVERSE) ? 1 : 0;
+        float *a = scr, *b = scr + L;
+        launch_range(ctx->stream, (long)L, src, rev, red + 4, red);
+        launch_quantise(ctx->stream, (long)L, src, rev, red, a);
+        for (int it = 0; it < o.i1; ++it) { launch_erode(ctx->stream, C, o.i0, a, b); float* t = a; a = b; b = t; }
+        launch_dequantise(ctx->stream, (long)L, a, src, rev, red, dst);      // (src may be dst: element i is read before it is written, by one thread)
+      } break;
+      default:
+        launch_get_plane(ctx->stream, ctx->kp, ctx->cells, 0, scr);
+        launch_get_plane(ctx->stream, ctx->kp, ctx->cells, 2, scr + L);
+        launch_robot_centric(ctx->stream, C, (float)ctx->prm.resolution, rotation9, (o.flags & EMAP_PLUGIN_THRESHOLD) ? 1 : 0, o.f0, scr, scr + L, dst);
+        break;
+    }
+    CK(hipGetLastError());
+  }
+  return EMAP_OK;
+}
+
+}  // extern "C"

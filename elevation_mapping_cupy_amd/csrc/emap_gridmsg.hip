@@ -78,6 +78,19 @@ __global__ __launch_bounds__(EM_BLOCK) void k_grid_map(KP P, Cells cells, GridAr
     } else if (kind == 2) {
 #pragma unroll
       for (int k = 0; k < NK; ++k) v[k] = normal_color(nrm[0][k], nrm[1][k], nrm[2][k]);
+    } else if (kind == 3) {                                    // resident plugin plane: LOGICAL cell (no circular origin), then _publish's order
+      const float* __restrict__ pp = A.plug + (long)index * C * C + (long)rr[0] * C + c;      // (rr[0] = 1 for a thread below the map: the pointer stays inside the plane)
+      const int fl = A.flags[l];
+#pragma unroll
+      for (int k = 0; k < NK; ++k) v[k] = in[k] ? pp[-(T / NK) * k * C] : 0.f;      // row M - i: (T / NK) k rows above the thread's first (cell_n <= 46340: an int)
+      if (fl & EM_GRID_FILL_NAN) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) if (!((have_hot ? hot[k].z : cold[k].w) > 0.5f)) v[k] = __uint_as_float(0x7fc00000u);
+      }
+      if (fl & EM_GRID_ADD_Z) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) v[k] = v[k] + A.center_z;
+      }
     } else if (index >= 6) {
 #pragma unroll
       for (int k = 0; k < NK; ++k) v[k] = index == 6 ? nrm[0][k] : (index == 7 ? nrm[1][k] : nrm[2][k]);

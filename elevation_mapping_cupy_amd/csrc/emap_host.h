@@ -148,6 +148,11 @@ struct emap_ctx {
   unsigned char* imsg_pin[2]; size_t imsg_pin_cap[2]; hipEvent_t imsg_ev[2]; bool imsg_ev_on[2]; int imsg_slot;   // imsg_ev: the slot's H2D copies are done
   // GridMap message output (emap_api_gridmsg.hip): the planes k_grid_map writes, grown on demand (`scratch` stays the single plane it is)
   float* grid_buf; size_t grid_cap;                           // floats
+  // publish-time plugins on resident planes (emap_api_plugchain.hip): plane_n planes of cell_n x cell_n floats, each the RAW output of a
+  // plugin (logical order, border included) -- what PluginManager.layers[k] holds; the scratch planes, counters and reduction words of a
+  // chain, one set per op, grown on demand
+  float* plane_buf; int plane_n, plane_cap;
+  float* chain_buf; size_t chain_cap; unsigned int* chain_cnt; size_t chain_cnt_cap; float* chain_red; size_t chain_red_cap;   // floats / words
   // frame state
   bool use_override; double sum_override; unsigned int cnt_override;
   bool committed;

@@ -47,11 +47,17 @@ struct ImgMsgArgs { const unsigned char* msg; int H, W, step, elem, esize, n_cha
 // plane pos[l] of `out` (planes of M * M floats, M = C - 2; the host packs the caller's slots in ascending order), element (i, j) at
 // i * M + j (order 0) or j * M + i (order 1: the message's column-major Float32MultiArray).  kind / index: emap_hip.h (EMAP_GRID_*).
 // need: what the table reads of a cell -- bit 0 the hot half, 1 the cold half, 2 .. 4 the normal planes x, y, z (set by grid_need).
+// kind 3: resident plugin plane `index` of `plug` (planes of C * C floats in LOGICAL order: no circular origin), read at the logical source
+// cell; flags[l] bit 0: NaN where the cell is not valid, bit 1: + center_z (the plugin's fill_nan / is_height_layer).
 #define EM_GRID_MAX_LAYERS 32
 #define EM_GRID_TILE 32
+#define EM_GRID_FILL_NAN 1
+#define EM_GRID_ADD_Z 2
 struct GridArgs { int n, order, only_above, need; float center_z; int pad_; long plane, sem_plane; const float* normal; const float* sem; float* out;
-                  unsigned char kind[EM_GRID_MAX_LAYERS], pos[EM_GRID_MAX_LAYERS]; int index[EM_GRID_MAX_LAYERS]; };
+                  unsigned char kind[EM_GRID_MAX_LAYERS], pos[EM_GRID_MAX_LAYERS]; int index[EM_GRID_MAX_LAYERS];
+                  const float* plug; unsigned char flags[EM_GRID_MAX_LAYERS]; };
 static inline int grid_need(int kind, int index) {
+  if (kind == 3) return 0;                                              // plugin plane: its own plane (FILL_NAN: the host adds a half that carries valid)
   if (kind == 1) return 0;                                              // semantic: its own plane
   if (kind == 2) return 4 | 8 | 16;                                     // normal colour
   if (index >= 6) return 4 << (index - 6);                              // normal_x / y / z
@@ -136,3 +142,12 @@ void launch_image_frame(hipStream_t, const KP&, const CamArgs&, Cells, float*, u
 
 // GridMap message output (emap_gridmsg.hip): whole-map contexts only (the caller checks)
 void launch_grid_map(hipStream_t, const KP&, Cells, const GridArgs&);
+
+// publish-time plugins on resident planes (emap_plugchain.hip); EM_RANGE_FLOATS: scratch of launch_range (256 partial triples + the result)
+#define EM_RANGE_FLOATS (3 * 256 + 4)
+void launch_mask_nan(hipStream_t, long, const float*, const float*, float*);
+void launch_smooth2(hipStream_t, int, const float*, float*);
+void launch_range(hipStream_t, long, const float*, int, float*, float*);
+void launch_quantise(hipStream_t, long, const float*, int, const float*, float*);
+void launch_dequantise(hipStream_t, long, const float*, const float*, int, const float*, float*);
+void launch_robot_centric(hipStream_t, int, float, const float*, int, float, const float*, const float*, float*);

@@ -16,9 +16,10 @@ from typing import List
 import numpy as np
 
 from . import _lib
-from ._lib import (EmapCloudMsgDesc, EmapDepthDesc, EmapError, EmapGridLayer, EmapImageMsgDesc, EmapImageSpec, EmapParams, EmapStats, EmapStrip,
-                   GRID_BUILTIN, GRID_MAX_LAYERS, GRID_NORMAL_COLOR, GRID_ORDERS, GRID_SEMANTIC, PLANES, f32p)
+from ._lib import (EmapCloudMsgDesc, EmapDepthDesc, EmapError, EmapGridLayer, EmapGridLayerEx, EmapImageMsgDesc, EmapImageSpec, EmapParams, EmapStats, EmapStrip,
+                   GRID_ADD_Z, GRID_BUILTIN, GRID_FILL_NAN, GRID_MAX_LAYERS, GRID_NORMAL_COLOR, GRID_ORDERS, GRID_PLUGIN, GRID_SEMANTIC, PLANES, f32p)
 from .parameter import Parameter
+from .plugins.plugin_manager import plugin_chain_plan
 
 
 def _shoelace_area(xy):
@@ -334,6 +335,7 @@ class ElevationMap:
         # managers are optional layers on top of the hot path (built lazily; see semantic_map / plugins)
         self.semantic_map = None
         self.plugin_manager = None
+        self._last_plugin_route = {}
         from .semantic_map import SemanticMap
         self.semantic_map = SemanticMap(self.param, self)
         # plugins (reference :110-113): same YAML format; a missing file just means "no plugins"
@@ -896,28 +898,48 @@ class ElevationMap:
 
     # ---- GridMap message output (include/emap_hip.h: emap_publish_grid_map) -----------------------------------------------------------
     def _grid_launch(self, entries, out, order):
-        """``entries``: ``(kind, index, slot)`` per device layer; ``out``: C-contiguous float32 ``(slots, M, M)``.  At most 32 layers per
-        launch: more go in groups of 32.  The caller holds ``map_lock``."""
-        entries = [(int(k), int(i), int(sl)) for k, i, sl in entries]
+        """``entries``: ``(kind, index, slot[, flags])`` per device layer; ``out``: C-contiguous float32 ``(slots, M, M)``.  At most 32 layers
+        per launch: more go in groups of 32.  The caller holds ``map_lock``."""
+        entries = [tuple(int(x) for x in e) + (0,) * (4 - len(e)) for e in entries]
         for a in range(0, len(entries), GRID_MAX_LAYERS):
             group = entries[a:a + GRID_MAX_LAYERS]
-            table = (EmapGridLayer * len(group))()
-            for g, (kind, index, slot) in zip(table, group):
-                g.kind, g.index, g.slot = kind, index, slot
-            self._chk(self._lib.emap_publish_grid_map(self._ctx, table, len(group), GRID_ORDERS[order], ct.c_float(float(self.center[2])),
-                                                      int(bool(self.param.use_only_above_for_upper_bound)), f32p(out), int(out.shape[0])))
+            table = (EmapGridLayerEx * len(group))()
+            for g, (kind, index, slot, flags) in zip(table, group):
+                g.kind, g.index, g.slot, g.flags = kind, index, slot, flags
+            self._chk(self._lib.emap_publish_grid_map_ex(self._ctx, table, len(group), GRID_ORDERS[order], ct.c_float(float(self.center[2])),
+                                                         int(bool(self.param.use_only_above_for_upper_bound)), f32p(out), int(out.shape[0])))
 
     def publish_grid_layers(self, entries, out, order="rows"):
-        """the layer table as it is: ``entries`` = ``(kind, index, slot)`` tuples or an ``EmapGridLayer`` array (``grid_map_descriptor``),
-        written into ``out`` (float32, C-contiguous, ``(slots, cell_n - 2, cell_n - 2)``); slots the table does not name are not written"""
+        """the layer table as it is: ``entries`` = ``(kind, index, slot)`` or ``(kind, index, slot, flags)`` tuples or an ``EmapGridLayer`` /
+        ``EmapGridLayerEx`` array (``grid_map_descriptor``), written into ``out`` (float32, C-contiguous, ``(slots, cell_n - 2, cell_n - 2)``);
+        slots the table does not name are not written.  Kind ``GRID_PLUGIN``: ``index`` = a resident plugin plane as an ``emap_plugin_chain``
+        left it, ``flags`` = ``GRID_FILL_NAN | GRID_ADD_Z``."""
         M = self.cell_n - 2
         if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.ndim == 3 and out.shape[1:] == (M, M)):
             raise ValueError("out must be a C-contiguous float32 array of shape (slots, %d, %d)" % (M, M))
         if order not in GRID_ORDERS:
             raise ValueError("order must be 'rows' or 'message'")
-        entries = [(e.kind, e.index, e.slot) if isinstance(e, EmapGridLayer) else tuple(e) for e in entries]
+        entries = [(e.kind, e.index, e.slot, e.flags) if isinstance(e, EmapGridLayerEx) else (e.kind, e.index, e.slot) if isinstance(e, EmapGridLayer)
+                   else tuple(e) for e in entries]
+        if any(len(e) not in (3, 4) for e in entries):
+            raise ValueError("an entry is (kind, index, slot) or (kind, index, slot, flags)")
         with self.map_lock:
             self._grid_launch(entries, out, order)
+
+    @property
+    def last_plugin_route(self):
+        """``{plugin layer: "device" | "host"}`` of the last ``get_grid_map_layers`` / ``get_grid_map_message`` call: computed by an op of the
+        plugin chain into a resident plane, or by the plugin's host route"""
+        return dict(self._last_plugin_route)
+
+    def _plugin_host_step(self, name):
+        """the host route of one plugin, as ``_stripped_layer`` runs it"""
+        sem = self.semantic_map
+        self.plugin_manager.update_with_name(
+            name, LazyPlanes(7, self.get_layer_raw, device_map=self), self.layer_names,
+            LazyPlanes(len(sem.layer_names), sem._layer, rows=self.rows, cols=self.cell_n) if sem is not None else None,
+            self.semantic_map.layer_names if self.semantic_map is not None else [],
+            self.base_rotation, self.semantic_map.elements_to_shift if self.semantic_map is not None else {})
 
     def get_grid_map_layers(self, layers, out=None, order="rows", normal_color=False):
         """What the wrapper's ``get_grid_map`` gathers for a publisher (elevation_mapping_wrapper.cpp:213-252), in one call: ``(names,
@@ -925,9 +947,15 @@ class ElevationMap:
         ``exists_layer`` is false are dropped, as there; with ``normal_color`` (the node's ``enable_normal_color``) ``normal_x``, ``normal_y``,
         ``normal_z`` and ``color`` are appended (a name already kept is not added twice).  ``order="rows"``: plane ``k`` is what
         ``get_map_with_name_ref(names[k], ...)`` leaves; ``order="message"``: its transpose stored C-contiguous, i.e. the column-major
-        ``Float32MultiArray`` of ``grid_map_msgs/GridMap``.  Every built-in and semantic layer comes from ONE device launch, one copy and one
-        wait (groups of 32 beyond 32 layers); plugin layers are computed as ``get_map_with_name_ref`` computes them and put into their
-        plane on the host.  The whole call runs under one ``map_lock``."""
+        ``Float32MultiArray`` of ``grid_map_msgs/GridMap``.
+
+        Plugin layers are computed in list order, as one ``get_map_with_name_ref`` per layer computes them.  A plugin that describes itself
+        as a device op (``PluginBase.device_op``: MinFilter, MaxFilter, SmoothFilter, Erosion, RobotCentricElevation) joins a chain of launches
+        that is enqueued without a wait and leaves its output in a resident plane (``plugins/plugin_manager.py``); the others (Inpainting, the
+        semantic plugins) take their host route and put their plane into ``array`` on the host.  Then ONE device launch writes every
+        built-in, semantic and resident plugin layer, with one copy and one wait (groups of 32 beyond 32 layers).  ``last_plugin_route`` tells
+        which route each plugin layer took; ``EMAP_PLUGIN_RESIDENT=0`` in the environment sends every plugin through its host route.  The
+        whole call runs under one ``map_lock``."""
         if order not in GRID_ORDERS:
             raise ValueError("order must be 'rows' or 'message'")
         self._require_full_map("get_grid_map_layers")
@@ -940,7 +968,8 @@ class ElevationMap:
             if normal_color:
                 names += [n for n in GRID_NORMAL_COLOR_LAYERS if n not in names]
             sem = self.semantic_map.layer_names if self.semantic_map is not None else []
-            plug = self.plugin_manager.layer_names if self.plugin_manager is not None else []
+            pm = self.plugin_manager
+            plug = pm.layer_names if pm is not None else []
             plan = []                                   # (name, device entry or None)
             for n in names:
                 if normal_color and n in GRID_NORMAL_COLOR_LAYERS:
@@ -958,13 +987,29 @@ class ElevationMap:
                 out = np.empty((len(names), M, M), np.float32)
             elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.shape == (len(names), M, M)):
                 raise ValueError("out must be a C-contiguous float32 array of shape (%d, %d, %d)" % (len(names), M, M))
-            device = [(e[0], e[1], slot) for slot, (_, e) in enumerate(plan) if e is not None]
+            slot_of = {n: slot for slot, (n, _) in enumerate(plan)}
+
+            def host_step(n):                           # the plugin's host route, then _publish, the flips and the layout on the host
+                self._plugin_host_step(n)
+                p = pm.get_param_with_name(n)
+                m = self._publish(np.asarray(pm.host_layer(n)), p.fill_nan, p.is_height_layer, self.get_layer_raw(2))
+                m = np.flip(np.flip(m, 0), 1).astype(np.float32)
+                out[slot_of[n]][...] = m.T if order == "message" else m
+
+            self._last_plugin_route = {}
+            if pm is not None and any(e is None for _, e in plan):
+                steps = plugin_chain_plan([n for n, e in plan if e is None], pm.plugins, plug, self.layer_names, sem,
+                                          resident=os.environ.get("EMAP_PLUGIN_RESIDENT", "1") != "0")
+                self._last_plugin_route = pm.run_plan(steps, host_step, self.base_rotation)
+            device = []
+            for slot, (n, e) in enumerate(plan):
+                if e is not None:
+                    device.append((e[0], e[1], slot, 0))
+                elif self._last_plugin_route.get(n) == "device":
+                    p = pm.get_param_with_name(n)
+                    device.append((GRID_PLUGIN, plug.index(n), slot, (GRID_FILL_NAN if p.fill_nan else 0) | (GRID_ADD_Z if p.is_height_layer else 0)))
             if device:
                 self._grid_launch(device, out, order)
-            for slot, (n, e) in enumerate(plan):
-                if e is None:
-                    m = np.flip(np.flip(self._stripped_layer(n), 0), 1).astype(np.float32)
-                    out[slot][...] = m.T if order == "message" else m
         return names, out
 
     def get_grid_map_message(self, layers, basic_layers=None, frame_id="", stamp=None, normal_color=False, out=None):
@@ -1020,13 +1065,8 @@ class ElevationMap:
         if self.semantic_map is not None and name in self.semantic_map.layer_names:
             return self.semantic_map.get_map_with_name(name)
         if self.plugin_manager is not None and name in self.plugin_manager.layer_names:
-            sem = self.semantic_map
-            self.plugin_manager.update_with_name(
-                name, LazyPlanes(7, self.get_layer_raw, device_map=self), self.layer_names,
-                LazyPlanes(len(sem.layer_names), sem._layer, rows=self.rows, cols=self.cell_n) if sem is not None else None,
-                self.semantic_map.layer_names if self.semantic_map is not None else [],
-                self.base_rotation, self.semantic_map.elements_to_shift if self.semantic_map is not None else {})
-            m = self.plugin_manager.get_map_with_name(name)
+            self._plugin_host_step(name)
+            m = self.plugin_manager.host_layer(name)
             p = self.plugin_manager.get_param_with_name(name)
             return self._publish(np.asarray(m), p.fill_nan, p.is_height_layer, self.get_layer_raw(2))
         return None

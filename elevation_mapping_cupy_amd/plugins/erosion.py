@@ -8,7 +8,7 @@ from typing import List
 
 import numpy as np
 
-from .._lib import f32p
+from .._lib import PLUGIN_REVERSE, f32p
 from .plugin_manager import PluginBase
 
 
@@ -22,6 +22,25 @@ class Erosion(PluginBase):
         self.reverse = bool(reverse)
         self.default_layer_name = default_layer_name
         self.emap = emap
+
+    def _input_name(self, layer_names, plugin_layer_names, semantic_layer_names):
+        """the first of input_layer_name, default_layer_name, "traversability" that get_layer_data finds"""
+        for name in (self.input_layer_name, self.default_layer_name, "traversability"):
+            if name in layer_names or name in plugin_layer_names or name in semantic_layer_names:
+                return name
+        return None
+
+    def device_op(self, layer_names, plugin_layer_names, semantic_layer_names):
+        name = self._input_name(layer_names, plugin_layer_names, semantic_layer_names)
+        if name is None or name != self.input_layer_name:            # (a fallback prints on the host route: leave it there)
+            return None
+        src = self.device_source(name, layer_names, plugin_layer_names)
+        if src is None or not (1 <= self.kernel_size <= 63 and 0 <= self.iterations <= 256):
+            return None
+        return dict(type="erosion", src=src, i0=self.kernel_size, i1=self.iterations, flags=PLUGIN_REVERSE if self.reverse else 0)
+
+    def plugin_inputs(self, plugin_layer_names):
+        return tuple(n for n in dict.fromkeys((self.input_layer_name, self.default_layer_name, "traversability")) if n in plugin_layer_names)
 
     def __call__(self, elevation_map: np.ndarray, layer_names: List[str], plugin_layers: np.ndarray, plugin_layer_names: List[str],
                  semantic_map: np.ndarray, semantic_layer_names: List[str], *args) -> np.ndarray:

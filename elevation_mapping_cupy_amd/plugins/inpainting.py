@@ -42,6 +42,9 @@ class Inpainting(PluginBase):
         self.fronts_run = 0
         self._ip = None                            # emap_inpainter of method "telea_fronts" (created on first use)
 
+    def plugin_inputs(self, plugin_layer_names):
+        return ()                                  # elevation and is_valid of the map only: no resident plane has to come back for it
+
     def __call__(self, elevation_map: np.ndarray, layer_names: List[str], plugin_layers: np.ndarray,
                  plugin_layer_names: List[str], *args) -> np.ndarray:
         known = np.ascontiguousarray(np.asarray(elevation_map[2]) >= 0.5)

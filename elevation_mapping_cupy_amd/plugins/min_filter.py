@@ -18,7 +18,15 @@ class MinFilter(PluginBase):
         self.dilation_size = int(dilation_size)
         self.width = self.height = cell_n
         self.emap = emap
-        self.sweeps_run = 0
+        self.sweeps_run = 0                # sweeps the last host-route call ran; None after the device route, which does not wait for its counters
+
+    def device_op(self, layer_names, plugin_layer_names, semantic_layer_names):
+        if not (0 <= self.dilation_size <= 32 and 0 <= self.iteration_n <= 4096):
+            return None
+        return dict(type="min_filter", src=None, i0=self.dilation_size, i1=self.iteration_n)
+
+    def plugin_inputs(self, plugin_layer_names):
+        return ()
 
     def __call__(self, elevation_map: np.ndarray, layer_names: List[str], plugin_layers: np.ndarray,
                  plugin_layer_names: List[str], *args) -> np.ndarray:

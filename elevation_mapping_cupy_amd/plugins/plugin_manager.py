@@ -2,7 +2,13 @@
 (reference EM/plugins/plugin_manager.py:15-260): YAML keys ``enable, fill_nan, is_height_layer, layer_name,
 extra_params[, type]``, discovery = first ``PluginBase`` subclass of module ``plugins.<type>``, call arity dispatch
 (5/7/8/9 parameters).  Arrays are NumPy (host copies of device layers); the manager injects ``emap`` (the owning
-``ElevationMap``) into plugins that accept it so that they can run their arithmetic on the device."""
+``ElevationMap``) into plugins that accept it so that they can run their arithmetic on the device.
+
+Resident planes.  A plugin may also describe itself as an op of ``emap_plugin_chain`` (``PluginBase.device_op``): its output then stays in
+a plane the context owns, next plugins and the GridMap launch read it there, and nothing crosses PCIe (``ElevationMap.get_grid_map_layers``).
+``PluginManager`` keeps the host array and the planes coherent: per layer it knows which side is newer, downloads a device-newer plane
+before the host looks at it (``layers``, ``get_map_with_name``; before a host plugin only the layers its ``plugin_inputs`` names) and
+uploads a host-newer layer before a device op reads it."""
 from __future__ import annotations
 
 import importlib
@@ -13,8 +19,13 @@ from dataclasses import dataclass
 from inspect import signature
 from typing import Dict, List, Optional
 
+import ctypes as ct
+
 import numpy as np
 import yaml
+
+from .._lib import (PLUGIN_MAX_OPS, PLUGIN_MAX_PLANES, PLUGIN_OPS, PLUGIN_REVERSE, PLUGIN_SRC_LAYER, PLUGIN_SRC_PLANE, PLUGIN_THRESHOLD, EmapPluginOp,
+                    f32p)
 
 
 @dataclass
@@ -35,6 +46,26 @@ class PluginBase(ABC):
         6 is_upper_bound; return a (cell_n, cell_n) array."""
         pass
 
+    def device_op(self, layer_names, plugin_layer_names, semantic_layer_names):
+        """This plugin as an op of ``emap_plugin_chain`` (include/emap_hip.h), or ``None`` when this configuration cannot run on resident
+        planes: ``dict(type=<key of _lib.PLUGIN_OPS>, src=None | ("layer", i) | ("plane", k), i0=0, i1=0, flags=0, f0=0.0)`` with ``i`` the
+        index in ``layer_names`` and ``k`` the index in ``plugin_layer_names``.  The op must leave, bit for bit, what ``__call__`` returns."""
+        return None
+
+    def plugin_inputs(self, plugin_layer_names):
+        """names of the plugin layers ``__call__`` reads; ``None``: unknown, i.e. all of them"""
+        return None
+
+    @staticmethod
+    def device_source(name, layer_names, plugin_layer_names):
+        """``src`` of ``device_op`` for the input layer ``name``: a RAW map layer or a plugin layer; ``None`` for anything else (a semantic
+        layer is not a device source)"""
+        if name in layer_names:
+            return ("layer", layer_names.index(name)) if layer_names.index(name) <= 6 else None
+        if name in plugin_layer_names:
+            return ("plane", plugin_layer_names.index(name))
+        return None
+
     def get_layer_data(self, elevation_map, layer_names, plugin_layers, plugin_layer_names, semantic_map,
                        semantic_layer_names, name: str) -> Optional[np.ndarray]:
         if name in layer_names:
@@ -47,6 +78,36 @@ class PluginBase(ABC):
         return None
 
 
+def plugin_chain_plan(names, plugins, plugin_layer_names, layer_names, semantic_layer_names=(), resident=True):
+    """How the plugin layers ``names`` (in this order) are computed; needs no context.  ``plugins[k]`` is the plugin behind
+    ``plugin_layer_names[k]``.  Returns a list of steps in the order of ``names``: ``("device", name, op)`` -- ``op`` a dict with the fields of
+    ``struct emap_plugin_op`` (``type, dst_plane, src_kind, src_index, i0, i1, flags, f0``; plane k = plugin layer k) -- or ``("host", name)``
+    for a plugin without ``device_op``, a configuration its ``device_op`` declines (``None``), an op that would read its own plane, a layer
+    beyond the 32 planes (``PLUGIN_MAX_PLANES``), or everything with ``resident=False``.  Names that are no plugin layer are left out."""
+    plugin_layer_names, layer_names, semantic_layer_names = list(plugin_layer_names), list(layer_names), list(semantic_layer_names)
+    steps = []
+    for n in names:
+        if n not in plugin_layer_names:
+            continue
+        k = plugin_layer_names.index(n)
+        d = None
+        if resident and k < PLUGIN_MAX_PLANES and k < len(plugins):
+            d = plugins[k].device_op(layer_names, plugin_layer_names, semantic_layer_names)
+        if d is not None:
+            src = d.get("src")
+            if src is not None and (src[0] not in ("layer", "plane") or (src[0] == "plane" and (src[1] == k or src[1] >= PLUGIN_MAX_PLANES))):
+                d = None
+        if d is None:
+            steps.append(("host", n))
+            continue
+        src = d.get("src")
+        steps.append(("device", n, dict(type=PLUGIN_OPS[d["type"]], dst_plane=k,
+                                        src_kind=PLUGIN_SRC_PLANE if src is not None and src[0] == "plane" else PLUGIN_SRC_LAYER,
+                                        src_index=int(src[1]) if src is not None else 0, i0=int(d.get("i0", 0)), i1=int(d.get("i1", 0)),
+                                        flags=int(d.get("flags", 0)), f0=float(d.get("f0", 0.0)))))
+    return steps
+
+
 class PluginManager(object):
     def __init__(self, cell_n: int, emap=None, package: str = "elevation_mapping_cupy_amd.plugins"):
         self.cell_n = cell_n
@@ -54,9 +115,109 @@ class PluginManager(object):
         self.package = package
         self.plugin_params: List[PluginParams] = []
         self.plugins = []
+        self._reserved = 0                 # resident planes the context holds (emap_plugin_planes)
         self.layers = np.zeros((0, cell_n, cell_n), np.float32)
         self.layer_names: List[str] = []
         self.plugin_names: List[str] = []
+
+    # ---- the host array and the resident planes ---------------------------------------------------------------------------------------
+    # _newer[k]: "host" (the host array holds what the plane does not), "device" (the other way round) or None (the same on both sides)
+    @property
+    def layers(self):
+        """``(n_plugins, cell_n, cell_n)`` float32 on the host.  Planes that are newer on the device are downloaded first, and every plane
+        counts as newer on the host afterwards: the caller may write into the array in place, as into the reference's, and the next
+        device op that reads a layer uploads it.  (``host_layer`` and ``get_param_with_name`` are the read-only ways.)  The property
+        talks to the device: outside ``ElevationMap``'s own methods, hold its ``map_lock`` around it like around any other map access."""
+        self._download(range(len(self._newer)))
+        self._newer = ["host"] * len(self._newer)
+        return self._host
+
+    @layers.setter
+    def layers(self, value):
+        self._host = value
+        # planes the context has never held start as zero there, as this array does in init(); anything else has to be uploaded before use
+        fresh = self._reserved == 0 and not np.any(value)
+        self._newer = [None if fresh else "host"] * len(value)
+
+    def _call(self, fn, *args):
+        self.emap._chk(getattr(self.emap._lib, fn)(self.emap._ctx, *args))
+
+    def _reserve(self):
+        n = min(len(self._newer), PLUGIN_MAX_PLANES)
+        if n > self._reserved:
+            self._call("emap_plugin_planes", n)
+            self._reserved = n
+
+    def _download(self, indices):
+        for k in indices:
+            if self._newer[k] == "device":
+                self._call("emap_plugin_plane_read", k, f32p(self._host[k]))
+                self._newer[k] = None
+
+    def _upload(self, k):
+        if self._newer[k] == "host":
+            self._reserve()
+            self._staged = np.ascontiguousarray(self._host[k], np.float32)      # (kept until the next upload: never a temporary behind the call)
+            self._call("emap_plugin_plane_write", k, f32p(self._staged))
+            self._newer[k] = None
+
+    def host_layer(self, name):
+        """the host array of ONE layer, to READ (only this plane is downloaded if the device holds the newer one; a write into it is not
+        tracked: write through ``layers``)"""
+        idx = self.get_layer_index_with_name(name)
+        if idx is None:
+            return None
+        self._download([idx])
+        return self._host[idx]
+
+    def _enqueue(self, ops, rotation):
+        """one ``emap_plugin_chain`` call (no wait); the planes it writes are then newer on the device"""
+        self._reserve()
+        table = (EmapPluginOp * len(ops))()
+        for t, op in zip(table, ops):
+            for f, _ in EmapPluginOp._fields_:
+                setattr(t, f, op[f])
+        R = np.ascontiguousarray(np.asarray(rotation if rotation is not None else np.eye(3), np.float32).reshape(-1))
+        self._call("emap_plugin_chain", table, len(ops), f32p(R))
+        for op in ops:
+            self._newer[op["dst_plane"]] = "device"
+            p = self.plugins[op["dst_plane"]]
+            if hasattr(p, "sweeps_run"):
+                p.sweeps_run = None            # nothing waited for the sweeps' counters (MinFilter / MaxFilter on the device route)
+
+    def run_plan(self, steps, host_step, rotation=None):
+        """Run the steps of ``plugin_chain_plan`` in order.  Device ops gather in one chain that is enqueued as late as their order allows:
+        at the end, before a host plugin that reads (``plugin_inputs``) a plane the chain writes, before an upload a later op needs, or
+        when it holds 32 ops (``PLUGIN_MAX_OPS``).  ``host_step(name)`` runs a host plugin (``update_with_name``).  Returns
+        ``{name: "device" | "host"}``."""
+        route, pending = {}, []
+
+        def flush():
+            if pending:
+                self._enqueue(pending, rotation)
+                del pending[:]
+
+        for step in steps:
+            name = step[1]
+            if step[0] == "device":
+                op = step[2]
+                if op["src_kind"] == PLUGIN_SRC_PLANE and self._newer[op["src_index"]] == "host" \
+                        and op["src_index"] not in [q["dst_plane"] for q in pending]:
+                    flush()                    # (an op waiting in the chain may read the plane as it is now)
+                    self._upload(op["src_index"])
+                if len(pending) == PLUGIN_MAX_OPS:
+                    flush()
+                pending.append(op)
+                route[name] = "device"
+            else:
+                inputs = self.plugins[self.layer_names.index(name)].plugin_inputs(self.layer_names)
+                written = [self.layer_names[q["dst_plane"]] for q in pending]
+                if inputs is None or any(n in written for n in inputs):
+                    flush()
+                host_step(name)
+                route[name] = "host"
+        flush()
+        return route
 
     def init(self, plugin_params: List[PluginParams], extra_params: List[Dict]):
         self.plugins = []
@@ -113,7 +274,9 @@ class PluginManager(object):
             return
         plugin = self.plugins[idx]
         n_param = len(signature(plugin).parameters)        # arity dispatch of the reference (:199-225)
-        args = [elevation_map, layer_names, self.layers, self.layer_names]
+        inputs = plugin.plugin_inputs(self.layer_names)    # the host plugin reads the host array: fetch what it reads and the device holds newer
+        self._download(range(len(self._newer)) if inputs is None else [self.layer_names.index(n) for n in inputs if n in self.layer_names])
+        args = [elevation_map, layer_names, self._host, self.layer_names]
         if n_param == 5:
             pass
         elif n_param == 7:
@@ -125,11 +288,16 @@ class PluginManager(object):
         out = plugin(*args)
         if out is None:                    # (semantic_traversability without its input layer: the reference prints and returns nothing)
             return
-        self.layers[idx] = np.asarray(out, np.float32)
+        self._host[idx] = np.asarray(out, np.float32)
+        self._newer[idx] = "host"
 
     def get_map_with_name(self, name: str):
+        """the layer on the host (all device-newer planes come back first); to read -- in-place writes go through ``layers``"""
         idx = self.get_layer_index_with_name(name)
-        return None if idx is None else self.layers[idx]
+        if idx is None:
+            return None
+        self._download(range(len(self._newer)))
+        return self._host[idx]
 
     def get_param_with_name(self, name: str):
         idx = self.get_layer_index_with_name(name)

@@ -6,12 +6,15 @@ from typing import List
 
 import numpy as np
 
+from .._lib import PLUGIN_THRESHOLD
 from .plugin_manager import PluginBase
 
 
 class RobotCentricElevation(PluginBase):
-    def __init__(self, cell_n: int = 100, resolution: float = 0.05, threshold: float = 0.4, use_threshold: bool = False, **kwargs):
+    def __init__(self, cell_n: int = 100, resolution: float = 0.05, threshold: float = 0.4, use_threshold: bool = False, emap=None, **kwargs):
         super().__init__()
+        self.emap = emap
+        self.resolution = np.float32(resolution)
         self.cell_n = int(cell_n)
         self.threshold = np.float32(threshold)
         self.use_threshold = bool(use_threshold)
@@ -20,6 +23,15 @@ class RobotCentricElevation(PluginBase):
         self._rx = cells[:, None]
         self._ry = cells[None, :]
         self.min_filtered = np.zeros((self.cell_n, self.cell_n), np.float32)
+
+    def device_op(self, layer_names, plugin_layer_names, semantic_layer_names):
+        e = self.emap      # the device op multiplies by the MAP's resolution: only when this plugin's is the same float
+        if e is None or self.cell_n != e.cell_n or self.resolution != np.float32(e.resolution) or layer_names[:3] != ["elevation", "variance", "is_valid"]:
+            return None
+        return dict(type="robot_centric", src=None, flags=PLUGIN_THRESHOLD if self.use_threshold else 0, f0=float(self.threshold))
+
+    def plugin_inputs(self, plugin_layer_names):
+        return ()
 
     def __call__(self, elevation_map, layer_names: List[str], plugin_layers, plugin_layer_names: List[str], semantic_map,
                  semantic_layer_names: List[str], rotation, *args) -> np.ndarray:

@@ -16,6 +16,13 @@ class SmoothFilter(PluginBase):
         self.input_layer_name = input_layer_name
         self.emap = emap
 
+    def device_op(self, layer_names, plugin_layer_names, semantic_layer_names):
+        src = self.device_source(self.input_layer_name, layer_names, plugin_layer_names)
+        return None if src is None else dict(type="smooth", src=src)      # (a name found nowhere: the host route prints and takes the elevation)
+
+    def plugin_inputs(self, plugin_layer_names):
+        return (self.input_layer_name,) if self.input_layer_name in plugin_layer_names else ()
+
     def __call__(self, elevation_map: np.ndarray, layer_names: List[str], plugin_layers: np.ndarray,
                  plugin_layer_names: List[str], *args) -> np.ndarray:
         if self.emap is None:

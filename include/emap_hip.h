@@ -241,6 +241,19 @@ enum { EMAP_GRID_BUILTIN = 0, EMAP_GRID_SEMANTIC = 1, EMAP_GRID_NORMAL_COLOR = 2
 typedef struct emap_grid_layer { int32_t kind, index, slot; } emap_grid_layer;
 int emap_publish_grid_map(emap_ctx* ctx, const emap_grid_layer* layers, int32_t n_layers, int32_t order,
                           float center_z, int32_t use_only_above_for_upper_bound, float* host_out, int64_t host_slots);
+/* The same launch with plugin layers read from the context's resident planes (emap_plugin_planes / emap_plugin_chain below) next to the
+ * cells: kind EMAP_GRID_PLUGIN, index = the resident plane, which holds the plugin's RAW output (cell_n x cell_n, logical order, border
+ * included: PluginManager.layers[index], EM/plugins/plugin_manager.py:130).  The plane is read at the logical source cell
+ * (M - i, M - j) and published as ElevationMap.process_map_for_publish does (EM/elevation_mapping.py:579-596), in its order: flags
+ * EMAP_GRID_FILL_NAN -- NaN where is_valid is not above 0.5 (the plugin's fill_nan) -- then EMAP_GRID_ADD_Z -- + center_z in float32
+ * (its is_height_layer).  flags must be 0 on every other kind.  Everything else, every refusal included, as emap_publish_grid_map;
+ * refused as well: a plugin plane outside the reservation, an unknown flag.  emap_publish_grid_map is this call without flags and
+ * without kind EMAP_GRID_PLUGIN, which it refuses. */
+enum { EMAP_GRID_PLUGIN = 3 };
+enum { EMAP_GRID_FILL_NAN = 1, EMAP_GRID_ADD_Z = 2 };
+typedef struct emap_grid_layer_ex { int32_t kind, index, slot, flags; } emap_grid_layer_ex;
+int emap_publish_grid_map_ex(emap_ctx* ctx, const emap_grid_layer_ex* layers, int32_t n_layers, int32_t order,
+                             float center_z, int32_t use_only_above_for_upper_bound, float* host_out, int64_t host_slots);
 /* ElevationMap.shift_map_xy / shift_map_z (EM/elevation_mapping.py:200-226): roll by (dx rows, dy cols) with
  * padding (0; variance plane initial_variance), planes 0 and 5 += dz -- as a rotation of the map's circular origin plus a pending
  * entry that later kernels replay: no cell is moved, only the entering band of the semantic layers is cleared.  Works on strips
@@ -323,6 +336,45 @@ int emap_smooth_filter(emap_ctx* ctx, const float* host_in, int32_t passes, floa
 /* Erosion plugin (EM/plugins/erosion.py:96-104): what its cv2.erode(img, ones((k, k)), iterations=n) call computes -- the k x k
  * window minimum (anchor k/2, pixels outside the image ignored), n times.  OpenCV is third-party and absent: parity unpinned. */
 int emap_erode(emap_ctx* ctx, const float* host_in, int32_t kernel_size, int32_t iterations, float* host_out);
+
+/* ---- publish-time plugins on device-resident planes --------------------------------------------------------------------------------
+ * The reference keeps every plugin's output in PluginManager.layers, a (n_plugins, cell_n, cell_n) array on ITS device
+ * (EM/plugins/plugin_manager.py:130, :181-236), and a plugin reads the others' outputs there.  The context owns the same: up to
+ * EMAP_PLUGIN_MAX_PLANES planes of cell_n x cell_n floats, each the RAW output of a plugin (logical row-major order, border included,
+ * unflipped).  Single-strip contexts only.
+ * emap_plugin_planes: reserve n planes, 0 .. 32.  New planes are zero (as PluginManager.layers starts); growing keeps the existing ones.
+ * emap_plugin_plane_write: host array -> plane, enqueued behind what the stream holds, no wait for the device.  host_in is ordinary
+ *   (pageable) memory: the runtime stages such a copy before hipMemcpyAsync returns, and on that the rule rests that the host array
+ *   may be reused when the call returns -- a caller who hands in pinned memory must keep it unchanged until the next call that waits.
+ * emap_plugin_plane_read: plane -> host array, returns when host_out is filled (and with it everything enqueued before). */
+#define EMAP_PLUGIN_MAX_PLANES 32
+int emap_plugin_planes(emap_ctx* ctx, int32_t n_planes);
+int emap_plugin_plane_write(emap_ctx* ctx, int32_t plane, const float* host_in);
+int emap_plugin_plane_read(emap_ctx* ctx, int32_t plane, float* host_out);
+/* emap_plugin_chain: n_ops (1 .. EMAP_PLUGIN_MAX_OPS) plugins, run in order on the context's stream into their dst_plane.  ENQUEUES
+ * and does NOT wait: emap_publish_grid_map_ex (kind EMAP_GRID_PLUGIN) or emap_plugin_plane_read behind it see the results.  A pending
+ * map shift is written out first.  Each op restates the plugin's own arithmetic bit for bit:
+ *   EMAP_PLUGIN_MIN_FILTER / _MAX_FILTER (EM/plugins/min_filter.py:84-118, max_filter.py:36-112): i0 = dilation_size 0 .. 32, i1 =
+ *     iteration_n 0 .. 4096, on the map's own elevation / is_valid as emap_min_filter with NULL inputs (device-side early exit); the
+ *     plane gets mask > 0.5 ? value : NaN.  The sweeps a chain ran are not reported (nothing waits).  src_* ignored.
+ *   EMAP_PLUGIN_SMOOTH (EM/plugins/smooth_filter.py:56-58): uniform_filter(size=3) twice, as emap_smooth_filter with passes = 2.
+ *   EMAP_PLUGIN_EROSION (EM/plugins/erosion.py:60-113): i0 = kernel_size 1 .. 63, i1 = iterations 0 .. 256, flag EMAP_PLUGIN_REVERSE
+ *     (1 - layer before and after): lo / hi of the layer on the device, ((layer - lo) * 255 / (hi - lo)) truncated to 8 bits, emap_erode's
+ *     window minimum, q * (hi - lo) / 255 + lo.  A layer with hi <= lo or with a NaN is returned as it came (under REVERSE as 1 - (1 - x), the
+ *     plugin's own double reversal).
+ *   EMAP_PLUGIN_ROBOT_CENTRIC (EM/plugins/robot_centric_elevation.py:54-57, :96-118): (R6 rx + R7 ry) + R8 h on valid cells, rx =
+ *     (float)row * (float)resolution, rotation9 row-major; flag EMAP_PLUGIN_THRESHOLD: 1 / 0 for z >= f0 instead.  src_* ignored.
+ * src_kind EMAP_PLUGIN_SRC_LAYER: src_index = RAW map layer 0 .. 6 (elevation, variance, is_valid, traversability, time, upper_bound,
+ * is_upper_bound: emap_get_layer's planes); EMAP_PLUGIN_SRC_PLANE: a resident plane -- as it is when the op runs, i.e. what an earlier
+ * op of the chain or an earlier call left.  Refused with EMAP_ERR_INVALID before anything is enqueued, planes and map untouched: a NULL
+ * pointer (rotation9 may be NULL without a ROBOT_CENTRIC op), n_ops outside 1 .. 32, an unknown type / src_kind / flag, a plane outside
+ * the reservation, a SMOOTH whose source is its own dst_plane, sizes outside the bounds above, a row-strip context. */
+#define EMAP_PLUGIN_MAX_OPS 32
+enum { EMAP_PLUGIN_MIN_FILTER = 0, EMAP_PLUGIN_MAX_FILTER = 1, EMAP_PLUGIN_SMOOTH = 2, EMAP_PLUGIN_EROSION = 3, EMAP_PLUGIN_ROBOT_CENTRIC = 4 };
+enum { EMAP_PLUGIN_SRC_LAYER = 0, EMAP_PLUGIN_SRC_PLANE = 1 };
+enum { EMAP_PLUGIN_REVERSE = 1, EMAP_PLUGIN_THRESHOLD = 2 };
+typedef struct emap_plugin_op { int32_t type, dst_plane, src_kind, src_index, i0, i1, flags; float f0; } emap_plugin_op;
+int emap_plugin_chain(emap_ctx* ctx, const emap_plugin_op* ops, int32_t n_ops, const float* rotation9);
 
 /* Inpainting plugin (EM/plugins/inpainting.py:53-61) -- DOCUMENTED SUBSTITUTE for the OpenCV Telea call it makes: fills
  * the pixels with known == 0 of a (cell_n, cell_n) image holding 8-bit values, front by front, with the distance-weighted
