@@ -34,7 +34,7 @@ static int sf_recover(emap_ctx* ctx) {
   ctx->sf_host[1] = 0u;
   CK(hipMemset(ctx->sf_poison, 0, 4));
   // the binding of the moment (maybe a cloud for a frame that has not been issued yet) comes back afterwards
-  const float* pts = ctx->pts; const long n_pts = ctx->n_pts, n_all = ctx->n_pts_all; const int stride = ctx->stride, n_cols = ctx->n_cols; const ChanView chan = ctx->chan;
+  const BoundCloud bound = ctx->cloud;
   const bool fsem_set = ctx->fsem_set; ctx->fsem_set = false;      // (a fusion declared for the frame to come is not the re-run frames')
   int rc = EMAP_OK;
   ctx->sf_redo = true;
@@ -44,12 +44,12 @@ static int sf_recover(emap_ctx* ctx) {
     ctx->sf_head = (ctx->sf_head + 1) % emap_ctx::SF_RING; --ctx->sf_count;
     if (f.epoch < first) continue;            // applied before the abort
     if (!first_done) { ctx->kp.mv = f.mv; first_done = true; }      // the pending map shifts the aborted launch was to write out (later frames: none, no shift can lie between unsettled frames)
-    ctx->pts = f.pts; ctx->n_pts = f.n_pts; ctx->n_pts_all = f.n_pts_all; ctx->stride = f.stride; ctx->chan = f.chan; ctx->n_cols = f.n_cols;
+    ctx->cloud = f.cloud;
     ++ctx->sf_aborts;
     if (rc == EMAP_OK) rc = frame_impl(ctx, f.R, f.t, f.pn, f.on, nullptr, false);
   }
   ctx->sf_redo = false; ctx->fsem_set = fsem_set;
-  ctx->pts = pts; ctx->n_pts = n_pts; ctx->n_pts_all = n_all; ctx->stride = stride; ctx->chan = chan; ctx->n_cols = n_cols;
+  ctx->cloud = bound;
   return rc;
 }
 int emap_host::sf_settle(emap_ctx* ctx) {
@@ -222,22 +222,8 @@ int emap_host::normal_row_lag(const emap_ctx* ctx) {
 }
 
 int emap_host::plugin_scratch(emap_ctx* ctx, size_t planes, int counters) {
-  const size_t need = planes * (size_t)ctx->prm.cell_n * ctx->prm.cell_n;
-  if (need > ctx->plug_cap) {
-    CK(hipStreamSynchronize(ctx->stream));
-    if (ctx->plug_buf) CK(hipFree(ctx->plug_buf));
-    ctx->plug_buf = nullptr; ctx->plug_cap = 0;
-    CK(hipMalloc((void**)&ctx->plug_buf, sizeof(float) * need));
-    ctx->plug_cap = need;
-  }
-  if (counters > ctx->plug_cnt_cap) {
-    CK(hipStreamSynchronize(ctx->stream));
-    if (ctx->plug_cnt) CK(hipFree(ctx->plug_cnt));
-    ctx->plug_cnt = nullptr; ctx->plug_cnt_cap = 0;
-    CK(hipMalloc((void**)&ctx->plug_cnt, sizeof(unsigned int) * counters));
-    ctx->plug_cnt_cap = counters;
-  }
-  return EMAP_OK;
+  int rc = grow(ctx, &ctx->plug_buf, &ctx->plug_cap, planes * (size_t)ctx->prm.cell_n * ctx->prm.cell_n); if (rc) return rc;
+  return grow(ctx, &ctx->plug_cnt, &ctx->plug_cnt_cap, (size_t)counters);
 }
 
 static int validate(const emap_params* p, const emap_strip* s, std::string* why) {
@@ -255,7 +241,7 @@ static int validate(const emap_params* p, const emap_strip* s, std::string* why)
   return 1;
 }
 
-// the copy stream, its events and the host worker threads of the upload paths, made at the first upload (emap_api_cloudmsg.hip: the workers)
+// the copy stream, its events and the host worker threads of the upload paths, made at the first upload (stage_send: the workers)
 int emap_host::upload_setup(emap_ctx* ctx) {
   if (ctx->copy_stream) return EMAP_OK;
   CK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
@@ -264,6 +250,41 @@ int emap_host::upload_setup(emap_ctx* ctx) {
   if (const char* e = getenv("EMAP_UPLOAD_THREADS")) { int v = atoi(e); if (v >= 1 && v <= 64) nt = v; }
   ctx->workers = new Workers(nt);
   return EMAP_OK;
+}
+
+// ---- Stage (emap_host.h) ----------------------------------------------------------------------------------------------------------
+int emap_host::stage_next(emap_ctx* ctx, Stage* s, size_t pin_bytes, size_t dev_bytes) {
+  const int sl = s->slot ^= 1;
+  if (!s->ev[sl]) CK(hipEventCreateWithFlags(&s->ev[sl], hipEventDisableTiming));
+  if (s->ev_on[sl]) { CK(hipEventSynchronize(s->ev[sl])); s->ev_on[sl] = false; }
+  int rc = grow(ctx, &s->pin[sl], &s->pin_cap[sl], pin_bytes, Grow::pinned); if (rc) return rc;
+  return grow(ctx, &s->dev, &s->dev_cap, dev_bytes);
+}
+// A message of a million points is 16-32 MB: one host thread copying it into the pinned slot would take longer than its DMA, so the
+// workers share every chunk, and each chunk's DMA overlaps the copy of the next; a message of one chunk is one memcpy and one DMA.
+int emap_host::stage_send(emap_ctx* ctx, Stage* s, const void* src, size_t bytes) {
+  const int sl = s->slot;
+  unsigned char* pin = s->pin[sl];
+  const unsigned char* data = static_cast<const unsigned char*>(src);
+  const size_t chunk = src ? (size_t)2 << 20 : bytes;
+  if (bytes > chunk) { const int rc = upload_setup(ctx); if (rc) return rc; }
+  for (size_t o = 0; o < bytes; o += chunk) {
+    const size_t len = bytes - o < chunk ? bytes - o : chunk;
+    if (bytes <= chunk) { if (src) memcpy(pin, data, len); }
+    else ctx->workers->run([&](int w, int nw) {
+      const size_t per = ((len + nw - 1) / nw + 63) & ~(size_t)63, a = (size_t)w * per;
+      if (a < len) memcpy(pin + o + a, data + o + a, len - a < per ? len - a : per);
+    });
+    CK(hipMemcpyAsync(s->dev + o, pin + o, len, hipMemcpyHostToDevice, ctx->stream));
+  }
+  CK(hipEventRecord(s->ev[sl], ctx->stream));
+  s->ev_on[sl] = true;
+  return EMAP_OK;
+}
+void emap_host::stage_free(Stage* s) {
+  for (int k = 0; k < 2; ++k) { if (s->pin[k]) hipHostFree(s->pin[k]); if (s->ev[k]) hipEventDestroy(s->ev[k]); }
+  hipFree(s->dev);
+  *s = Stage{};
 }
 
 extern "C" {
@@ -279,16 +300,14 @@ int emap_destroy(emap_ctx* ctx) {
   hipFree(ctx->cells.hot); hipFree(ctx->cells.cold); hipFree(ctx->acc); hipFree(ctx->accr); hipFree(ctx->trav_in);
   hipFree(ctx->normal); hipFree(ctx->scratch); hipFree(ctx->plug_buf); hipFree(ctx->plug_cnt); hipFree(ctx->slots); hipFree(ctx->frame); hipFree(ctx->cnt_sync);
   for (int k = 0; k < 2; ++k) { hipFree(ctx->pts_dev[k]); if (ctx->pts_pin[k]) hipHostFree(ctx->pts_pin[k]); if (ctx->ev_copied[k]) hipEventDestroy(ctx->ev_copied[k]); if (ctx->ev_used[k]) hipEventDestroy(ctx->ev_used[k]); }
-  hipFree(ctx->depth_cloud); hipFree(ctx->depth_img);
-  for (int k = 0; k < 2; ++k) { if (ctx->depth_pin[k]) hipHostFree(ctx->depth_pin[k]); if (ctx->depth_ev[k]) hipEventDestroy(ctx->depth_ev[k]); }
+  hipFree(ctx->own_cloud); stage_free(&ctx->cloud_stage); stage_free(&ctx->image_stage);
   if (ctx->copy_stream) hipStreamDestroy(ctx->copy_stream);
   delete ctx->workers;
   hipFree(ctx->tail_idx); hipFree(ctx->tail_flags); hipFree(ctx->ray_S); hipFree(ctx->ray_lut); hipFree(ctx->inert); hipFree(ctx->inl_plane); hipFree(ctx->ray_thr);
   hipFree(ctx->bin_recs); hipFree(ctx->bin_own); hipFree(ctx->bin_own_cnt); hipFree(ctx->bin_hist); hipFree(ctx->bin_tile_total); hipFree(ctx->bin_tile_start); hipFree(ctx->bin_sync); hipFree(ctx->split_mem); hipFree(ctx->sem_split_mem); if (ctx->split_need) hipHostFree((void*)ctx->split_need); if (ctx->sf_host) hipHostFree((void*)ctx->sf_host); hipFree(ctx->frame_save); hipFree(ctx->sf_poison);
   hipFree(ctx->img_uv); hipFree(ctx->img_valid); hipFree(ctx->img_buf);
-  hipFree(ctx->imsg_dev); hipFree(ctx->grid_buf);
+  hipFree(ctx->grid_buf);
   hipFree(ctx->plane_buf); hipFree(ctx->chain_buf); hipFree(ctx->chain_cnt); hipFree(ctx->chain_red);
-  for (int k = 0; k < 2; ++k) { if (ctx->imsg_pin[k]) hipHostFree(ctx->imsg_pin[k]); if (ctx->imsg_ev[k]) hipEventDestroy(ctx->imsg_ev[k]); }
   hipFree(ctx->sem_alpha); hipFree(ctx->sem); hipFree(ctx->sem_sums); hipFree(ctx->sem_col); hipFree(ctx->cnt_plane);
   emap_comm_destroy(ctx);
   hipFree(ctx->win_state); hipFree(ctx->win_rec); hipFree(ctx->win_bits); hipFree(ctx->win_thr); hipFree(ctx->win_dh); hipFree(ctx->win_key); hipFree(ctx->win_red_dh); hipFree(ctx->win_red_key);
@@ -426,24 +445,14 @@ static int upload_impl(emap_ctx* ctx, const void* host, int64_t n, int64_t strid
   const int sl = ctx->up_slot ^= 1;
   // this slot's device buffer was read by the kernels before the previous upload, its pinned memory by the DMA two uploads ago
   if (ctx->up_used[sl]) { CK(hipEventSynchronize(ctx->ev_used[sl])); CK(hipEventSynchronize(ctx->ev_copied[sl])); }
-  if (tot > ctx->pts_cap[sl]) {
-    if (ctx->pts_dev[sl]) CK(hipFree(ctx->pts_dev[sl]));
-    ctx->pts_dev[sl] = nullptr; ctx->pts_cap[sl] = 0;
-    CK(hipMalloc((void**)&ctx->pts_dev[sl], sizeof(float) * tot));
-    ctx->pts_cap[sl] = tot;
-  }
-  if (tot > ctx->pin_cap[sl]) {
-    if (ctx->pts_pin[sl]) CK(hipHostFree(ctx->pts_pin[sl]));
-    ctx->pts_pin[sl] = nullptr; ctx->pin_cap[sl] = 0;
-    CK(hipHostMalloc((void**)&ctx->pts_pin[sl], sizeof(float) * tot, hipHostMallocDefault));
-    ctx->pin_cap[sl] = tot;
-  }
-  // A cloud with extra channels is DE-INTERLEAVED on the way: the workers write xyz as an (n, 3) matrix and the K channels as an
-  // (n, K) matrix behind it (at a 256-byte boundary) -- the conversion touches every element anyway -- so that the frame's point
+  // (no stream drain: the two waits above cover every reader, and a drain would serialise the upload against the frame in front)
+  { const int rc = grow(ctx, &ctx->pts_dev[sl], &ctx->pts_cap[sl], (size_t)tot, Grow::covered); if (rc) return rc; }
+  { const int rc = grow(ctx, &ctx->pts_pin[sl], &ctx->pin_cap[sl], (size_t)tot, Grow::pinned); if (rc) return rc; }
+  // A cloud with extra channels is DE-INTERLEAVED on the way (CloudLayout) -- the conversion touches every element anyway -- so that the frame's point
   // passes stream 12 bytes per point instead of 12 + 4 K and the semantic fusion reads one K-float record per point.
   // With `keep` (row strips, emap_upload_points_strip) only the points that pass it are written, in order: every worker counts the
   // survivors of its share of the chunk, the shares' offsets follow, a second pass over the (cache-resident) share writes them.
-  const long K = stride - 3, chan_off = K ? ((3 * (long)n + 63) & ~63L) : 0;
+  const long K = stride - 3, chan_off = cloud_layout((long)n, K).chan_off;
   long kept = 0;
   if (tot > 0) {
     float* pin = ctx->pts_pin[sl];
@@ -515,10 +524,8 @@ static int upload_impl(emap_ctx* ctx, const void* host, int64_t n, int64_t strid
     CK(hipStreamWaitEvent(ctx->stream, ctx->ev_copied[sl], 0));     // kernels enqueued from now on see the cloud; nothing waits on the host
     ctx->up_used[sl] = true;
   }
-  ctx->pts = ctx->pts_dev[sl]; ctx->n_pts = keep ? kept : (long)n; ctx->n_pts_all = (long)n; ctx->stride = 3; ctx->n_cols = (int)stride;
-  ctx->chan.p = K ? ctx->pts_dev[sl] + chan_off : ctx->pts_dev[sl]; ctx->chan.stride = K ? (int)K : 3; ctx->chan.col0 = K ? 3 : 0;
-  ctx->pts_bucketed = false;
-  if (n_kept) *n_kept = ctx->n_pts;
+  bind_split_cloud(ctx, ctx->pts_dev[sl], ctx->pts_dev[sl] + chan_off, keep ? kept : (long)n, (long)n, (int)K);
+  if (n_kept) *n_kept = ctx->cloud.n;
   return EMAP_OK;
 }
 
@@ -567,9 +574,9 @@ int emap_strip_point_mask(emap_ctx* ctx, const void* host, int64_t n, int64_t st
 // A device-resident cloud the caller bucketed itself (with emap_strip_point_mask's predicate, for THIS pose): declares it, so that the
 // frame checks pose and ray mode as for an uploaded one.
 int emap_declare_points_bucketed(emap_ctx* ctx, const float R[9], const float t[3], int64_t n_all) {
-  CKARG(ctx && R && t && n_all >= ctx->n_pts, "bad argument");
+  CKARG(ctx && R && t && n_all >= ctx->cloud.n, "bad argument");
   if (ctx->strip.row_count >= ctx->prm.cell_n) return EMAP_OK;
-  ctx->pts_bucketed = true; ctx->n_pts_all = (long)n_all; ctx->bucket_org_r = ctx->kp.org_r;
+  ctx->pts_bucketed = true; ctx->cloud.n_all = (long)n_all; ctx->bucket_org_r = ctx->kp.org_r;
   memcpy(ctx->bucket_R, R, sizeof ctx->bucket_R); memcpy(ctx->bucket_t, t, sizeof ctx->bucket_t);
   return EMAP_OK;
 }
@@ -577,44 +584,35 @@ int emap_declare_points_bucketed(emap_ctx* ctx, const float R[9], const float t[
 int emap_set_points_device_split(emap_ctx* ctx, const float* xyz_dev, const float* chan_dev, int64_t n, int64_t n_chan) {
   CKARG(ctx, "null ctx");
   CKARG(n >= 0 && n_chan >= 0 && n_chan < 4093 && (n == 0 || (xyz_dev && (n_chan == 0 || chan_dev))), "bad device point buffers");
-  ctx->pts = xyz_dev; ctx->n_pts = (long)n; ctx->stride = 3; ctx->n_cols = 3 + (int)n_chan; ctx->pts_bucketed = false; ctx->n_pts_all = (long)n;
-  ctx->chan.p = n_chan ? chan_dev : xyz_dev; ctx->chan.stride = n_chan ? (int)n_chan : 3; ctx->chan.col0 = n_chan ? 3 : 0;
+  bind_split_cloud(ctx, xyz_dev, chan_dev, (long)n, (long)n, (int)n_chan);
   return EMAP_OK;
 }
 
 int emap_set_points_device(emap_ctx* ctx, const float* dev, int64_t n, int64_t stride) {
   CKARG(ctx, "null ctx");
   CKARG(n >= 0 && stride >= 3 && stride < 4096 && (n == 0 || dev), "bad device point buffer");
-  ctx->pts = dev; ctx->n_pts = (long)n; ctx->stride = (int)stride; ctx->n_cols = (int)stride; ctx->pts_bucketed = false; ctx->n_pts_all = (long)n;
-  ctx->chan.p = dev; ctx->chan.stride = (int)stride; ctx->chan.col0 = 0;            // interleaved rows: the channels sit behind xyz
+  ctx->cloud = BoundCloud{dev, (long)n, (int)stride, (long)n, ChanView{dev, (int)stride, 0}, (int)stride};      // interleaved rows: the channels sit behind xyz
+  ctx->pts_bucketed = false;
   return EMAP_OK;
 }
 
 static int ensure_tail(emap_ctx* ctx) {
-  if (ctx->n_pts > ctx->tail_cap) {
-    CK(hipStreamSynchronize(ctx->stream));
-    if (ctx->tail_idx) CK(hipFree(ctx->tail_idx));
-    if (ctx->tail_flags) CK(hipFree(ctx->tail_flags));
-    ctx->tail_idx = nullptr; ctx->tail_flags = nullptr; ctx->tail_cap = 0;
-    CK(hipMalloc((void**)&ctx->tail_idx, sizeof(int) * ctx->n_pts));
-    CK(hipMalloc((void**)&ctx->tail_flags, ctx->n_pts));
-    ctx->tail_cap = ctx->n_pts;
-  }
-  return EMAP_OK;
+  int rc = grow(ctx, &ctx->tail_idx, &ctx->tail_idx_cap, (size_t)ctx->cloud.n); if (rc) return rc;
+  return grow(ctx, &ctx->tail_flags, &ctx->tail_flags_cap, (size_t)ctx->cloud.n);
 }
 
 int emap_point_index(emap_ctx* ctx, const float R[9], const float t[3], int32_t* idx, uint8_t* valid, uint8_t* inside) {
   CKARG(ctx && R && t && idx && valid && inside, "null argument"); SF_CHECK();
-  if (!ctx->pts && ctx->n_pts) { ctx->err = "no point cloud bound"; return EMAP_ERR_NO_POINTS; }
+  NEED_POINTS();
   CK(hipSetDevice(ctx->device));
-  if (ctx->n_pts == 0) return EMAP_OK;
+  if (ctx->cloud.n == 0) return EMAP_OK;
   int rc = ensure_tail(ctx); if (rc) return rc;
-  launch_point_index(ctx->stream, ctx->kp, make_pose(ctx, R, t), ctx->pts, ctx->n_pts, ctx->stride, ctx->tail_idx, ctx->tail_flags);
+  launch_point_index(ctx->stream, ctx->kp, make_pose(ctx, R, t), ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->tail_idx, ctx->tail_flags);
   CK(hipGetLastError());
-  CK(hipMemcpyAsync(idx, ctx->tail_idx, sizeof(int) * ctx->n_pts, hipMemcpyDeviceToHost, ctx->stream));
-  CK(hipMemcpyAsync(valid, ctx->tail_flags, ctx->n_pts, hipMemcpyDeviceToHost, ctx->stream));
+  CK(hipMemcpyAsync(idx, ctx->tail_idx, sizeof(int) * ctx->cloud.n, hipMemcpyDeviceToHost, ctx->stream));
+  CK(hipMemcpyAsync(valid, ctx->tail_flags, ctx->cloud.n, hipMemcpyDeviceToHost, ctx->stream));
   CK(hipStreamSynchronize(ctx->stream));
-  for (long i = 0; i < ctx->n_pts; ++i) { uint8_t f = valid[i]; valid[i] = f & 1; inside[i] = (f >> 1) & 1; }
+  for (long i = 0; i < ctx->cloud.n; ++i) { uint8_t f = valid[i]; valid[i] = f & 1; inside[i] = (f >> 1) & 1; }
   return EMAP_OK;
 }
 
@@ -638,7 +636,7 @@ extern "C++" bool emap_host::takes_bins(const emap_ctx* ctx, long n) {
   return ctx->scatter_mode == 2 || (ctx->scatter_mode == 0 && bins_possible(ctx) && n >= BIN_MIN_POINTS);
 }
 static int ensure_bins(emap_ctx* ctx, bool raybin, const Frame* f) {
-  const long n = ctx->n_pts;
+  const long n = ctx->cloud.n;
   BinGeo& g = ctx->bg;
   g.sub = bin_sub(ctx);
   g.tiles_x = (ctx->prm.cell_n + 63) / 64; g.tiles_y = (ctx->strip.row_count + 16 * g.sub - 1) / (16 * g.sub); g.T = g.tiles_x * g.tiles_y; g.TB = g.T + 1;
@@ -671,14 +669,7 @@ static int ensure_bins(emap_ctx* ctx, bool raybin, const Frame* f) {
   long chunk = (n + B - 1) / B; chunk = ((chunk + unit - 1) / unit) * unit;
   g.B = (int)((n + chunk - 1) / chunk); if (g.B < 1) g.B = 1;
   g.chunk = chunk;
-  const size_t hist_need = (size_t)g.pitch * (size_t)g.B;
-  if (hist_need > ctx->bin_hist_cap) {
-    CK(hipStreamSynchronize(ctx->stream));
-    if (ctx->bin_hist) CK(hipFree(ctx->bin_hist));
-    ctx->bin_hist = nullptr; ctx->bin_hist_cap = 0;
-    CK(hipMalloc((void**)&ctx->bin_hist, sizeof(unsigned int) * hist_need));
-    ctx->bin_hist_cap = hist_need;
-  }
+  int rc = grow(ctx, &ctx->bin_hist, &ctx->bin_hist_cap, (size_t)g.pitch * (size_t)g.B); if (rc) return rc;
   if (!ctx->bin_tile_total) {
     CK(hipMalloc((void**)&ctx->bin_tile_total, sizeof(unsigned int) * (BIN_MAX_T + 2)));
     CK(hipMalloc((void**)&ctx->bin_tile_start, sizeof(unsigned int) * (BIN_MAX_T + 2)));
@@ -705,21 +696,10 @@ static int ensure_bins(emap_ctx* ctx, bool raybin, const Frame* f) {
     CK(hipHostGetDevicePointer((void**)&ctx->split.need_host, const_cast<unsigned int*>(ctx->split_need), 0));
     ctx->split.on = 0;
   }
-  if (n * ctx->bin_rs > ctx->bin_cap) {
-    CK(hipStreamSynchronize(ctx->stream));
-    if (ctx->bin_recs) CK(hipFree(ctx->bin_recs));
-    ctx->bin_recs = nullptr; ctx->bin_cap = 0;
-    CK(hipMalloc((void**)&ctx->bin_recs, sizeof(BinRec) * n * ctx->bin_rs));
-    ctx->bin_cap = n * ctx->bin_rs;
-  }
-  if (ctx->bin_strip && (long)g.B * chunk > ctx->bin_own_cap) {
-    CK(hipStreamSynchronize(ctx->stream));
-    if (ctx->bin_own) CK(hipFree(ctx->bin_own));
-    if (ctx->bin_own_cnt) CK(hipFree(ctx->bin_own_cnt));
-    ctx->bin_own = nullptr; ctx->bin_own_cnt = nullptr; ctx->bin_own_cap = 0;
-    CK(hipMalloc((void**)&ctx->bin_own, 16 * (size_t)g.B * chunk));           // 16-byte staging records; only the owned share is ever touched
-    CK(hipMalloc((void**)&ctx->bin_own_cnt, sizeof(unsigned int) * (size_t)BIN_MAX_B));
-    ctx->bin_own_cap = (long)g.B * chunk;
+  if ((rc = grow(ctx, &ctx->bin_recs, &ctx->bin_recs_cap, (size_t)n * ctx->bin_rs))) return rc;
+  if (ctx->bin_strip) {
+    if ((rc = grow(ctx, &ctx->bin_own, &ctx->bin_own_cap, (size_t)g.B * chunk))) return rc;      // only the owned share is ever touched
+    if (!ctx->bin_own_cnt) CK(hipMalloc((void**)&ctx->bin_own_cnt, sizeof(unsigned int) * (size_t)BIN_MAX_B));
   }
   return EMAP_OK;
 }
@@ -759,7 +739,7 @@ static GateArgs gate_args(emap_ctx* ctx, double position_noise, double orientati
   g.enable = p.enable_drift_compensation; g.min_cnt = p.min_height_drift_cnt; g.max_drift = p.max_drift; g.alpha = (float)p.drift_compensation_alpha;
   g.noise_ok = (position_noise > p.position_noise_thresh) || (orientation_noise > p.orientation_noise_thresh);
   g.use_override = ctx->use_override ? 1 : 0; g.sum_override = ctx->sum_override; g.cnt_override = ctx->cnt_override;
-  g.n_points = (unsigned int)ctx->n_pts;
+  g.n_points = (unsigned int)ctx->cloud.n;
   return g;
 }
 
@@ -779,7 +759,7 @@ static int count_impl(emap_ctx* ctx, const float R[9], const float t[3], const F
   const bool gate_possible = !f || f->gate_possible;
   ctx->bin_rs = 1;
   CK(hipSetDevice(ctx->device));
-  const bool binned = ctx->n_pts > 0 && takes_bins(ctx, ctx->n_pts_all);
+  const bool binned = ctx->cloud.n > 0 && takes_bins(ctx, ctx->cloud.n_all);
   ctx->frame_binned = binned;
   const bool tm = ctx->stage_timing && f;
   if (binned) {
@@ -787,9 +767,9 @@ static int count_impl(emap_ctx* ctx, const float R[9], const float t[3], const F
     // marches the cloud in its own order instead of the sorted records)
     int rc = ensure_bins(ctx, ctx->prm.enable_visibility_cleanup != 0, f); if (rc) return rc;
     const Pose pose = make_pose(ctx, R, t);
-    BinStg* own = ctx->bin_strip ? ctx->bin_own : nullptr;
+    BinStg* own = ctx->bin_strip ? reinterpret_cast<BinStg*>(ctx->bin_own) : nullptr;
     if (tm) CK(hipEventRecord(ctx->ev[ST_HIST], ctx->stream));
-    launch_bin_hist(ctx->stream, ctx->kp, pose, ctx->bg, ctx->pts, ctx->n_pts, ctx->stride, ctx->bin_hist, own, ctx->bin_own_cnt);
+    launch_bin_hist(ctx->stream, ctx->kp, pose, ctx->bg, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->bin_hist, own, ctx->bin_own_cnt);
     if (tm) CK(hipEventRecord(ctx->ev[ST_SCAN], ctx->stream));
     // heavy tiles are split only when k_tile_count runs in this frame (it leaves the per-cell counts k_tile_fuse's parts need)
     static const bool split_off = getenv("EMAP_SPLIT") && atoi(getenv("EMAP_SPLIT")) == 0;      // A/B and test hook
@@ -821,17 +801,17 @@ static int count_impl(emap_ctx* ctx, const float R[9], const float t[3], const F
     ctx->split_dirty = ctx->split_dirty || (ctx->split.on != 0 && ctx->split.cap > 0);      // (slots are only used by the SPLIT instantiations: extra workgroups in the launch)
     launch_bin_scan(ctx->stream, ctx->bg, ctx->bin_hist, ctx->bin_tile_total, ctx->bin_tile_start, ctx->bin_sync, ctx->split);
     if (tm) CK(hipEventRecord(ctx->ev[ST_SCATTER], ctx->stream));
-    launch_bin_scatter(ctx->stream, ctx->kp, pose, ctx->bg, ctx->pts, ctx->n_pts, ctx->stride, ctx->bin_hist, ctx->bin_tile_start, ctx->bin_recs, own, ctx->bin_own_cnt,
-                       ctx->chan, ctx->carry);
+    launch_bin_scatter(ctx->stream, ctx->kp, pose, ctx->bg, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->bin_hist, ctx->bin_tile_start, ctx->bin_recs, own, ctx->bin_own_cnt,
+                       ctx->cloud.chan, ctx->carry);
     if (tm) CK(hipEventRecord(ctx->ev[ST_GATE], ctx->stream));        // the "gate" stage = per-tile error sums + k_gate
-    if (gate_possible) launch_tile_count(ctx->stream, ctx->kp, ctx->bg, ctx->bin_recs, ctx->bin_rs, ctx->bin_tile_start, ctx->cells, ctx->slots, ctx->split, ctx->n_pts);
+    if (gate_possible) launch_tile_count(ctx->stream, ctx->kp, ctx->bg, ctx->bin_recs, ctx->bin_rs, ctx->bin_tile_start, ctx->cells, ctx->slots, ctx->split, ctx->cloud.n);
   } else {
     ctx->carry.on = 0;
     if (tm) for (int e = ST_HIST; e <= ST_SCATTER; ++e) CK(hipEventRecord(ctx->ev[e], ctx->stream));
     // whole frames (emap_update) on this path: the drift gate rides in k_count's last workgroup, one launch less in a chain of six
     static const bool fold_off = getenv("EMAP_GATE_FOLD") && atoi(getenv("EMAP_GATE_FOLD")) == 0;      // A/B and test hook
     const bool fold = f && f->fold_gate && !fold_off && ctx->cnt_sync;
-    const bool folded = launch_count(ctx->stream, ctx->kp, make_pose(ctx, R, t), ctx->pts, ctx->n_pts, ctx->stride, ctx->cells, ctx->acc, ctx->slots,
+    const bool folded = launch_count(ctx->stream, ctx->kp, make_pose(ctx, R, t), ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->cells, ctx->acc, ctx->slots,
                                      fold ? &f->gate : nullptr, ctx->frame, ctx->cnt_sync);
     if (gate_folded) *gate_folded = folded;
     if (tm) CK(hipEventRecord(ctx->ev[ST_GATE], ctx->stream));
@@ -912,13 +892,13 @@ static int fuse_impl(emap_ctx* ctx, const float R[9], const float t[3], bool fus
     if (ctx->fsem_set) ctx->update_path |= merged ? 4 : (ctx->carry.on ? 8 : 0);      // (emap_last_update_path)
     launch_bin_fuse(ctx->stream, ctx->kp, ctx->bg, ctx->bin_recs, ctx->bin_rs, ctx->bin_tile_start, ctx->cells, ctx->acc, ctx->frame, fuse_average, rays,
                     (merged && !ctx->fsem_keep_counts) ? nullptr : ctx->cnt_plane, ctx->inert, ctx->inl_plane, ctx->ray_thr, f ? f->ov : OverlapArgs{},
-                    f ? f->gate_fold : GateFold{}, ctx->split, ctx->n_pts, merged ? &sm : nullptr);
+                    f ? f->gate_fold : GateFold{}, ctx->split, ctx->cloud.n, merged ? &sm : nullptr);
     if (ctx->split.on) ctx->split_dirty = false;        // k_tile_fuse's parts cleared their slots (a frame that splits nothing leaves an older count stage's slots as they are)
     if (fuse_average) ctx->kp.mv.n = 0;   // every owned cell rewritten: pending map shifts are in memory now
     CK(hipGetLastError());
     return EMAP_OK;
   }
-  launch_fuse(ctx->stream, ctx->kp, make_pose(ctx, R, t), ctx->pts, ctx->n_pts, ctx->stride, ctx->cells, ctx->acc, ctx->frame);
+  launch_fuse(ctx->stream, ctx->kp, make_pose(ctx, R, t), ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->cells, ctx->acc, ctx->frame);
   CK(hipGetLastError());
   return EMAP_OK;
 }
@@ -966,7 +946,7 @@ static int rays_impl(emap_ctx* ctx, const float R[9], const float t[3], const Fr
   KP kr = ctx->kp;
   kr.nlag = nlag ? 1 : 0;                                // sharded frame after a row shift: the row-aligned copy of the normal planes (normal_exchange)
   kr.ray_pref = ctx->split_need ? (int)ctx->split_need[1] : 0;      // (host-mapped word written by k_ray_apply: FrameDev::ray_class)
-  launch_rays(ctx->stream, kr, make_pose(ctx, R, t), ctx->rt, ctx->pts, ctx->n_pts, ctx->stride, ctx->cells, av,
+  launch_rays(ctx->stream, kr, make_pose(ctx, R, t), ctx->rt, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->cells, av,
               nlag ? ctx->nlag_buf : ctx->normal, nlag ? (long)ctx->strip.row_count * ctx->prm.cell_n : ctx->ncells_alloc,
               ctx->frame, ctx->want_ray_stats, ctx->inert, inl, fused ? 1 : (int)(sizeof(AccF) / 4),
               fused ? ctx->ray_thr : nullptr,
@@ -1179,8 +1159,8 @@ static int frame_impl(emap_ctx* ctx, const float R[9], const float t[3], double 
   // (not with a visibility pass or a declared semantic fusion behind it: an ABORTED launch must leave nothing for the rest of the frame to
   // act on -- the stencil launch that follows is a pure function of the map -- until sf_recover has re-run the frame)
   static const bool sf_env_off = getenv("EMAP_SMALL_FRAME") && atoi(getenv("EMAP_SMALL_FRAME")) == 0;      // A/B and test hook
-  const int sf_grid = (!sharded && !sf_env_off && !ctx->sf_redo && !takes_bins(ctx, ctx->n_pts_all) && ctx->cnt_sync && !ctx->pts_bucketed && !rays_on && !ctx->fsem_set)
-                      ? small_frame_grid(ctx->kp, ctx->n_pts) : 0;
+  const int sf_grid = (!sharded && !sf_env_off && !ctx->sf_redo && !takes_bins(ctx, ctx->cloud.n_all) && ctx->cnt_sync && !ctx->pts_bucketed && !rays_on && !ctx->fsem_set)
+                      ? small_frame_grid(ctx->kp, ctx->cloud.n) : 0;
   if (sf_grid == 0) SF_CHECK();                 // (a frame on any other path: the small frames in flight are settled first)
   Frame fr; memset(&fr, 0, sizeof fr);
   if ((rc = frame_sem_begin(ctx, rays_on, &fr))) return rc;
@@ -1212,13 +1192,13 @@ static int frame_impl(emap_ctx* ctx, const float R[9], const float t[3], double 
     {   // what the launch stands for, should a barrier be aborted (sf_recover)
       emap_ctx::SfFrame& f = ctx->sf_ring[(ctx->sf_head + ctx->sf_count) % emap_ctx::SF_RING];
       f.epoch = ctx->sf_epoch; memcpy(f.R, R, sizeof f.R); memcpy(f.t, t, sizeof f.t); f.pn = position_noise; f.on = orientation_noise; f.mv = ctx->kp.mv;
-      f.pts = ctx->pts; f.n_pts = ctx->n_pts; f.n_pts_all = ctx->n_pts_all; f.stride = ctx->stride; f.chan = ctx->chan; f.n_cols = ctx->n_cols;
+      f.cloud = ctx->cloud;
       ++ctx->sf_count;
     }
     unsigned int spin = SF_SPIN_DEFAULT; int test_abort = 0;      // test hooks (read per frame: a test toggles them)
     if (const char* e = getenv("EMAP_SF_SPIN_LIMIT")) { const long v = atol(e); if (v >= 1 && v <= (1L << 24)) spin = (unsigned int)v; }
     if (const char* e = getenv("EMAP_SF_TEST_ABORT")) test_abort = atoi(e);
-    launch_small_frame(ctx->stream, sf_grid, ctx->kp, make_pose(ctx, R, t), ctx->pts, ctx->n_pts, ctx->stride, ctx->cells, ctx->acc,
+    launch_small_frame(ctx->stream, sf_grid, ctx->kp, make_pose(ctx, R, t), ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->cells, ctx->acc,
                        ctx->cnt_plane, fr.ov, fr.gate, ctx->frame, ctx->frame_save, ctx->slots,
                        ctx->cnt_sync, ctx->cnt_sync + 2048, ctx->sf_host_dev, ctx->sf_poison, ctx->sf_epoch, spin, test_abort);
     CK(hipGetLastError());

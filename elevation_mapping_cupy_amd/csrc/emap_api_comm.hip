@@ -266,12 +266,7 @@ extern "C++" int emap_host::normal_exchange(emap_ctx* ctx) {
   const int C = ctx->prm.cell_n, W = ctx->comm_world, me = ctx->comm_rank;
   const long n = ctx->strip.row_count, H = ctx->strip.halo_rows;
   if (!ctx->cuts_ok) { ctx->err = "normal_exchange: the strips the ranks reported to emap_comm_init do not tile the map"; return EMAP_ERR_COMM; }
-  if ((long)n * C > ctx->nlag_cap) {
-    CK(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->nlag_buf); ctx->nlag_buf = nullptr; ctx->nlag_cap = 0;
-    CK(hipMalloc((void**)&ctx->nlag_buf, sizeof(float) * 3 * (size_t)n * C));
-    ctx->nlag_cap = n * C;
-  }
+  { const int rc = grow(ctx, &ctx->nlag_buf, &ctx->nlag_cap, 3 * (size_t)n * C); if (rc) return rc; }
   std::vector<LagPiece> plan;
   lag_pieces(C, W, ctx->cut_begin.data(), ctx->cut_count.data(), normal_row_lag(ctx), plan);
   const RcclApi* a = ctx->rccl;
@@ -301,7 +296,7 @@ extern "C++" int emap_host::normal_exchange(emap_ctx* ctx) {
 // Decided from values every rank shares (parameters, world size, cloud size): all ranks take the same branch of the collective code.
 extern "C++" bool emap_host::rays_by_ray(const emap_ctx* ctx) {
   if (!ctx->rccl || ctx->comm_world <= 1 || !ctx->prm.enable_visibility_cleanup || ctx->ray_mode == 1) return false;
-  if (!(ctx->n_pts_all > 0 && takes_bins(ctx, ctx->n_pts_all))) return false;      // the window march walks the frame's tile-sorted records
+  if (!(ctx->cloud.n_all > 0 && takes_bins(ctx, ctx->cloud.n_all))) return false;      // the window march walks the frame's tile-sorted records
   // by row below 2048^2 cells: the window exchange (three all-reduces) costs about what the whole pass costs there
   return ctx->ray_mode == 2 || ctx->prm.cell_n >= 2048;
 }
@@ -328,6 +323,7 @@ static long window_cap(const emap_ctx* ctx) {
   const long nr = std::min<long>(((W + 7) & ~7L) + 8, (C + 7) & ~7L), nc = std::min<long>(((W + 63) & ~63L) + 64, (C + 63) & ~63L);
   return nr * nc;
 }
+// (not emap_host::grow: eight buffers share one capacity, and the allocation is collective -- see ensure_window)
 static int alloc_window(emap_ctx* ctx, long cap) {
   CK(hipStreamSynchronize(ctx->stream));
   hipFree(ctx->win_state); hipFree(ctx->win_rec); hipFree(ctx->win_bits); hipFree(ctx->win_thr); hipFree(ctx->win_dh); hipFree(ctx->win_key); hipFree(ctx->win_red_dh); hipFree(ctx->win_red_key);
@@ -418,7 +414,7 @@ extern "C++" int emap_host::rays_by_ray_pass(emap_ctx* ctx, const float R[9], co
   Cells wc; wc.hot = w.hot; wc.cold = w.cold;
   char* const db = reinterpret_cast<char*>(w.dh);
   const AccRView av = {db, db + 8, reinterpret_cast<char*>(w.key), 16, 16, 4, 0};
-  launch_rays(st, kw, make_pose(ctx, R, t), ctx->rt, ctx->pts, ctx->n_pts, ctx->stride, wc, av, w.normal, n, ctx->frame, ctx->want_ray_stats,
+  launch_rays(st, kw, make_pose(ctx, R, t), ctx->rt, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, wc, av, w.normal, n, ctx->frame, ctx->want_ray_stats,
               w.bits, w.inl, 1, w.thr, reinterpret_cast<const unsigned int*>(ctx->bin_recs), ctx->bin_tile_start + ctx->bg.TB);
   CK(hipGetLastError());
   // (4) effects back to the owners: sums of {dec, hits}, maxima of the upper-bound keys

@@ -1,7 +1,8 @@
 // C ABI of the MI355X elevation-map fusion core, host side of the depth-image input (kernel: emap_depth.hip): a depth camera's frame
 // is uploaded as IMAGES and back-projected on the device into a cloud the context owns and binds -- the reference back-projects on
 // the host (sensor_processing/semantic_sensor/.../pointcloud_node.py:205-250, 261-269) and hands the float cloud to
-// input_pointcloud.  Also the read-back of whatever cloud is bound (emap_get_bound_points).
+// input_pointcloud.  Also the owned cloud of the doors that produce theirs (owned_cloud_prepare) and the read-back of whatever cloud
+// is bound (emap_get_bound_points).
 #include "emap_host.h"
 #include <cmath>
 #include <cstring>
@@ -10,38 +11,13 @@ using namespace emap_host;
 
 static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// The buffers behind a cloud the context produces itself (depth image, PointCloud2 message): the next pinned slot (its copy of two calls
-// ago done), the device copy of the caller's bytes and the owned cloud, each grown on demand.  Only one cloud is bound at a time, so
-// both doors share them.
-int emap_host::owned_cloud_prepare(emap_ctx* ctx, size_t pin_bytes, size_t img_bytes, long tot, int* slot) {
-  const int sl = ctx->depth_slot ^= 1;
-  if (!ctx->depth_ev[sl]) CK(hipEventCreateWithFlags(&ctx->depth_ev[sl], hipEventDisableTiming));
-  if (ctx->depth_ev_on[sl]) CK(hipEventSynchronize(ctx->depth_ev[sl]));      // the copy out of this slot two calls ago (long done in a running stream)
-  if (pin_bytes > ctx->depth_pin_cap[sl]) {
-    if (ctx->depth_pin[sl]) CK(hipHostFree(ctx->depth_pin[sl]));
-    ctx->depth_pin[sl] = nullptr; ctx->depth_pin_cap[sl] = 0; ctx->depth_ev_on[sl] = false;
-    CK(hipHostMalloc((void**)&ctx->depth_pin[sl], pin_bytes, hipHostMallocDefault));
-    ctx->depth_pin_cap[sl] = pin_bytes;
-  }
-  if (img_bytes > ctx->depth_img_cap || tot > ctx->depth_cloud_cap) {
-    // growing: kernels in flight may still read either buffer, and the cloud may be the bound one -- drain, unbind, then replace
-    CK(hipStreamSynchronize(ctx->stream));
-    if (img_bytes > ctx->depth_img_cap) {
-      if (ctx->depth_img) CK(hipFree(ctx->depth_img));
-      ctx->depth_img = nullptr; ctx->depth_img_cap = 0;
-      CK(hipMalloc((void**)&ctx->depth_img, img_bytes));
-      ctx->depth_img_cap = img_bytes;
-    }
-    if (tot > ctx->depth_cloud_cap) {
-      if (ctx->depth_cloud && ctx->pts == ctx->depth_cloud) { ctx->pts = nullptr; ctx->n_pts = 0; ctx->n_pts_all = 0; ctx->pts_bucketed = false; }
-      if (ctx->depth_cloud) CK(hipFree(ctx->depth_cloud));
-      ctx->depth_cloud = nullptr; ctx->depth_cloud_cap = 0;
-      CK(hipMalloc((void**)&ctx->depth_cloud, sizeof(float) * (size_t)tot));
-      ctx->depth_cloud_cap = tot;
-    }
-  }
-  *slot = sl;
-  return EMAP_OK;
+// The next slot of cloud_stage and the owned cloud of `tot` floats.  The small frames in flight keep raw pointers to the cloud they
+// read and may be re-run after an abort: the caller has settled them (SF_CHECK) before the owned buffer is overwritten.
+int emap_host::owned_cloud_prepare(emap_ctx* ctx, size_t pin_bytes, size_t dev_bytes, long tot) {
+  const int rc = stage_next(ctx, &ctx->cloud_stage, pin_bytes, dev_bytes); if (rc) return rc;
+  // a cloud about to be replaced must not stay bound
+  if ((size_t)tot > ctx->own_cloud_cap && ctx->own_cloud && ctx->cloud.pts == ctx->own_cloud) { ctx->cloud.pts = nullptr; ctx->cloud.n = 0; ctx->cloud.n_all = 0; ctx->pts_bucketed = false; }
+  return grow(ctx, &ctx->own_cloud, &ctx->own_cloud_cap, (size_t)tot);
 }
 
 extern "C" {
@@ -61,8 +37,6 @@ int emap_bind_depth_image(emap_ctx* ctx, const emap_depth_desc* d, const void* d
   CKARG(d->n_features >= 0 && d->n_features <= EM_DEPTH_MAX_CHAN && (d->has_rgb ? 1 : 0) + d->n_features <= EM_DEPTH_MAX_CHAN,
         "emap_bind_depth_image: at most 16 channels (colour + features)");
   CKARG((!d->has_rgb || rgb_or_null) && (d->n_features == 0 || features_or_null), "emap_bind_depth_image: null channel image");
-  // the small frames in flight keep raw pointers to the cloud they read and may be re-run after an abort: settled before the owned
-  // buffer is overwritten (as upload_impl does)
   SF_CHECK();
   CK(hipSetDevice(ctx->device));
 
@@ -75,45 +49,40 @@ int emap_bind_depth_image(emap_ctx* ctx, const emap_depth_desc* d, const void* d
   // the images in one block, every one at a 256-byte boundary: depth | confidence | features | rgb
   const size_t b_depth = px * (d->depth_dtype == 0 ? 4 : 2), b_conf = confidence_or_null ? px * 4 : 0, b_feat = px * 4 * (size_t)A.n_feat, b_rgb = A.has_rgb ? px * 3 : 0;
   const size_t o_conf = up256(b_depth), o_feat = o_conf + up256(b_conf), o_rgb = o_feat + up256(b_feat), img_bytes = o_rgb + up256(b_rgb);
-  // the cloud as upload_impl lays it out: xyz (n, 3), the channel matrix behind it at a 256-byte boundary
-  const long chan_off = Kc ? ((3 * A.n + 63) & ~63L) : 0, tot = Kc ? chan_off + (long)Kc * A.n : 3 * A.n;
+  const CloudLayout lay = cloud_layout(A.n, Kc);
 
-  int sl;
-  { const int rc = owned_cloud_prepare(ctx, img_bytes, img_bytes, tot, &sl); if (rc) return rc; }
-  unsigned char* pin = ctx->depth_pin[sl];
+  { const int rc = owned_cloud_prepare(ctx, img_bytes, img_bytes, lay.tot); if (rc) return rc; }
+  Stage& st = ctx->cloud_stage;
+  unsigned char* pin = st.pin[st.slot];
   memcpy(pin, depth, b_depth);
   if (b_conf) memcpy(pin + o_conf, confidence_or_null, b_conf);
   if (b_feat) memcpy(pin + o_feat, features_or_null, b_feat);
   if (b_rgb) memcpy(pin + o_rgb, rgb_or_null, b_rgb);
-  // one block when the images fill it (the gaps are < 256 bytes each), stream-ordered behind the kernel that read the block before
-  CK(hipMemcpyAsync(ctx->depth_img, pin, img_bytes, hipMemcpyHostToDevice, ctx->stream));
-  CK(hipEventRecord(ctx->depth_ev[sl], ctx->stream));
-  ctx->depth_ev_on[sl] = true;
-  A.depth = ctx->depth_img; A.conf = b_conf ? reinterpret_cast<const float*>(ctx->depth_img + o_conf) : nullptr;
-  A.feat = b_feat ? reinterpret_cast<const float*>(ctx->depth_img + o_feat) : nullptr; A.rgb = b_rgb ? ctx->depth_img + o_rgb : nullptr;
-  A.xyz = ctx->depth_cloud; A.chan = Kc ? ctx->depth_cloud + chan_off : nullptr;
+  // one block when the images fill it (the gaps are < 256 bytes each): one DMA
+  { const int rc = stage_send(ctx, &st, nullptr, img_bytes); if (rc) return rc; }
+  A.depth = st.dev; A.conf = b_conf ? reinterpret_cast<const float*>(st.dev + o_conf) : nullptr;
+  A.feat = b_feat ? reinterpret_cast<const float*>(st.dev + o_feat) : nullptr; A.rgb = b_rgb ? st.dev + o_rgb : nullptr;
+  A.xyz = ctx->own_cloud; A.chan = Kc ? ctx->own_cloud + lay.chan_off : nullptr;
   launch_depth_cloud(ctx->stream, A, d->depth_dtype);
   CK(hipGetLastError());
-  // bound exactly as emap_set_points_device_split binds a caller's de-interleaved cloud (a row-strip context: whole and unbucketed)
-  ctx->pts = ctx->depth_cloud; ctx->n_pts = A.n; ctx->stride = 3; ctx->n_cols = 3 + Kc; ctx->pts_bucketed = false; ctx->n_pts_all = A.n;
-  ctx->chan.p = Kc ? ctx->depth_cloud + chan_off : ctx->depth_cloud; ctx->chan.stride = Kc ? Kc : 3; ctx->chan.col0 = Kc ? 3 : 0;
+  bind_split_cloud(ctx, ctx->own_cloud, ctx->own_cloud + lay.chan_off, A.n, A.n, Kc);
   if (n_points_out) *n_points_out = A.n;
   return EMAP_OK;
 }
 
 int emap_get_bound_points(emap_ctx* ctx, float* xyz_host, float* chan_host_or_null) {
   CKARG(ctx && xyz_host, "null argument"); SF_CHECK();
-  if (!ctx->pts) { ctx->err = "no point cloud bound"; return EMAP_ERR_NO_POINTS; }
+  if (!ctx->cloud.pts) { ctx->err = "no point cloud bound"; return EMAP_ERR_NO_POINTS; }
   CK(hipSetDevice(ctx->device));
-  const size_t n = (size_t)ctx->n_pts, K = (size_t)(ctx->n_cols - 3);
+  const size_t n = (size_t)ctx->cloud.n, K = (size_t)(ctx->cloud.n_cols - 3);
   if (n) {
     // rows of `stride` floats (xyz) / of chan.stride floats with the caller's column 3 at chan.p + 3 - col0 (emap_device.h: ChanView)
-    if (ctx->stride == 3) CK(hipMemcpyAsync(xyz_host, ctx->pts, 12 * n, hipMemcpyDeviceToHost, ctx->stream));
-    else CK(hipMemcpy2DAsync(xyz_host, 12, ctx->pts, sizeof(float) * (size_t)ctx->stride, 12, n, hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->cloud.stride == 3) CK(hipMemcpyAsync(xyz_host, ctx->cloud.pts, 12 * n, hipMemcpyDeviceToHost, ctx->stream));
+    else CK(hipMemcpy2DAsync(xyz_host, 12, ctx->cloud.pts, sizeof(float) * (size_t)ctx->cloud.stride, 12, n, hipMemcpyDeviceToHost, ctx->stream));
     if (chan_host_or_null && K) {
-      const float* src = ctx->chan.p + (3 - ctx->chan.col0);
-      if ((size_t)ctx->chan.stride == K) CK(hipMemcpyAsync(chan_host_or_null, src, sizeof(float) * K * n, hipMemcpyDeviceToHost, ctx->stream));
-      else CK(hipMemcpy2DAsync(chan_host_or_null, sizeof(float) * K, src, sizeof(float) * (size_t)ctx->chan.stride, sizeof(float) * K, n, hipMemcpyDeviceToHost, ctx->stream));
+      const float* src = ctx->cloud.chan.p + (3 - ctx->cloud.chan.col0);
+      if ((size_t)ctx->cloud.chan.stride == K) CK(hipMemcpyAsync(chan_host_or_null, src, sizeof(float) * K * n, hipMemcpyDeviceToHost, ctx->stream));
+      else CK(hipMemcpy2DAsync(chan_host_or_null, sizeof(float) * K, src, sizeof(float) * (size_t)ctx->cloud.chan.stride, sizeof(float) * K, n, hipMemcpyDeviceToHost, ctx->stream));
     }
   }
   CK(hipStreamSynchronize(ctx->stream));

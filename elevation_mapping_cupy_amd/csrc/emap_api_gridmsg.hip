@@ -44,13 +44,7 @@ static int grid_publish(emap_ctx* ctx, const emap_grid_layer_ex* layers, int32_t
   CK(hipSetDevice(ctx->device));
   FLUSH();
   const size_t MM = (size_t)(ctx->prm.cell_n - 2) * (ctx->prm.cell_n - 2);
-  if ((size_t)n_layers * MM > ctx->grid_cap) {
-    CK(hipStreamSynchronize(ctx->stream));      // (nothing reads the old buffer any more: every call ends with a wait; kept for safety on a caller's stream)
-    if (ctx->grid_buf) CK(hipFree(ctx->grid_buf));
-    ctx->grid_buf = nullptr; ctx->grid_cap = 0;
-    CK(hipMalloc((void**)&ctx->grid_buf, sizeof(float) * (size_t)n_layers * MM));
-    ctx->grid_cap = (size_t)n_layers * MM;
-  }
+  { const int rc = grow(ctx, &ctx->grid_buf, &ctx->grid_cap, (size_t)n_layers * MM); if (rc) return rc; }
   GridArgs A; memset(&A, 0, sizeof A);
   A.n = n_layers; A.order = order; A.only_above = use_only_above_for_upper_bound ? 1 : 0; A.center_z = center_z;
   A.plane = ctx->ncells_alloc; A.sem_plane = ctx->ncells_alloc; A.normal = ctx->normal; A.sem = ctx->sem; A.out = ctx->grid_buf; A.plug = ctx->plane_buf;

@@ -2,13 +2,10 @@
 // sensor_msgs/Image are uploaded as they are and ONE launch computes the correspondence and fuses every channel -- the reference's node
 // converts the message to one float matrix per channel on the host (elevation_mapping_cupy/src/elevation_mapping_ros.cpp:375-446) and
 // input_image (EM/elevation_mapping.py:468-562) uploads the stack, then launches the correspondence kernel and one sampling kernel per
-// channel.  The bytes pass through two pinned slots and a device buffer of the camera path's OWN: the buffers of the doors that produce
-// a cloud (emap_api_depth.hip: owned_cloud_prepare) hold the bound cloud, which stays bound, and the small frames in flight keep raw
-// pointers into it.
+// channel.  The bytes pass through the context's image_stage (emap_host.h), the camera path's own.
 #include "emap_host.h"
 #include <cmath>
 #include <cstring>
-#include <functional>
 
 using namespace emap_host;
 
@@ -50,46 +47,16 @@ int emap_input_image_message(emap_ctx* ctx, const emap_image_msg_desc* d, const 
   const size_t L = (size_t)ctx->prm.cell_n * ctx->prm.cell_n;
   if (!ctx->img_uv) { CK(hipMalloc((void**)&ctx->img_uv, sizeof(float) * 2 * L)); CK(hipMalloc((void**)&ctx->img_valid, L)); }
 
-  // the next pinned slot: its copy of two calls ago is done (long done in a running stream)
-  const size_t total = (size_t)bytes;
-  const int sl = ctx->imsg_slot ^= 1;
-  if (!ctx->imsg_ev[sl]) CK(hipEventCreateWithFlags(&ctx->imsg_ev[sl], hipEventDisableTiming));
-  if (ctx->imsg_ev_on[sl]) CK(hipEventSynchronize(ctx->imsg_ev[sl]));
-  if (total > ctx->imsg_pin_cap[sl]) {
-    if (ctx->imsg_pin[sl]) CK(hipHostFree(ctx->imsg_pin[sl]));
-    ctx->imsg_pin[sl] = nullptr; ctx->imsg_pin_cap[sl] = 0; ctx->imsg_ev_on[sl] = false;
-    CK(hipHostMalloc((void**)&ctx->imsg_pin[sl], total, hipHostMallocDefault));
-    ctx->imsg_pin_cap[sl] = total;
-  }
-  if (total + EM_IMGMSG_SLACK > ctx->imsg_cap) {
-    CK(hipStreamSynchronize(ctx->stream));      // growing: the kernel of the frame before may still read the buffer
-    if (ctx->imsg_dev) CK(hipFree(ctx->imsg_dev));
-    ctx->imsg_dev = nullptr; ctx->imsg_cap = 0;
-    CK(hipMalloc((void**)&ctx->imsg_dev, total + EM_IMGMSG_SLACK));
-    ctx->imsg_cap = total + EM_IMGMSG_SLACK;
-  }
-  // as emap_bind_cloud_message copies its message: one memcpy and one DMA up to 2 MB, beyond it the worker threads chunk by chunk, each
-  // chunk's DMA -- on the context's stream, in order -- overlapping the copy of the next
-  unsigned char* pin = ctx->imsg_pin[sl];
-  const size_t chunk = (size_t)2 << 20;
-  if (total > chunk) { const int rc = upload_setup(ctx); if (rc) return rc; }
-  for (size_t o = 0; o < total; o += chunk) {
-    const size_t len = total - o < chunk ? total - o : chunk;
-    if (total <= chunk) memcpy(pin, data, len);
-    else ctx->workers->run([&](int w, int nw) {
-      const size_t per = ((len + nw - 1) / nw + 63) & ~(size_t)63, a = (size_t)w * per;
-      if (a < len) memcpy(pin + o + a, data + o + a, len - a < per ? len - a : per);
-    });
-    CK(hipMemcpyAsync(ctx->imsg_dev + o, pin + o, len, hipMemcpyHostToDevice, ctx->stream));
-  }
-  CK(hipEventRecord(ctx->imsg_ev[sl], ctx->stream));
-  ctx->imsg_ev_on[sl] = true;
+  // EM_IMGMSG_SLACK behind the device copy: the kernel's aligned loads run up to the message's end rounded up
+  Stage& st = ctx->image_stage;
+  { const int rc = stage_next(ctx, &st, (size_t)bytes, (size_t)bytes + EM_IMGMSG_SLACK); if (rc) return rc; }
+  { const int rc = stage_send(ctx, &st, data, (size_t)bytes); if (rc) return rc; }
 
   CamArgs A;
   memcpy(A.P, P, sizeof A.P); memcpy(A.K, K, sizeof A.K); memcpy(A.D, D, sizeof A.D); memcpy(A.center, center, sizeof A.center);
   A.x1 = x1; A.y1 = y1; A.z1 = z1; A.ih = (float)d->height; A.iw = (float)d->width; A.tol = ctx->img_tol_set ? ctx->img_tol : 0.10;
   ImgMsgArgs M; memset(&M, 0, sizeof M);
-  M.msg = ctx->imsg_dev; M.H = d->height; M.W = d->width; M.step = d->step; M.elem = d->elem; M.esize = esize; M.n_chan = d->n_chan;
+  M.msg = st.dev; M.H = d->height; M.W = d->width; M.step = d->step; M.elem = d->elem; M.esize = esize; M.n_chan = d->n_chan;
   M.big = d->is_bigendian ? 1 : 0; M.swap = d->swap_rb ? 1 : 0; M.n_specs = n_specs;
   for (int k = 0; k < n_specs; ++k) { M.e[k].kind = specs[k].kind; M.e[k].layer = specs[k].layer; M.e[k].plane = specs[k].plane; M.e[k].alpha = specs[k].alpha; }
   launch_image_frame(ctx->stream, ctx->kp, A, ctx->cells, ctx->img_uv, ctx->img_valid, M, ctx->sem, ctx->ncells_alloc);

@@ -23,15 +23,6 @@ size_t op_planes(const emap_plugin_op& o) {
 }
 size_t op_counters(const emap_plugin_op& o) { return o.type <= EMAP_PLUGIN_MAX_FILTER ? (size_t)o.i1 + 1 : 0; }
 
-template <class T> int grow(emap_ctx* ctx, T** buf, size_t* cap, size_t need) {
-  if (need <= *cap) return EMAP_OK;
-  CK(hipStreamSynchronize(ctx->stream));      // a chain enqueued earlier may still read the old buffer
-  if (*buf) CK(hipFree(*buf));
-  *buf = nullptr; *cap = 0;
-  CK(hipMalloc((void**)buf, sizeof(T) * need));
-  *cap = need;
-  return EMAP_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -42,7 +33,7 @@ int emap_plugin_planes(emap_ctx* ctx, int32_t n_planes) {
   CKARG(full_map(ctx), "emap_plugin_planes: single-strip contexts only");
   CK(hipSetDevice(ctx->device));
   const size_t L = plane_len(ctx);
-  if (n_planes > ctx->plane_cap) {
+  if (n_planes > ctx->plane_cap) {      // (not emap_host::grow: the planes already written are kept)
     float* nb = nullptr;
     CK(hipMalloc((void**)&nb, sizeof(float) * L * n_planes));
     hipError_t e = hipSuccess;

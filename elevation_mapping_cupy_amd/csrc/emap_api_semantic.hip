@@ -24,7 +24,7 @@ int emap_semantic_configure(emap_ctx* ctx, int32_t n_layers) {
     CK(hipMalloc((void**)&ctx->sem_col, sizeof(unsigned int) * n * 13));
     CK(hipMemsetAsync(ctx->sem_col, 0, sizeof(unsigned int) * n * 13, ctx->stream));
   }
-  if (n_layers > ctx->sem_layers) {      // grow, keeping existing layers (SemanticMap.add_layer, semantic_map.py:80-97)
+  if (n_layers > ctx->sem_layers) {      // grow, KEEPING the existing layers (SemanticMap.add_layer, semantic_map.py:80-97): not emap_host::grow, which drops the old contents
     float* ns = nullptr; double* nq = nullptr;
     CK(hipMalloc((void**)&ns, sizeof(float) * n * n_layers));
     CK(hipMalloc((void**)&nq, sizeof(double) * n * n_layers));
@@ -59,9 +59,9 @@ static int sem_spec_checked(emap_ctx* ctx, const emap_sem_spec* spec, SemSpec* o
   CKARG(spec->n_sum >= 0 && spec->n_sum <= SEM_MAX_CH && spec->n_col >= 0 && spec->n_col <= 4, "too many channels");
   CKARG(ctx->cnt_plane, "emap_semantic_configure must be called before the frame (the average pass records the counts)");
   for (int k = 0; k < spec->n_sum; ++k)
-    CKARG(spec->sum_layer[k] >= 0 && spec->sum_layer[k] < ctx->sem_layers && spec->sum_chan[k] >= 3 && spec->sum_chan[k] < ctx->n_cols, "bad channel/layer index");
+    CKARG(spec->sum_layer[k] >= 0 && spec->sum_layer[k] < ctx->sem_layers && spec->sum_chan[k] >= 3 && spec->sum_chan[k] < ctx->cloud.n_cols, "bad channel/layer index");
   for (int k = 0; k < spec->n_col; ++k)
-    CKARG(spec->col_layer[k] >= 0 && spec->col_layer[k] < ctx->sem_layers && spec->col_chan[k] >= 3 && spec->col_chan[k] < ctx->n_cols, "bad colour channel/layer index");
+    CKARG(spec->col_layer[k] >= 0 && spec->col_layer[k] < ctx->sem_layers && spec->col_chan[k] >= 3 && spec->col_chan[k] < ctx->cloud.n_cols, "bad colour channel/layer index");
   SemSpec& S = *out; memset(&S, 0, sizeof S); memcpy(&S, spec, sizeof *spec);
   int nk[4] = {0, 0, 0, 0};
   for (int k = 0; k < S.n_sum; ++k) { CKARG(S.sum_kind[k] >= 0 && S.sum_kind[k] <= 3, "bad fusion kind"); nk[S.sum_kind[k]]++; }
@@ -108,9 +108,9 @@ extern "C++" int emap_host::frame_sem_begin(emap_ctx* ctx, bool rays_on, Frame* 
   for (int k = 0; k < S.n_col; ++k) { cmin = std::min(cmin, S.col_chan[k]); cmax = std::max(cmax, S.col_chan[k]); }
   if (cmax - cmin >= 4) return EMAP_OK;
   fr->carry = true;
-  ctx->carry.c0 = cmin; ctx->carry.ncols = ctx->n_cols;
+  ctx->carry.c0 = cmin; ctx->carry.ncols = ctx->cloud.n_cols;
   // the de-interleaved (N, 4) channel matrix of an uploaded cloud: one aligned 16-byte load per point
-  ctx->carry.on = (ctx->chan.stride == 4 && ctx->chan.col0 == cmin && ((uintptr_t)ctx->chan.p & 15) == 0) ? 2 : 1;
+  ctx->carry.on = (ctx->cloud.chan.stride == 4 && ctx->cloud.chan.col0 == cmin && ((uintptr_t)ctx->cloud.chan.p & 15) == 0) ? 2 : 1;
   return EMAP_OK;
 }
 // End of the frame's fusion stages: whatever the tile kernel did not fuse itself (merged) runs now (the frame's counts are in cnt_plane)
@@ -138,12 +138,12 @@ static int semantic_update_impl(emap_ctx* ctx, const float R[9], const float t[3
       if (hipMemsetAsync(m, 0, sem_split_bytes(SEM_SPLIT_SLOTS), ctx->stream) != hipSuccess) { hipFree(m); ctx->err = "hipMemsetAsync(semantic split scratch)"; return EMAP_ERR_HIP; }
       ctx->sem_split_mem = m;
     }
-    launch_tile_semantic(ctx->stream, ctx->kp, ctx->bg, S, ctx->bin_recs, ctx->bin_rs, ctx->carry.on ? ctx->carry.c0 : -1, ctx->bin_tile_start, ctx->chan, ctx->n_pts,
+    launch_tile_semantic(ctx->stream, ctx->kp, ctx->bg, S, ctx->bin_recs, ctx->bin_rs, ctx->carry.on ? ctx->carry.c0 : -1, ctx->bin_tile_start, ctx->cloud.chan, ctx->cloud.n,
                          ctx->cnt_plane, ctx->sem, ctx->sem_alpha, ctx->ncells_alloc, ctx->split, ctx->sem_split_mem, SEM_SPLIT_SLOTS);
     CK(hipGetLastError());
     return EMAP_OK;
   }
-  launch_sem_points(ctx->stream, ctx->kp, make_pose(ctx, R, t), S, ctx->pts, ctx->n_pts, ctx->stride, ctx->chan, ctx->sem_sums, ctx->sem_col, ctx->ncells_alloc);
+  launch_sem_points(ctx->stream, ctx->kp, make_pose(ctx, R, t), S, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->cloud.chan, ctx->sem_sums, ctx->sem_col, ctx->ncells_alloc);
   launch_sem_finalize(ctx->stream, ctx->kp, S, ctx->cnt_plane, ctx->sem_sums, ctx->sem_col, ctx->sem, ctx->sem_alpha, ctx->ncells_alloc);
   CK(hipGetLastError());
   return EMAP_OK;
@@ -224,7 +224,7 @@ int emap_semantic_class_max(emap_ctx* ctx, const float R[9], const float t[3], i
   CKARG(ctx->strip.halo_rows == 0 && ctx->strip.row_count == ctx->prm.cell_n, "class_max: single-strip contexts only");
   NEED_POINTS();
   for (int k = 0; k < n_ch; ++k)
-    CKARG(layer[k] >= 0 && layer[k] < ctx->sem_layers && chan[k] >= 3 && chan[k] < ctx->n_cols, "bad channel/layer index");
+    CKARG(layer[k] >= 0 && layer[k] < ctx->sem_layers && chan[k] >= 3 && chan[k] < ctx->cloud.n_cols, "bad channel/layer index");
   CK(hipSetDevice(ctx->device));
   { int rc = ensure_alpha(ctx); if (rc) return rc; }
   hipStream_t st = ctx->stream;
@@ -236,7 +236,7 @@ int emap_semantic_class_max(emap_ctx* ctx, const float R[9], const float t[3], i
   CK(b_seen.alloc(2 * 65536));
   unsigned char* const d_seen = (unsigned char*)b_seen.d;
   CK(hipMemsetAsync(d_seen, 0, 2 * 65536, st));
-  launch_cmax_ids(st, ctx->kp, S, ctx->chan, ctx->n_pts, ctx->sem_alpha, plane, d_seen, d_seen + 65536);
+  launch_cmax_ids(st, ctx->kp, S, ctx->cloud.chan, ctx->cloud.n, ctx->sem_alpha, plane, d_seen, d_seen + 65536);
   CK(hipGetLastError());
   std::vector<unsigned char> seen(2 * 65536);
   CK(hipMemcpyAsync(seen.data(), d_seen, 2 * 65536, hipMemcpyDeviceToHost, st));
@@ -268,7 +268,7 @@ int emap_semantic_class_max(emap_ctx* ctx, const float R[9], const float t[3], i
   CK(hipMemsetAsync(d_new, 0, sizeof(float) * (size_t)n_ch * plane, st));
   CK(hipMemcpyAsync(d_pos, pos.data(), sizeof(int) * 65536, hipMemcpyHostToDevice, st));
   CK(hipMemcpyAsync(d_uniq, uniq.data(), sizeof(unsigned int) * U, hipMemcpyHostToDevice, st));
-  launch_cmax_sum(st, ctx->kp, make_pose(ctx, R, t), S, ctx->pts, ctx->n_pts, ctx->stride, ctx->chan, d_pos, d_sum, plane);
+  launch_cmax_sum(st, ctx->kp, make_pose(ctx, R, t), S, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->cloud.chan, d_pos, d_sum, plane);
   // (3) + (4): per layer the maximum and its class, the winners' planes zeroed in between; then the normalisation
   launch_cmax_select(st, ctx->kp, S, U, d_sum, plane, d_flags, d_flags + U, d_uniq, d_new, ctx->sem_alpha, ctx->sem);
   CK(hipGetLastError());
@@ -354,13 +354,7 @@ int emap_image_fuse(emap_ctx* ctx, int32_t kind, int32_t layer, const float* hos
   CKARG(n_planes >= (kind == 1 ? 3 : 1) && height > 0 && width > 0, "bad image shape");
   CK(hipSetDevice(ctx->device));
   const size_t need = (size_t)n_planes * height * width;
-  if (need > ctx->img_cap) {
-    CK(hipStreamSynchronize(ctx->stream));
-    if (ctx->img_buf) CK(hipFree(ctx->img_buf));
-    ctx->img_buf = nullptr; ctx->img_cap = 0;
-    CK(hipMalloc((void**)&ctx->img_buf, sizeof(float) * need));
-    ctx->img_cap = need;
-  }
+  { const int rc = grow(ctx, &ctx->img_buf, &ctx->img_cap, need); if (rc) return rc; }
   CK(hipMemcpyAsync(ctx->img_buf, host_image, sizeof(float) * need, hipMemcpyHostToDevice, ctx->stream));
   launch_image_fuse(ctx->stream, ctx->kp, kind, ctx->sem + (size_t)layer * ctx->ncells_alloc, ctx->img_buf, ctx->img_uv, ctx->img_valid,
                     (float)height, (float)width, alpha);

@@ -1,6 +1,8 @@
 // What the host files of the C ABI share (emap_api.hip: the core; emap_api_semantic.hip: semantic layers and the camera path;
-// emap_api_plugins.hip: the publish-time plugins on caller planes; emap_api_comm.hip: halos, the RCCL communicator, rays by ray):
-// the context, the frame record, the error macros, the one call-scoped device buffer and the few helpers that cross a file boundary.
+// emap_api_plugins.hip: the publish-time plugins on caller planes; emap_api_comm.hip: halos, the RCCL communicator, rays by ray; the
+// doors emap_api_{depth,cloudmsg,image_msg,gridmsg,plugchain}.hip): the context, the frame record, the error macros and the three
+// mechanisms every door is built from -- a buffer grown on demand (grow), caller bytes staged through pinned slots (Stage) and the
+// bound cloud (BoundCloud) -- each described where it is defined below, plus the few helpers that cross a file boundary.
 // Whatever has a symbol here lives in namespace emap_host, so that nothing can collide with a symbol of the program that loads the
 // library.  RCCL stays inside emap_api_comm.hip: the context holds the communicator and the bound entry points as opaque pointers.
 #pragma once
@@ -67,6 +69,29 @@ struct DevBuf {
   DevBuf& operator=(const DevBuf&) = delete;
   ~DevBuf() { if (d) hipFree(d); }
 };
+
+// The cloud the frame kernels read: bound by an upload, a caller's device pointers or a door that produces its cloud on the device.
+// One record, so that whoever has to remember a binding (the small-frame ring, sf_recover) copies it whole.
+struct BoundCloud {
+  const float* pts; long n; int stride;      // xyz: rows of `stride` floats (3 for a de-interleaved cloud)
+  long n_all;                                // size of the cloud the caller handed over (> n for a bucketed one): what every rank of a sharded map shares
+  ChanView chan; int n_cols;                 // its extra channels (emap_device.h: ChanView); n_cols = columns of the caller's matrix (3 + K)
+};
+// A de-interleaved cloud in ONE buffer: xyz as an (n, 3) matrix, the K channels as an (n, K) matrix behind it at a 256-byte boundary.
+struct CloudLayout { long chan_off, tot; };      // floats
+inline CloudLayout cloud_layout(long n, long K) {
+  const long off = K ? ((3 * n + 63) & ~63L) : 0;
+  return {off, K ? off + K * n : 3 * n};
+}
+
+// Caller bytes on their way to the device: two pinned slots, used in turn, and ONE device buffer.  A slot is written by the host while
+// the other's DMA may still run; its event says that its own DMA of two calls ago is done (long done in a running stream).  The device
+// buffer is overwritten in stream order, behind the kernel that read what the call before put there.  (stage_next, stage_send,
+// stage_free: emap_api.hip.)
+struct Stage {
+  unsigned char* pin[2]; size_t pin_cap[2]; hipEvent_t ev[2]; bool ev_on[2]; int slot;
+  unsigned char* dev; size_t dev_cap;        // bytes
+};
 }  // namespace emap_host
 
 struct emap_ctx {
@@ -82,7 +107,7 @@ struct emap_ctx {
   AccF* acc; AccR* accr;
   float* trav_in; float* normal;   // normal: 3 planes of ncells_alloc
   float* scratch;                  // one plane (get/set staging)
-  float* plug_buf; size_t plug_cap; unsigned int* plug_cnt; int plug_cnt_cap;   // plane scratch of the publish-time plugins (kept between calls)
+  float* plug_buf; size_t plug_cap; unsigned int* plug_cnt; size_t plug_cnt_cap;   // plane scratch of the publish-time plugins (kept between calls)
   ErrSlot* slots; FrameDev* frame;
   RayTab rt; float* ray_S; unsigned short* ray_lut;
   unsigned long long* inert;       // 1 bit per owned cell (rows of ceil(C/64) words), written by k_commit / k_tile_fuse<true, true>
@@ -108,14 +133,15 @@ struct emap_ctx {
   // their fate and, after an abort, re-runs them in order on the chain of launches.
   unsigned int sf_epoch; volatile unsigned int* sf_host; unsigned int* sf_host_dev; unsigned int* sf_poison;
   FrameDev* frame_save;            // the frame record as the gate of the last k_small_frame found it
-  struct SfFrame { unsigned int epoch; float R[9], t[3]; double pn, on; Moves mv; const float* pts; long n_pts, n_pts_all; int stride; ChanView chan; int n_cols; };
+  struct SfFrame { unsigned int epoch; float R[9], t[3]; double pn, on; Moves mv; emap_host::BoundCloud cloud; };
   enum { SF_RING = 8 };
   SfFrame sf_ring[SF_RING]; int sf_head, sf_count;
   bool sf_redo;                    // inside sf_recover: frames take the chain of launches
   unsigned int sf_aborts;          // frames re-run so far (emap_small_frame_aborts)
   int update_path;                 // emap_last_update_path
-  BinGeo bg; BinRec* bin_recs; BinStg* bin_own; unsigned int* bin_own_cnt; long bin_own_cap; bool bin_strip;   // bin_own*: staged records of the owned points per block (strip contexts without a visibility pass)
-  unsigned int* bin_hist; unsigned int* bin_tile_total; unsigned int* bin_tile_start; long bin_cap; size_t bin_hist_cap;      // bin_cap: 16-byte units
+  BinGeo bg; BinRec* bin_recs; size_t bin_recs_cap; bool bin_strip;
+  float4* bin_own; size_t bin_own_cap; unsigned int* bin_own_cnt;   // staged 16-byte records (BinStg: emap_binned.hip) of the owned points per block (strip contexts without a visibility pass); bin_own_cnt: BIN_MAX_B words, sized once
+  unsigned int* bin_hist; size_t bin_hist_cap; unsigned int* bin_tile_total; unsigned int* bin_tile_start;
   // The semantic fusion declared for the NEXT whole frame (emap_frame_semantics): run inside the frame.  A frame that can CARRIES the
   // channels in 32-byte sorted records (bin_rs = 2, carry: which columns) and fuses them in the tile kernel itself;
   // every other frame runs the stand-alone semantic kernels before it returns -- the result is the same either way.
@@ -127,25 +153,20 @@ struct emap_ctx {
   float* sem_alpha;   // class_bayesian pseudo-counts (the reference's persistent new_map layers), sem_layers planes, on demand
   int sem_layers; float* sem; double* sem_sums; unsigned int* sem_col; unsigned int* cnt_plane;
   // point cloud
-  float* pts_dev[2]; long pts_cap[2];      // owned device buffers (floats), ping-pong between consecutive uploads
-  float* pts_pin[2]; long pin_cap[2];      // pinned host slots the clouds are converted / copied into
+  float* pts_dev[2]; size_t pts_cap[2];    // owned device buffers (floats), ping-pong between consecutive uploads
+  float* pts_pin[2]; size_t pin_cap[2];    // pinned host slots the clouds are converted / copied into
   hipEvent_t ev_copied[2], ev_used[2];     // DMA of slot done (copy stream) / the frame that read the slot's device buffer done (main stream)
   int up_slot; bool up_used[2]; hipStream_t copy_stream; emap_host::Workers* workers;
-  const float* pts; long n_pts; int stride;         // xyz of the bound cloud: rows of `stride` floats (3 for a de-interleaved cloud)
-  long n_pts_all;                                   // size of the cloud the caller handed over (> n_pts for a bucketed one): what every rank of a sharded map shares
+  emap_host::BoundCloud cloud;
   bool pts_bucketed; float bucket_R[9], bucket_t[3]; int bucket_org_r;   // the bound cloud only holds the points that can land in this strip's rows under this pose (emap_upload_points_strip)
-  ChanView chan; int n_cols;                        // its extra channels (emap_device.h: ChanView); n_cols = columns of the caller's matrix (3 + K)
-  int* tail_idx; unsigned char* tail_flags; long tail_cap;
-  // depth-image input (emap_api_depth.hip): the cloud k_depth_cloud writes lives in ONE owned buffer (stream order: the kernels of the
-  // frame before precede the overwrite); the caller's images pass through two pinned slots into one device buffer
-  float* depth_cloud; long depth_cloud_cap;                   // floats
-  unsigned char* depth_img; size_t depth_img_cap;             // bytes
-  unsigned char* depth_pin[2]; size_t depth_pin_cap[2]; hipEvent_t depth_ev[2]; bool depth_ev_on[2]; int depth_slot;   // depth_ev: the slot's H2D copies are done
-  // image message input (emap_api_image_msg.hip): the message bytes pass through two pinned slots of the camera path's OWN into one
-  // device buffer (stream order: the kernel of the frame before precedes the overwrite) -- never the owned-cloud buffers above, whose
-  // cloud stays bound while a camera frame runs
-  unsigned char* imsg_dev; size_t imsg_cap;                   // bytes (EM_IMGMSG_SLACK included)
-  unsigned char* imsg_pin[2]; size_t imsg_pin_cap[2]; hipEvent_t imsg_ev[2]; bool imsg_ev_on[2]; int imsg_slot;   // imsg_ev: the slot's H2D copies are done
+  int* tail_idx; size_t tail_idx_cap; unsigned char* tail_flags; size_t tail_flags_cap;
+  // the doors that produce their cloud on the device (depth image, PointCloud2 message): the caller's bytes pass through cloud_stage,
+  // the cloud the kernel writes lives in ONE owned buffer (stream order: the kernels of the frame before precede the overwrite).  Only one
+  // cloud is bound at a time, so both doors share them.
+  emap_host::Stage cloud_stage; float* own_cloud; size_t own_cloud_cap;      // floats
+  // image message input: a Stage of the camera path's OWN -- never cloud_stage or own_cloud, whose cloud stays bound while a camera
+  // frame runs and which the small frames in flight keep raw pointers into
+  emap_host::Stage image_stage;
   // GridMap message output (emap_api_gridmsg.hip): the planes k_grid_map writes, grown on demand (`scratch` stays the single plane it is)
   float* grid_buf; size_t grid_cap;                           // floats
   // publish-time plugins on resident planes (emap_api_plugchain.hip): plane_n planes of cell_n x cell_n floats, each the RAW output of a
@@ -172,7 +193,7 @@ struct emap_ctx {
   hipStream_t comm_stream; hipEvent_t ev_ready, ev_done; double* comm_sums;   // [0..1] local err_sum / err_cnt, [2..3] totals, [4..36) emap_comm_allreduce_host
   // the un-shifted normal planes after a row shift (normal_exchange): a row-aligned copy of the rows this strip's cells belong to
   std::vector<int> cut_begin, cut_count;   // every rank's owned PHYSICAL rows (gathered by emap_comm_init)
-  float* nlag_buf; long nlag_cap;          // 3 planes of row_count x cell_n
+  float* nlag_buf; size_t nlag_cap;        // 3 planes of row_count x cell_n
   bool cuts_ok;                            // the gathered strips tile the map
   std::string err;
 };
@@ -219,12 +240,43 @@ int halo_exchange_start(emap_ctx* ctx);
 int normal_exchange(emap_ctx* ctx);
 bool rays_by_ray(const emap_ctx* ctx);
 int rays_by_ray_pass(emap_ctx* ctx, const float R[9], const float t[3], const Frame* f);
-// emap_api_depth.hip: pinned slot, device copy of the caller's bytes (img_bytes) and owned cloud (tot floats) of the doors that produce their cloud
-int owned_cloud_prepare(emap_ctx* ctx, size_t pin_bytes, size_t img_bytes, long tot, int* slot);
+// emap_api_depth.hip: the next slot of cloud_stage and the owned cloud (tot floats) of the doors that produce their cloud
+int owned_cloud_prepare(emap_ctx* ctx, size_t pin_bytes, size_t dev_bytes, long tot);
+
+// Stage (above).  stage_next: the other slot becomes the current one, its DMA of two calls ago is waited for, and it holds pin_bytes,
+// the device buffer dev_bytes.  stage_send: `bytes` from src into the current slot (one memcpy up to 2 MB, beyond that the worker threads
+// chunk by chunk) and on to the device buffer, a DMA behind each chunk, in order on ctx->stream; src == nullptr sends what the caller
+// placed in the slot itself, in one DMA.
+int stage_next(emap_ctx* ctx, Stage* s, size_t pin_bytes, size_t dev_bytes);
+int stage_send(emap_ctx* ctx, Stage* s, const void* src, size_t bytes);
+void stage_free(Stage* s);
+
+// A context buffer of `need` elements, grown on demand; the old contents are NOT kept.  Kernels enqueued earlier may still read the old
+// buffer, so the stream is drained before it is freed -- unless the caller's own events cover every reader (Grow::covered: the
+// ping-pong buffers of upload_impl) or the buffer is a pinned host slot whose DMA the caller has waited for (Grow::pinned).  An
+// allocation that fails leaves *buf == nullptr, *cap == 0.
+enum class Grow { drain, covered, pinned };
+template <class T> int grow(emap_ctx* ctx, T** buf, size_t* cap, size_t need, Grow how = Grow::drain) {
+  if (need <= *cap) return EMAP_OK;
+  if (how == Grow::drain) CK(hipStreamSynchronize(ctx->stream));
+  if (*buf) CK(how == Grow::pinned ? hipHostFree(*buf) : hipFree(*buf));
+  *buf = nullptr; *cap = 0;
+  void* m = nullptr;
+  CK(how == Grow::pinned ? hipHostMalloc(&m, sizeof(T) * need, hipHostMallocDefault) : hipMalloc(&m, sizeof(T) * need));
+  *buf = static_cast<T*>(m); *cap = need;
+  return EMAP_OK;
+}
+
+// Binds a de-interleaved cloud: xyz (n, 3) at `xyz`, K channels (n, K) at `chan` (CloudLayout: xyz + chan_off; or a buffer of the
+// caller's), whole and unbucketed unless the caller says otherwise afterwards.  (Interleaved rows: emap_set_points_device.)
+inline void bind_split_cloud(emap_ctx* ctx, const float* xyz, const float* chan, long n, long n_all, int K) {
+  ctx->cloud = BoundCloud{xyz, n, 3, n_all, ChanView{K ? chan : xyz, K ? K : 3, K ? 3 : 0}, 3 + K};
+  ctx->pts_bucketed = false;
+}
 }  // namespace emap_host
 
 // Every entry point that reads or changes the map, the drift record or a cloud buffer settles the small frames in flight first
 // (emap_api.hip: sf_settle); map shifts are lazy (emap_shift) and written out before anything but a frame kernel looks at the cells.
 #define SF_CHECK() do { if (ctx->sf_count > 0) { int rc_sf_ = emap_host::sf_settle(ctx); if (rc_sf_) return rc_sf_; } } while (0)
 #define FLUSH() do { int rc_ = emap_host::flush_moves(ctx); if (rc_) return rc_; } while (0)
-#define NEED_POINTS() do { if (!ctx->pts && ctx->n_pts) { ctx->err = "no point cloud bound"; return EMAP_ERR_NO_POINTS; } } while (0)
+#define NEED_POINTS() do { if (!ctx->cloud.pts && ctx->cloud.n) { ctx->err = "no point cloud bound"; return EMAP_ERR_NO_POINTS; } } while (0)
