@@ -214,6 +214,16 @@ int emap_host::flush_moves(emap_ctx* ctx) {
   return EMAP_OK;
 }
 
+// The last frame's stencil pass, left pending by frame_impl for the next frame's fused launch: launched now, exactly as the frame would
+// have launched it.  On an error the pass stays pending.
+static int post_part_impl(emap_ctx* ctx, int32_t part);
+int emap_host::post_settle(emap_ctx* ctx) {
+  if (!ctx->post_pending) return EMAP_OK;
+  const int rc = post_part_impl(ctx, 0);
+  if (rc == EMAP_OK) ctx->post_pending = false;
+  return rc;
+}
+
 // rows between the origin the normal planes were written with and the map's origin (signed, shortest way round)
 int emap_host::normal_row_lag(const emap_ctx* ctx) {
   const int C = ctx->prm.cell_n;
@@ -296,6 +306,7 @@ const char* emap_last_error(const emap_ctx* ctx) { return ctx ? ctx->err.c_str()
 int emap_destroy(emap_ctx* ctx) {
   if (!ctx) return EMAP_OK;
   hipSetDevice(ctx->device);
+  if (ctx->post_pending) post_settle(ctx);      // (the stream ends with the complete frame, whoever looks at it next)
   if (ctx->stream) hipStreamSynchronize(ctx->stream);
   hipFree(ctx->cells.hot); hipFree(ctx->cells.cold); hipFree(ctx->acc); hipFree(ctx->accr); hipFree(ctx->trav_in);
   hipFree(ctx->normal); hipFree(ctx->scratch); hipFree(ctx->plug_buf); hipFree(ctx->plug_cnt); hipFree(ctx->slots); hipFree(ctx->frame); hipFree(ctx->cnt_sync);
@@ -400,7 +411,9 @@ int emap_set_params(emap_ctx* ctx, const emap_params* params) {
 }
 
 int emap_sync(emap_ctx* ctx) {
-  CKARG(ctx, "null ctx"); CK(hipSetDevice(ctx->device)); CK(hipStreamSynchronize(ctx->stream));
+  CKARG(ctx, "null ctx"); CK(hipSetDevice(ctx->device));
+  if (ctx->post_pending) SF_CHECK();            // the last frame's stencil pass is queued before the wait
+  CK(hipStreamSynchronize(ctx->stream));
   if (ctx->sf_count > 0) { SF_CHECK(); CK(hipStreamSynchronize(ctx->stream)); }      // (an aborted small frame is re-run before the caller is told the stream is idle)
   return EMAP_OK;
 }
@@ -532,7 +545,7 @@ static int upload_impl(emap_ctx* ctx, const void* host, int64_t n, int64_t strid
 int emap_upload_points(emap_ctx* ctx, const void* host, int64_t n, int64_t stride, int dtype) {
   CKARG(ctx, "null ctx");
   CKARG(n >= 0 && stride >= 3 && stride < 4096 && (dtype == 0 || dtype == 1), "bad point buffer description");
-  CKARG(n == 0 || host, "null host buffer");
+  CKARG(n == 0 || host, "null host buffer"); SF_CHECK();
   return upload_impl(ctx, host, n, stride, dtype, nullptr, nullptr);
 }
 
@@ -544,7 +557,7 @@ int emap_upload_points(emap_ctx* ctx, const void* host, int64_t n, int64_t strid
 int emap_upload_points_strip(emap_ctx* ctx, const void* host, int64_t n, int64_t stride, int dtype, const float R[9], const float t[3], int64_t* n_kept) {
   CKARG(ctx && R && t, "null argument");
   CKARG(n >= 0 && stride >= 3 && stride < 4096 && (dtype == 0 || dtype == 1), "bad point buffer description");
-  CKARG(n == 0 || host, "null host buffer");
+  CKARG(n == 0 || host, "null host buffer"); SF_CHECK();
   if (ctx->strip.row_count >= ctx->prm.cell_n) return upload_impl(ctx, host, n, stride, dtype, nullptr, n_kept);
   const StripKeep keep(ctx, R, t);
   int rc = upload_impl(ctx, host, n, stride, dtype, &keep, n_kept);
@@ -559,7 +572,7 @@ int emap_upload_points_strip(emap_ctx* ctx, const void* host, int64_t n, int64_t
 int emap_strip_point_mask(emap_ctx* ctx, const void* host, int64_t n, int64_t stride, int dtype, const float R[9], const float t[3], uint8_t* keep_out) {
   CKARG(ctx && R && t && keep_out, "null argument");
   CKARG(n >= 0 && stride >= 3 && stride < 4096 && (dtype == 0 || dtype == 1), "bad point buffer description");
-  CKARG(n == 0 || host, "null host buffer");
+  CKARG(n == 0 || host, "null host buffer"); SF_CHECK();
   const bool whole = ctx->strip.row_count >= ctx->prm.cell_n;
   const StripKeep keep(ctx, R, t);
   for (int64_t i = 0; i < n; ++i) {
@@ -574,7 +587,7 @@ int emap_strip_point_mask(emap_ctx* ctx, const void* host, int64_t n, int64_t st
 // A device-resident cloud the caller bucketed itself (with emap_strip_point_mask's predicate, for THIS pose): declares it, so that the
 // frame checks pose and ray mode as for an uploaded one.
 int emap_declare_points_bucketed(emap_ctx* ctx, const float R[9], const float t[3], int64_t n_all) {
-  CKARG(ctx && R && t && n_all >= ctx->cloud.n, "bad argument");
+  CKARG(ctx && R && t && n_all >= ctx->cloud.n, "bad argument"); SF_CHECK();
   if (ctx->strip.row_count >= ctx->prm.cell_n) return EMAP_OK;
   ctx->pts_bucketed = true; ctx->cloud.n_all = (long)n_all; ctx->bucket_org_r = ctx->kp.org_r;
   memcpy(ctx->bucket_R, R, sizeof ctx->bucket_R); memcpy(ctx->bucket_t, t, sizeof ctx->bucket_t);
@@ -715,7 +728,7 @@ int emap_set_scatter_mode(emap_ctx* ctx, int32_t mode) {
 }
 
 int emap_set_ray_mode(emap_ctx* ctx, int32_t mode) {
-  CKARG(ctx && mode >= 0 && mode <= 2, "ray mode: 0 auto, 1 by row, 2 by ray");
+  CKARG(ctx && mode >= 0 && mode <= 2, "ray mode: 0 auto, 1 by row, 2 by ray"); SF_CHECK();
   ctx->ray_mode = mode;
   return EMAP_OK;
 }
@@ -769,7 +782,23 @@ static int count_impl(emap_ctx* ctx, const float R[9], const float t[3], const F
     const Pose pose = make_pose(ctx, R, t);
     BinStg* own = ctx->bin_strip ? reinterpret_cast<BinStg*>(ctx->bin_own) : nullptr;
     if (tm) CK(hipEventRecord(ctx->ev[ST_HIST], ctx->stream));
-    launch_bin_hist(ctx->stream, ctx->kp, pose, ctx->bg, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->bin_hist, own, ctx->bin_own_cnt);
+    // The stencil pass the frame before left pending runs in ONE grid with this frame's histogram (k_post_hist) when the workgroups of
+    // both are resident together -- the launcher asks the occupancy calculator; EMAP_POST_FUSE_MAX_WG (test hook, read per frame) lowers
+    // the bound.  Otherwise the pass is launched first and the frame runs the launches it always ran.
+    bool hist_done = false;
+    if (ctx->post_pending) {
+      if (f && !tm && !own && ctx->kp.mv.n == 0) {
+        long max_wg = 0;
+        if (const char* e = getenv("EMAP_POST_FUSE_MAX_WG")) max_wg = atol(e);
+        hist_done = launch_post_hist(ctx->stream, ctx->device, ctx->kp, ctx->prm.w1, ctx->prm.w2, ctx->prm.w3, ctx->prm.w_out, ctx->cells, ctx->trav_in, ctx->normal,
+                                     ctx->ncells_alloc, ctx->prm.dilation_size, pose, ctx->bg, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->bin_hist, max_wg);
+      }
+      if (hist_done) {
+        ctx->post_pending = false; ++ctx->post_fused;
+        ctx->kp.norg_r = ctx->torg_r = ctx->kp.org_r; ctx->kp.norg_c = ctx->torg_c = ctx->kp.org_c;      // outputs carry the current origin (post_part_impl)
+      } else if ((rc = post_settle(ctx))) return rc;
+    }
+    if (!hist_done) launch_bin_hist(ctx->stream, ctx->kp, pose, ctx->bg, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->bin_hist, own, ctx->bin_own_cnt);
     if (tm) CK(hipEventRecord(ctx->ev[ST_SCAN], ctx->stream));
     // heavy tiles are split only when k_tile_count runs in this frame (it leaves the per-cell counts k_tile_fuse's parts need)
     static const bool split_off = getenv("EMAP_SPLIT") && atoi(getenv("EMAP_SPLIT")) == 0;      // A/B and test hook
@@ -806,6 +835,7 @@ static int count_impl(emap_ctx* ctx, const float R[9], const float t[3], const F
     if (tm) CK(hipEventRecord(ctx->ev[ST_GATE], ctx->stream));        // the "gate" stage = per-tile error sums + k_gate
     if (gate_possible) launch_tile_count(ctx->stream, ctx->kp, ctx->bg, ctx->bin_recs, ctx->bin_rs, ctx->bin_tile_start, ctx->cells, ctx->slots, ctx->split, ctx->cloud.n);
   } else {
+    { const int rc = post_settle(ctx); if (rc) return rc; }
     ctx->carry.on = 0;
     if (tm) for (int e = ST_HIST; e <= ST_SCATTER; ++e) CK(hipEventRecord(ctx->ev[e], ctx->stream));
     // whole frames (emap_update) on this path: the drift gate rides in k_count's last workgroup, one launch less in a chain of six
@@ -1016,7 +1046,7 @@ int emap_dilate(emap_ctx* ctx) {          // dilation_filter_kernel alone: trave
   return EMAP_OK;
 }
 
-int emap_traversability_normals(emap_ctx* ctx) { return emap_post_part(ctx, 0); }     // (recomputes the dilation it consumes: same values)
+int emap_traversability_normals(emap_ctx* ctx) { CKARG(ctx, "null ctx"); SF_CHECK(); return emap_post_part(ctx, 0); }     // (recomputes the dilation it consumes: same values)
 
 // dilation + traversability + normals in one launch.  part: 0 = whole strip,
 // 1 = only the rows that do not depend on halo rows (can run while the halo exchange is in flight),
@@ -1038,7 +1068,7 @@ static int post_part_impl(emap_ctx* ctx, int32_t part) {      // (inside a frame
   CK(hipGetLastError());
   return EMAP_OK;
 }
-int emap_post(emap_ctx* ctx) { return emap_post_part(ctx, 0); }
+int emap_post(emap_ctx* ctx) { CKARG(ctx, "null ctx"); SF_CHECK(); return emap_post_part(ctx, 0); }
 
 int emap_update_variance(emap_ctx* ctx) { CKARG(ctx, "null ctx"); SF_CHECK(); CK(hipSetDevice(ctx->device)); launch_var_time(ctx->stream, ctx->kp, ctx->cells, 1, 0); ctx->kp.mv.n = 0; CK(hipGetLastError()); return EMAP_OK; }
 int emap_update_time(emap_ctx* ctx) { CKARG(ctx, "null ctx"); SF_CHECK(); CK(hipSetDevice(ctx->device)); launch_var_time(ctx->stream, ctx->kp, ctx->cells, 0, 1); ctx->kp.mv.n = 0; CK(hipGetLastError()); return EMAP_OK; }
@@ -1075,7 +1105,7 @@ static int plane_view(emap_ctx* ctx, int plane, float* host, bool to_device) { S
 }
 
 int emap_get_layer(emap_ctx* ctx, int plane, float* host_out) {
-  CKARG(ctx && host_out && plane >= 0 && plane < EMAP_PLANE_COUNT, "bad argument");
+  CKARG(ctx && host_out && plane >= 0 && plane < EMAP_PLANE_COUNT, "bad argument"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   return plane_view(ctx, plane, host_out, false);
 }
@@ -1094,7 +1124,7 @@ int emap_publish_layer(emap_ctx* ctx, int32_t kind, float center_z, int32_t use_
 }
 
 int emap_set_layer(emap_ctx* ctx, int plane, const float* host_in) {
-  CKARG(ctx && host_in && plane >= 0 && plane < EMAP_PLANE_COUNT, "bad argument");
+  CKARG(ctx && host_in && plane >= 0 && plane < EMAP_PLANE_COUNT, "bad argument"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   return plane_view(ctx, plane, const_cast<float*>(host_in), true);
 }
@@ -1145,6 +1175,7 @@ int emap_update(emap_ctx* ctx, const float R[9], const float t[3], double positi
   return run_frame(ctx, R, t, position_noise, orientation_noise, stats, false);
 }
 int emap_update_sharded(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise, emap_stats* stats) {
+  if (ctx && ctx->post_pending) { const int rc = post_settle(ctx); if (rc) return rc; }      // (a sharded frame never takes a pending pass along)
   return run_frame(ctx, R, t, position_noise, orientation_noise, stats, true);
 }
 static int frame_impl(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise, emap_stats* stats, bool sharded) {
@@ -1161,7 +1192,10 @@ static int frame_impl(emap_ctx* ctx, const float R[9], const float t[3], double 
   static const bool sf_env_off = getenv("EMAP_SMALL_FRAME") && atoi(getenv("EMAP_SMALL_FRAME")) == 0;      // A/B and test hook
   const int sf_grid = (!sharded && !sf_env_off && !ctx->sf_redo && !takes_bins(ctx, ctx->cloud.n_all) && ctx->cnt_sync && !ctx->pts_bucketed && !rays_on && !ctx->fsem_set)
                       ? small_frame_grid(ctx->kp, ctx->cloud.n) : 0;
-  if (sf_grid == 0) SF_CHECK();                 // (a frame on any other path: the small frames in flight are settled first)
+  if (sf_grid == 0) SF_SETTLE_FRAMES();         // (a frame on any other path: the small frames in flight are settled first)
+  // The stencil pass of the frame before may be pending (below).  A binned whole-map frame takes it into its histogram launch
+  // (count_impl); every other frame -- a small-frame launch, the atomic path, a sharded or timed frame -- launches it first.
+  if (ctx->post_pending && !(!sharded && sf_grid == 0 && !tm && ctx->cloud.n > 0 && takes_bins(ctx, ctx->cloud.n_all)) && (rc = post_settle(ctx))) return rc;
   Frame fr; memset(&fr, 0, sizeof fr);
   if ((rc = frame_sem_begin(ctx, rays_on, &fr))) return rc;
   fr.gate_possible = p.enable_drift_compensation && (position_noise > p.position_noise_thresh || orientation_noise > p.orientation_noise_thresh);
@@ -1251,7 +1285,16 @@ static int frame_impl(emap_ctx* ctx, const float R[9], const float t[3], double 
     if ((rc = post_part_impl(ctx, 1))) return rc;                                                   // ... overlapped with the interior tiles
     CK(hipStreamWaitEvent(ctx->stream, ctx->ev_done, 0));
     if ((rc = post_part_impl(ctx, 2))) return rc;
-  } else if ((rc = post_part_impl(ctx, 0))) return rc;
+  } else {
+    // A whole-map frame on the binned path whose stencil launch is the plain k_post with 16- or 32-row tiles leaves the pass PENDING: the
+    // next such frame runs it beside its own histogram (count_impl, k_post_hist), anything else that enters the library launches it
+    // first (SF_CHECK).  EMAP_POST_DEFER=0 (read per frame: a test toggles it) launches it here, as every other frame does.
+    bool defer = !sharded && ctx->frame_binned && !tm && ctx->kp.mv.n == 0 && ctx->strip.row_count == p.cell_n && ctx->strip.halo_rows == 0 &&
+                 post_hist_tile_rows(ctx->kp, p.dilation_size) != 0;
+    if (defer) { if (const char* e = getenv("EMAP_POST_DEFER")) defer = atoi(e) != 0; }
+    if (defer) ctx->post_pending = true;
+    else if ((rc = post_part_impl(ctx, 0))) return rc;
+  }
   STAGE(ST_N);
 #undef STAGE
   if (tm) {
@@ -1265,13 +1308,14 @@ static int frame_impl(emap_ctx* ctx, const float R[9], const float t[3], double 
 // ---- timing -----------------------------------------------------------------------------------------------------
 int emap_timer_begin(emap_ctx* ctx) { CKARG(ctx, "null ctx"); CK(hipSetDevice(ctx->device)); CK(hipEventRecord(ctx->t0, ctx->stream)); return EMAP_OK; }
 int emap_timer_end(emap_ctx* ctx, float* ms) {
-  CKARG(ctx && ms, "null argument");
+  CKARG(ctx && ms, "null argument"); SF_CHECK();      // (the interval ends behind the complete last frame)
   CK(hipSetDevice(ctx->device));
   CK(hipEventRecord(ctx->t1, ctx->stream)); CK(hipEventSynchronize(ctx->t1)); CK(hipEventElapsedTime(ms, ctx->t0, ctx->t1));
   return EMAP_OK;
 }
 int emap_enable_stage_timing(emap_ctx* ctx, int enable) { CKARG(ctx, "null ctx"); ctx->stage_timing = enable != 0; ctx->want_ray_stats = enable > 1; return EMAP_OK; }
 int emap_small_frame_aborts(emap_ctx* ctx, uint32_t* frames) { CKARG(ctx && frames, "null argument"); SF_CHECK(); *frames = ctx->sf_aborts; return EMAP_OK; }
+int emap_post_fused_launches(emap_ctx* ctx, uint32_t* launches) { CKARG(ctx && launches, "null argument"); SF_CHECK(); *launches = ctx->post_fused; return EMAP_OK; }
 int emap_last_update_path(emap_ctx* ctx, int32_t* path) { CKARG(ctx && path, "null argument"); *path = ctx->update_path; return EMAP_OK; }
 int emap_get_stage_times(emap_ctx* ctx, float ms_out[10]) { CKARG(ctx && ms_out, "null argument"); for (int i = 0; i < ST_N; ++i) ms_out[i] = ctx->stage_ms[i]; return EMAP_OK; }
 

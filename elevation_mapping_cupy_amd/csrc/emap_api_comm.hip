@@ -25,7 +25,7 @@ extern "C" {
 
 // ---- halos ----------------------------------------------------------------------------------------------------
 int emap_halo_bytes(emap_ctx* ctx, int64_t* bytes_per_side) {
-  CKARG(ctx && bytes_per_side, "null argument");
+  CKARG(ctx && bytes_per_side, "null argument"); SF_CHECK();
   *bytes_per_side = (int64_t)ctx->strip.halo_rows * ctx->prm.cell_n * (int64_t)sizeof(float4);      // the cold half-cell plane only (see halo_exchange_start)
   return EMAP_OK;
 }
@@ -51,7 +51,7 @@ int emap_halo_unpack(emap_ctx* ctx, int side, const float* dev_buf) {
 
 // boundary rows of the three normal planes (3 x halo_rows x cell_n floats per side) for the exchange after a row shift
 // (see normal_exchange); emap_normal_row_lag tells the caller whether it is due
-int emap_normal_row_lag(emap_ctx* ctx, int32_t* lag) { CKARG(ctx && lag, "null argument"); *lag = normal_row_lag(ctx); return EMAP_OK; }
+int emap_normal_row_lag(emap_ctx* ctx, int32_t* lag) { CKARG(ctx && lag, "null argument"); SF_CHECK(); *lag = normal_row_lag(ctx); return EMAP_OK; }
 int emap_normal_halo_pack(emap_ctx* ctx, int side, float* dev_buf) {
   CKARG(ctx && dev_buf && (side == 0 || side == 1), "bad argument"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
@@ -119,7 +119,7 @@ int emap_comm_init(emap_ctx* ctx, const char* rccl_path, const uint8_t id[128], 
   CKARG(ctx && id && world >= 1 && rank >= 0 && rank < world, "bad rank / world");
   CKARG(world <= 16, "at most 16 ranks");                    // (before anything collective: every rank sees the same `world`)
   CKARG(!ctx->rccl, "communicator already initialised");
-  CKARG(world == 1 || ctx->strip.halo_rows > 0, "a strip of a multi-rank map needs halo rows");
+  CKARG(world == 1 || ctx->strip.halo_rows > 0, "a strip of a multi-rank map needs halo rows"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   std::string why;
   RcclApi* a = rccl_open(rccl_path, &why);
@@ -185,6 +185,7 @@ int emap_comm_init(emap_ctx* ctx, const char* rccl_path, const uint8_t id[128], 
 int emap_comm_destroy(emap_ctx* ctx) {
   if (!ctx || !ctx->rccl) return EMAP_OK;
   hipSetDevice(ctx->device);
+  if (ctx->post_pending) post_settle(ctx);
   if (ctx->comm_stream) hipStreamSynchronize(ctx->comm_stream);
   if (ctx->stream) hipStreamSynchronize(ctx->stream);
   if (ctx->comm) ctx->rccl->CommDestroy(ctx->comm);
@@ -462,13 +463,13 @@ extern "C++" int emap_host::drift_allreduce(emap_ctx* ctx) {
 }
 
 int emap_comm_wire_bytes(emap_ctx* ctx, uint64_t* bytes) {
-  CKARG(ctx && bytes, "null argument");
+  CKARG(ctx && bytes, "null argument"); SF_CHECK();
   *bytes = (uint64_t)ctx->wire_bytes;
   return EMAP_OK;
 }
 
 int emap_comm_count(emap_ctx* ctx, int32_t* ranks) {
-  CKARG(ctx && ranks && ctx->rccl && ctx->comm, "emap_comm_init has not been called");
+  CKARG(ctx && ranks && ctx->rccl && ctx->comm, "emap_comm_init has not been called"); SF_CHECK();
   int n = 0;
   CKN(ctx->rccl->CommCount(ctx->comm, &n));
   *ranks = n;
@@ -502,7 +503,7 @@ int emap_comm_gather_layer(emap_ctx* ctx, int32_t plane, float* host_full_out) {
 
 int emap_comm_allreduce_host(emap_ctx* ctx, double* inout, int32_t n, int32_t op) {
   CKARG(ctx && ctx->rccl && ctx->comm, "emap_comm_init has not been called");
-  CKARG(inout && n >= 1 && n <= 16 && (op == 0 || op == 1), "bad argument");
+  CKARG(inout && n >= 1 && n <= 16 && (op == 0 || op == 1), "bad argument"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   double* buf = ctx->comm_sums + 4;     // [4..20) send, [20..36) receive
   CK(hipMemcpyAsync(buf, inout, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
@@ -515,7 +516,7 @@ int emap_comm_allreduce_host(emap_ctx* ctx, double* inout, int32_t n, int32_t op
 // Hardware self-test of the communicator (any world size): all-reduce of known values and one halo round trip.  With a single
 // rank the halo rows are exchanged with the rank itself (send to / receive from rank 0 inside one group).
 int emap_comm_selftest(emap_ctx* ctx) {
-  CKARG(ctx && ctx->rccl && ctx->comm, "emap_comm_init has not been called");
+  CKARG(ctx && ctx->rccl && ctx->comm, "emap_comm_init has not been called"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   const RcclApi* a = ctx->rccl;
   const double mine[2] = {1.0 + ctx->comm_rank, 0.5};

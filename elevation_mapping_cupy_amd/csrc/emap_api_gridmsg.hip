@@ -72,12 +72,14 @@ static int grid_publish(emap_ctx* ctx, const emap_grid_layer_ex* layers, int32_t
 
 int emap_publish_grid_map_ex(emap_ctx* ctx, const emap_grid_layer_ex* layers, int32_t n_layers, int32_t order,
                              float center_z, int32_t use_only_above_for_upper_bound, float* host_out, int64_t host_slots) {
+  CKARG(ctx, "null ctx"); SF_CHECK();
   return grid_publish(ctx, layers, n_layers, order, center_z, use_only_above_for_upper_bound, host_out, host_slots, "emap_publish_grid_map_ex", true);
 }
 
 // the table without flags: built-in, semantic and normal-colour layers only (a plugin plane is refused here as it always was)
 int emap_publish_grid_map(emap_ctx* ctx, const emap_grid_layer* layers, int32_t n_layers, int32_t order,
                           float center_z, int32_t use_only_above_for_upper_bound, float* host_out, int64_t host_slots) {
+  CKARG(ctx, "null ctx"); SF_CHECK();
   emap_grid_layer_ex ex[EMAP_GRID_MAX_LAYERS];
   if (layers && n_layers >= 1 && n_layers <= EMAP_GRID_MAX_LAYERS)
     for (int k = 0; k < n_layers; ++k) { ex[k].kind = layers[k].kind; ex[k].index = layers[k].index; ex[k].slot = layers[k].slot; ex[k].flags = 0; }

@@ -30,7 +30,7 @@ extern "C" {
 int emap_plugin_planes(emap_ctx* ctx, int32_t n_planes) {
   CKARG(ctx, "null ctx");
   CKARG(n_planes >= 0 && n_planes <= EMAP_PLUGIN_MAX_PLANES, "emap_plugin_planes: n_planes must lie in 0 .. 32");
-  CKARG(full_map(ctx), "emap_plugin_planes: single-strip contexts only");
+  CKARG(full_map(ctx), "emap_plugin_planes: single-strip contexts only"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   const size_t L = plane_len(ctx);
   if (n_planes > ctx->plane_cap) {      // (not emap_host::grow: the planes already written are kept)
@@ -53,7 +53,7 @@ int emap_plugin_planes(emap_ctx* ctx, int32_t n_planes) {
 int emap_plugin_plane_write(emap_ctx* ctx, int32_t plane, const float* host_in) {
   CKARG(ctx, "null ctx");
   CKARG(host_in, "emap_plugin_plane_write: null argument");
-  CKARG(plane >= 0 && plane < ctx->plane_n, "emap_plugin_plane_write: plane outside the reservation (emap_plugin_planes)");
+  CKARG(plane >= 0 && plane < ctx->plane_n, "emap_plugin_plane_write: plane outside the reservation (emap_plugin_planes)"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   const size_t L = plane_len(ctx);
   CK(hipMemcpyAsync(ctx->plane_buf + L * plane, host_in, sizeof(float) * L, hipMemcpyHostToDevice, ctx->stream));
@@ -63,7 +63,7 @@ int emap_plugin_plane_write(emap_ctx* ctx, int32_t plane, const float* host_in) 
 int emap_plugin_plane_read(emap_ctx* ctx, int32_t plane, float* host_out) {
   CKARG(ctx, "null ctx");
   CKARG(host_out, "emap_plugin_plane_read: null argument");
-  CKARG(plane >= 0 && plane < ctx->plane_n, "emap_plugin_plane_read: plane outside the reservation (emap_plugin_planes)");
+  CKARG(plane >= 0 && plane < ctx->plane_n, "emap_plugin_plane_read: plane outside the reservation (emap_plugin_planes)"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   const size_t L = plane_len(ctx);
   CK(hipMemcpyAsync(host_out, ctx->plane_buf + L * plane, sizeof(float) * L, hipMemcpyDeviceToHost, ctx->stream));

@@ -48,16 +48,18 @@ static int minmax_filter(emap_ctx* ctx, const float* host_elevation, const float
 
 int emap_min_filter(emap_ctx* ctx, const float* host_elevation, const float* host_valid, int32_t dilation_size, int32_t iteration_n,
                     float* host_out, int32_t* sweeps_run) {
+  CKARG(ctx, "null ctx"); SF_CHECK();
   return minmax_filter(ctx, host_elevation, host_valid, dilation_size, iteration_n, host_out, sweeps_run, false);
 }
 int emap_max_filter(emap_ctx* ctx, const float* host_elevation, const float* host_valid, int32_t dilation_size, int32_t iteration_n,
                     float* host_out, int32_t* sweeps_run) {
+  CKARG(ctx, "null ctx"); SF_CHECK();
   return minmax_filter(ctx, host_elevation, host_valid, dilation_size, iteration_n, host_out, sweeps_run, true);
 }
 
 // ---- SmoothFilter plugin (EM/plugins/smooth_filter.py:56-58): `passes` x uniform_filter(size=3) on a host plane ---------------
 int emap_smooth_filter(emap_ctx* ctx, const float* host_in, int32_t passes, float* host_out) {
-  CKARG(ctx && host_in && host_out && passes >= 1 && passes <= 64, "bad argument");
+  CKARG(ctx && host_in && host_out && passes >= 1 && passes <= 64, "bad argument"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   const int C = ctx->prm.cell_n; const size_t L = (size_t)C * C, bytes = L * sizeof(float);
   DevBuf buf;
@@ -72,7 +74,7 @@ int emap_smooth_filter(emap_ctx* ctx, const float* host_in, int32_t passes, floa
 
 // ---- Erosion plugin (EM/plugins/erosion.py:96-104): cv2.erode with a k x k rectangle, `iterations` times, on a host plane ------
 int emap_erode(emap_ctx* ctx, const float* host_in, int32_t kernel_size, int32_t iterations, float* host_out) {
-  CKARG(ctx && host_in && host_out && kernel_size >= 1 && kernel_size <= 63 && iterations >= 0 && iterations <= 256, "bad argument");
+  CKARG(ctx && host_in && host_out && kernel_size >= 1 && kernel_size <= 63 && iterations >= 0 && iterations <= 256, "bad argument"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   const int C = ctx->prm.cell_n; const size_t L = (size_t)C * C, bytes = L * sizeof(float);
   DevBuf buf;
@@ -88,7 +90,7 @@ int emap_erode(emap_ctx* ctx, const float* host_in, int32_t kernel_size, int32_t
 // ---- Inpainting plugin substitute (see emap_semantic.hip): fill the pixels with known == 0 of an 8-bit image ---------
 int emap_inpaint_u8(emap_ctx* ctx, const float* host_image, const float* host_known, int32_t max_sweeps, float* host_out,
                     int32_t* sweeps_run) {
-  CKARG(ctx && host_image && host_known && host_out && max_sweeps >= 0 && max_sweeps <= 65536, "bad argument");
+  CKARG(ctx && host_image && host_known && host_out && max_sweeps >= 0 && max_sweeps <= 65536, "bad argument"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   const int C = ctx->prm.cell_n; const size_t L = (size_t)C * C, bytes = L * sizeof(float);
   const int BATCH = 16;                      // sweeps between two looks at the unfilled counter
@@ -141,7 +143,7 @@ static int polygon_cell(const emap_params& p, float x, float y, float cx, float 
 }
 int emap_polygon_mask(emap_ctx* ctx, const float* polygon_xy, int32_t n_vertices, float center_x, float center_y, float* host_mask) {
   CKARG(ctx && polygon_xy && host_mask && n_vertices >= 1 && n_vertices <= 4096, "bad polygon");
-  CKARG(ctx->strip.halo_rows == 0 && ctx->strip.row_count == ctx->prm.cell_n, "emap_polygon_mask: single-strip contexts only");
+  CKARG(ctx->strip.halo_rows == 0 && ctx->strip.row_count == ctx->prm.cell_n, "emap_polygon_mask: single-strip contexts only"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   const int C = ctx->prm.cell_n;
   std::vector<int> v(2 * (size_t)n_vertices);
@@ -168,7 +170,7 @@ int emap_polygon_mask(emap_ctx* ctx, const float* polygon_xy, int32_t n_vertices
 int emap_dilate_planes(emap_ctx* ctx, const float* host_plane, const float* host_mask, int32_t dilation_size, int32_t iterations,
                        float* host_out, float* host_out_mask) {
   CKARG(ctx && host_plane && host_mask && host_out && host_out_mask, "null argument");
-  CKARG(dilation_size >= 0 && dilation_size <= 64 && iterations >= 1 && iterations <= 64, "bad dilation size / iteration count");
+  CKARG(dilation_size >= 0 && dilation_size <= 64 && iterations >= 1 && iterations <= 64, "bad dilation size / iteration count"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   const int C = ctx->prm.cell_n; const size_t L = (size_t)C * C, bytes = L * sizeof(float);
   DevBuf buf;

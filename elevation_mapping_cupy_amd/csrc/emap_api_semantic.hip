@@ -156,7 +156,7 @@ int emap_semantic_accumulate(emap_ctx* ctx, int32_t op, const float* points, int
                              const float* max_pt, const int32_t* max_id, int32_t n_max) {
   CKARG(ctx && points && newmap_inout && op >= 0 && op <= 4, "bad argument");
   CKARG(n_rows >= 0 && stride >= 3 && n_ch >= 1 && n_ch <= 64 && size >= 0 && cells > 0 && newmap_layers >= 1, "bad shape");
-  CKARG(op == 2 ? (max_pt && max_id && n_max >= 1 && size <= n_rows) : (pcl_chan && map_lay && size <= n_rows * (int64_t)n_ch), "bad channel description / size");
+  CKARG(op == 2 ? (max_pt && max_id && n_max >= 1 && size <= n_rows) : (pcl_chan && map_lay && size <= n_rows * (int64_t)n_ch), "bad channel description / size"); SF_CHECK();
   // The index CONTENTS decide which plane / column a thread touches: check them on the host before anything is
   // launched -- a bad index from a caller of the kernel factories must not write into other device memory of the shared context.
   if (op == 2) {
@@ -190,7 +190,7 @@ int emap_semantic_finalize(emap_ctx* ctx, int32_t op, void* newmap_inout, int32_
   CKARG(ctx && newmap_inout && map_lay && map_inout && op >= 0 && op <= 3, "bad argument");
   CKARG(n_ch >= 1 && n_ch <= 64 && size >= 0 && size <= cells * (int64_t)n_ch && cells > 0 && newmap_layers >= 1 && map_layers >= 1, "bad shape");
   CKARG(op == 3 || new_elmap3, "the accepted-point counts (new_elmap plane 2) are needed");
-  CKARG(op != 2 || (sum_mean && sum_layers >= n_ch), "bayesian_inference needs sum_mean");
+  CKARG(op != 2 || (sum_mean && sum_layers >= n_ch), "bayesian_inference needs sum_mean"); SF_CHECK();
   for (int k = 0; k < n_ch; ++k)      // (colour: newmap is the colour map, indexed by channel; every other op indexes newmap AND map with map_lay)
     CKARG(map_lay[k] >= 0 && map_lay[k] < map_layers && (op == 3 || map_lay[k] < newmap_layers), "map layer index outside the planes of map / newmap");
   CKARG(op != 3 || 3 * n_ch + 1 <= newmap_layers, "color_average: the colour map needs 3 n_ch + 1 planes");
@@ -288,25 +288,25 @@ static int sem_view(emap_ctx* ctx, float* planes, int32_t layer, float* host, bo
   return EMAP_OK;
 }
 int emap_semantic_get_alpha(emap_ctx* ctx, int32_t layer, float* host_out) {
-  CKARG(ctx && host_out && layer >= 0 && layer < ctx->sem_layers, "bad argument");
+  CKARG(ctx && host_out && layer >= 0 && layer < ctx->sem_layers, "bad argument"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   int rc = ensure_alpha(ctx); if (rc) return rc;
   return sem_view(ctx, ctx->sem_alpha, layer, host_out, false);
 }
 int emap_semantic_set_alpha(emap_ctx* ctx, int32_t layer, const float* host_in) {
-  CKARG(ctx && host_in && layer >= 0 && layer < ctx->sem_layers, "bad argument");
+  CKARG(ctx && host_in && layer >= 0 && layer < ctx->sem_layers, "bad argument"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   int rc = ensure_alpha(ctx); if (rc) return rc;
   return sem_view(ctx, ctx->sem_alpha, layer, const_cast<float*>(host_in), true);
 }
 
 int emap_semantic_get_layer(emap_ctx* ctx, int32_t layer, float* host_out) {
-  CKARG(ctx && host_out && layer >= 0 && layer < ctx->sem_layers, "bad argument");
+  CKARG(ctx && host_out && layer >= 0 && layer < ctx->sem_layers, "bad argument"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   return sem_view(ctx, ctx->sem, layer, host_out, false);
 }
 int emap_semantic_set_layer(emap_ctx* ctx, int32_t layer, const float* host_in) {
-  CKARG(ctx && host_in && layer >= 0 && layer < ctx->sem_layers, "bad argument");
+  CKARG(ctx && host_in && layer >= 0 && layer < ctx->sem_layers, "bad argument"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
   return sem_view(ctx, ctx->sem, layer, const_cast<float*>(host_in), true);
 }
@@ -364,7 +364,7 @@ int emap_image_fuse(emap_ctx* ctx, int32_t kind, int32_t layer, const float* hos
 }
 
 int emap_image_set_tolerance(emap_ctx* ctx, double tolerance_z_collision) {
-  CKARG(ctx && tolerance_z_collision == tolerance_z_collision, "bad argument");
+  CKARG(ctx && tolerance_z_collision == tolerance_z_collision, "bad argument"); SF_CHECK();
   ctx->img_tol = tolerance_z_collision; ctx->img_tol_set = true;
   return EMAP_OK;
 }

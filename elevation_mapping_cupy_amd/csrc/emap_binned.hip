@@ -33,27 +33,13 @@
 // ONE 12-byte stream over the cloud per frame does not.  With a visibility pass every VALID point marches a ray through the strip
 // (custom_kernels.py:199-258), validity needs the full geometry, and the non-strip kernels run (same records, ray-only bin).
 #include "emap_launch.h"
+#include "emap_bin_hist.h"
 #include <cstring>
 #include <cstdlib>
 
-#define BIN_TR 16
-#define BIN_TC 64
 #define BIN_QCAP 128      /* entries of a wave's compaction queue (strip variants): < 64 pending + <= 64 pushed per step */
 
-// (BinGeo, BinRec: emap_device.h; BIN_MAX_T: emap_launch.h)
-
-// sort bin of a point (-1: none) and its cell inside the bin.  Tiles are PHYSICAL: 16 owned rows x 64 columns of memory.
-__device__ __forceinline__ int bin_of(const KP& P, const BinGeo& G, const Geo& g, unsigned int& lc) {
-  const int lrow = phys_row(P, g.ix) - P.row0, pcol = phys_col(P, g.iy);
-  lc = 0u;
-  if (!(g.finite && g.valid)) return -1;
-  if (g.inside && lrow >= 0 && lrow < P.nrows) {
-    const int BR = BIN_TR * G.sub;
-    lc = (unsigned int)((lrow % BR) * BIN_TC + (pcol % BIN_TC));
-    return (lrow / BR) * G.tiles_x + (pcol / BIN_TC);
-  }
-  return G.raybin ? G.T : -1;             // ray only (custom_kernels.py:199-258 marches every valid point)
-}
+// (BinGeo, BinRec: emap_device.h; BIN_MAX_T: emap_launch.h; BIN_TR, BIN_TC, bin_of, bin_chunk_of_block, bin_hist_chunk: emap_bin_hist.h)
 
 // the cheap ownership test of the strip variants: only the x row of transform_p (custom_kernels.py:54-57) and its axis index
 template <int MODE> __device__ __forceinline__ bool row_owned(const KP& P, const Pose& T, float rx, float ry, float rz) {
@@ -66,52 +52,18 @@ template <int MODE> __device__ __forceinline__ bool row_owned(const KP& P, const
 // staging record of the strip variants: what k_bin_scatter needs to place a point, computed once by k_bin_hist
 struct __attribute__((aligned(16))) BinStg { unsigned int key; float z, v; unsigned int i; };      // key = (bin << 16) | cell in bin
 
-// Which chunk of the cloud (= row of the (block, tile) matrix, region of the staging array) workgroup b of the two point passes takes.
-// A tile's records are the runs of chunks 0, 1, 2, ... one behind the other, about four records (64 bytes) each at 1 M points; workgroup b
-// runs on XCD b % 8 (observed dispatch rule, as in bin_of_block: for speed only), so with chunk = b every 128-byte line of the record
-// buffer is put together from pieces that lie dirty in two or three different L2s and each piece goes to memory on its own.  rho sends
-// the workgroups of one residue class mod 8 to CONSECUTIVE chunks: neighbouring runs of a tile then meet in one L2.  A bijection on
-// [0, B) for every B (B = 8 q + r: class x holds q + (x < r) workgroups and starts at chunk x q + min(x, r); B < 8 is the identity);
-// rows stay indexed by chunk, so the scan, the record order and every byte of the sorted records are what they were -- only who
-// writes them changes, and nothing depends on the placement for correctness.  The identity order (chunk = b) was the other side of the
-// measurement and lost: k_bin_scatter 12.2 -> 11.0 us, 30.0 -> 27.2 MB written at 1 M points.
-__device__ __forceinline__ unsigned int bin_chunk_of_block() {
-  const unsigned int b = blockIdx.x, B = gridDim.x, q = B >> 3, r = B & 7u, x = b & 7u, j = b >> 3;
-  return x * q + min(x, r) + j;
-}
-
 // STRIP: the context owns a row strip and no visibility pass follows (see the header).  The staged records of block b are
 // stg[b * chunk ...], their number stg_cnt[b].
-#ifndef HIST_U
-#define HIST_U 4
-#endif
 template <int MODE, int BLK, bool STRIP>
 __global__ __launch_bounds__(BLK) void k_bin_hist(KP P, Pose T, BinGeo G, const float* __restrict__ pts, long n, int stride,
                                                   unsigned int* __restrict__ hist, BinStg* __restrict__ stg,
                                                   unsigned int* __restrict__ stg_cnt) {
   extern __shared__ __attribute__((aligned(16))) unsigned int h[];
-  for (int t = threadIdx.x; t < G.TB; t += BLK) h[t] = 0u;
-  const unsigned int blk = bin_chunk_of_block();             // the chunk this workgroup takes
-  const long base = (long)blk * G.chunk;
-  if (!STRIP) {
-    __syncthreads();
-    constexpr int U = HIST_U;                                  // loads in flight per thread (as in k_bin_scatter)
-    for (long k0 = threadIdx.x; k0 < G.chunk; k0 += (long)U * BLK) {
-      float rx[U], ry[U], rz[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const long k = k0 + (long)u * BLK, i = base + k;
-        rx[u] = ry[u] = rz[u] = NAN;                           // (a NaN row: no bin)
-        if (k < G.chunk && i < n) load_point(pts, i, stride, rx[u], ry[u], rz[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        unsigned int lc;
-        const int bin = bin_of(P, G, geometry<MODE>(P, T, rx[u], ry[u], rz[u]), lc);
-        if (bin >= 0) atomicAdd(&h[bin], 1u);
-      }
-    }
-  } else {
+  if (!STRIP) bin_hist_chunk<MODE, BLK, HIST_U>(P, T, G, pts, n, stride, hist, h, blockIdx.x, gridDim.x);      // (emap_bin_hist.h: shared with k_post_hist)
+  else {
+    for (int t = threadIdx.x; t < G.TB; t += BLK) h[t] = 0u;
+    const unsigned int blk = bin_chunk_of_block();             // the chunk this workgroup takes
+    const long base = (long)blk * G.chunk;
     float4* q = reinterpret_cast<float4*>(h + G.pitch) + (threadIdx.x >> 6) * BIN_QCAP;      // this wave's queue: (x, y, z, index)
     unsigned int* blk_cnt = h + G.pitch + (BLK / 64) * BIN_QCAP * 4;
     if (threadIdx.x == 0) *blk_cnt = 0u;
@@ -158,10 +110,10 @@ __global__ __launch_bounds__(BLK) void k_bin_hist(KP P, Pose T, BinGeo G, const 
     if (qn > 0) work(0, qn);
     __syncthreads();
     if (threadIdx.x == 0) stg_cnt[blk] = *blk_cnt;
+    __syncthreads();
+    unsigned int* row = hist + (long)blk * G.pitch;
+    for (int t = threadIdx.x; t < G.pitch; t += BLK) row[t] = t < G.TB ? h[t] : 0u;
   }
-  __syncthreads();
-  unsigned int* row = hist + (long)blk * G.pitch;
-  for (int t = threadIdx.x; t < G.pitch; t += BLK) row[t] = t < G.TB ? h[t] : 0u;
 }
 
 // Column scan of the (block, tile) matrix hist[B][pitch]: workgroup g owns the 64 columns [64 g, 64 g + 64) -- one lane per column --

@@ -139,6 +139,12 @@ struct emap_ctx {
   bool sf_redo;                    // inside sf_recover: frames take the chain of launches
   unsigned int sf_aborts;          // frames re-run so far (emap_small_frame_aborts)
   int update_path;                 // emap_last_update_path
+  // The stencil pass of the last frame, not launched yet (frame_impl): the next binned whole-map frame runs it in one grid with its own
+  // histogram (k_post_hist); every other way into the library launches it first (post_settle, part of SF_CHECK).  Nothing that changes
+  // the map, its origin or the parameters gets past it, so what is launched then is what post_part_impl(ctx, 0) would have launched when
+  // the frame ended.
+  bool post_pending;
+  unsigned int post_fused;         // fused launches since creation (emap_post_fused_launches)
   BinGeo bg; BinRec* bin_recs; size_t bin_recs_cap; bool bin_strip;
   float4* bin_own; size_t bin_own_cap; unsigned int* bin_own_cnt;   // staged 16-byte records (BinStg: emap_binned.hip) of the owned points per block (strip contexts without a visibility pass); bin_own_cnt: BIN_MAX_B words, sized once
   unsigned int* bin_hist; size_t bin_hist_cap; unsigned int* bin_tile_total; unsigned int* bin_tile_start;
@@ -228,6 +234,7 @@ int sf_settle(emap_ctx* ctx);
 int upload_setup(emap_ctx* ctx);
 Pose make_pose(const emap_ctx* ctx, const float R[9], const float t[3]);
 int flush_moves(emap_ctx* ctx);
+int post_settle(emap_ctx* ctx);
 int normal_row_lag(const emap_ctx* ctx);
 int plugin_scratch(emap_ctx* ctx, size_t planes, int counters);
 bool takes_bins(const emap_ctx* ctx, long n);
@@ -277,6 +284,10 @@ inline void bind_split_cloud(emap_ctx* ctx, const float* xyz, const float* chan,
 
 // Every entry point that reads or changes the map, the drift record or a cloud buffer settles the small frames in flight first
 // (emap_api.hip: sf_settle); map shifts are lazy (emap_shift) and written out before anything but a frame kernel looks at the cells.
-#define SF_CHECK() do { if (ctx->sf_count > 0) { int rc_sf_ = emap_host::sf_settle(ctx); if (rc_sf_) return rc_sf_; } } while (0)
+// The same door settles the last frame's pending stencil pass (post_settle): every entry point passes through SF_CHECK but the ones that
+// make up the next frame or touch neither the map nor the stream (DESIGN.md section 5 lists them; tests/test_post_settle_surface.py
+// holds the list).  SF_SETTLE_FRAMES: the small frames alone -- frame_impl, which decides about the pending pass itself.
+#define SF_SETTLE_FRAMES() do { if (ctx->sf_count > 0) { int rc_sf_ = emap_host::sf_settle(ctx); if (rc_sf_) return rc_sf_; } } while (0)
+#define SF_CHECK() do { SF_SETTLE_FRAMES(); if (ctx->post_pending) { int rc_ps_ = emap_host::post_settle(ctx); if (rc_ps_) return rc_ps_; } } while (0)
 #define FLUSH() do { int rc_ = emap_host::flush_moves(ctx); if (rc_) return rc_; } while (0)
 #define NEED_POINTS() do { if (!ctx->cloud.pts && ctx->cloud.n) { ctx->err = "no point cloud bound"; return EMAP_ERR_NO_POINTS; } } while (0)

@@ -4,6 +4,7 @@
 // write integer/fixed-point accumulators, per-cell passes commit) -- not a translation of the CuPy kernels.
 // Compiled with -ffp-contract=off: decisions (indices, gates) must be bit-identical to the oracle.
 #include "emap_launch.h"
+#include "emap_bin_hist.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -1356,151 +1357,45 @@ __global__ __launch_bounds__(512) void k_post_dma(KP P, TravW Wt, Cells cells, f
 template <int PT_R, int STAGE>
 __global__ __launch_bounds__(PT_R >= 32 ? POST_T32 : 512) void k_post(KP P, TravW Wt, Cells cells, float* __restrict__ trav_in,
                                                     float* __restrict__ normal, long plane_stride, int d, PostSegs S) {
-  int seg_b = S.b[0], seg_e = S.e[0], ty = blockIdx.y;
-#pragma unroll
-  for (int k = 1; k < 4; ++k) if (k < S.n && (int)blockIdx.y >= S.t0[k]) { seg_b = S.b[k]; seg_e = S.e[k]; ty = blockIdx.y - S.t0[k]; }
-  constexpr int PT_THREADS = PT_R >= 32 ? POST_T32 : 512, PT_WAVES = PT_THREADS / 64;     // (POST_T32: compile-time knob of the A/B builds -- 256 and 1024 threads were measured slower)
-  extern __shared__ float lds[];
-  const int RW = PT_C + 6 + 2 * d, rp = RW + 1, RH = PT_R + 6 + 2 * d;     // staged region: tile + halo 3 + d
-  const int DW = PT_C + 6, DH = PT_R + 6;                                   // region whose DILATED value is needed (halo 3)
-  // Region cell (r, c) = three consecutive floats at reg[(r * rp + c) * 3]: the raw upper_bound (holes inside the DW x DH region are
-  // overwritten by their dilated value), the mask >= 0 (stored as -(mask)-1 when the cell is NOT is_inside: never a source) and
-  // is_valid (normal filter).  One 12-byte LDS write per staged cell; a stride of three dwords across the lanes is conflict free.
-  float* reg = lds;
-  int* rtab = reinterpret_cast<int*>(reg + 3 * RH * rp);       // RH + 2 row terms
-  unsigned int* hs = reinterpret_cast<unsigned int*>(rtab + ((RH + 3) & ~1));      // sparse tiles: source bits of the region rows, 5 words each (post_source_masks)
-  unsigned short* holes = reinterpret_cast<unsigned short*>(hs + 8 * RH);         // compacted list of the holes of the DW x DH region
-  __shared__ unsigned int n_holes, s_special;
-  if (threadIdx.x == 0) { n_holes = 0u; s_special = 0u; }
-  __syncthreads();
-  const int C = P.C;
-  const int tile_r = seg_b + ty * PT_R, tile_c = blockIdx.x * PT_C;      // logical row / column of the tile origin
-  const int tc = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // wave index in an SGPR
-  // staging (post_stage_trips: rows and column walk, up to six rows' and two pairs' loads in flight per thread).  Everything that
-  // depends on the row (circular origin, strip ownership, border) is computed ONCE per tile into a small LDS table.  Two forms of the walk (round 4): INTERIOR tiles need nothing else;
-  // tiles along the map's edges carry the row table's and the column's flag bits (bit 31: no such cell, bit 30: border cell) and the
-  // reference's flat-index row wrap (:403-407: column -1 of row r is column C - 1 of row r - 1).
-  {
-    const int r0 = tile_r - 3 - d, c0 = tile_c - 3 - d, EC = RW - 64;
-    constexpr int U = PT_R >= 32 ? 6 : (PT_R >= 16 ? 4 : 2);                 // region rows per wave with their loads in flight together (post_stage_trips)
-    // row table: region row j - 1 (one extra row on both sides for the flat-index carry) -> local row of the arrays (bits 0..23;
-    // 0 with bit 31 set: not in the map / strip), bit 30: a border row (never a dilation source)
-    for (int j = threadIdx.x; j < RH + 2; j += PT_THREADS) {
-      const int g = r0 - 1 + j;
-      const bool in_map = g >= 0 && g <= C - 1;
-      const int lr = in_map ? local_row(P, phys_row(P, g)) : -1;
-      const int rt = lr < 0 ? (int)0x80000000 : lr | ((g >= 1 && g <= C - 2) ? 0 : 0x40000000);
-      rtab[j] = rt;
-      if ((rt & (int)0xC0000000) && j >= 1 && j <= RH) s_special = 1u;      // a region row that does not exist here or is a border row (racing writers store the same value)
-    }
-    __syncthreads();
-    // INTERIOR tiles -- every cell of the staged region exists, none is a border cell, no column leaves the map (so there is no
-    // flat-index row carry): all but the tiles along the map's (or the strip's missing) edges, 82 % of the tiles at 1024^2, 98 % at
-    // 8192^2.  Their staging needs none of the flag logic below: per region cell one address (row term x pitch + physical column), one
-    // 16-byte load, one add, one 12-byte LDS write, one compare for the hole list -- about a dozen instructions instead of the ~85 of
-    // the general path, which was 40 % of this kernel's instructions (round 4; the kernel is issue bound at every map size:
-    // tools/exp_post_pitch.py).  The LDS contents are the same bit for bit.
-    const bool interior = s_special == 0u && c0 >= 1 && c0 + RW - 1 <= C - 2;      // (uniform)
-    auto cold_at = [&](int T, unsigned int pc) { return cells.cold[(long)(__umul24((unsigned int)T & 0xffffffu, (unsigned int)C) + pc)]; };      // row term (without its flag bits) x pitch + physical column
-    if (interior) {
-      const unsigned int pc0 = (unsigned int)phys_col(P, c0 + tc);
-      post_stage_trips<U, PT_THREADS>(wv, tc, RH, EC, S.emagic,
-        [&](int r) { return PostLd{cold_at(rtab[r + 1], pc0), 0}; },
-        [&](int r, int cc) { return PostLd{cold_at(rtab[r + 1], (unsigned int)phys_col(P, c0 + cc)), 0}; },
-        [&](int r, int cc, const PostLd& l) {
-          const float4& q1 = l.q;
-          const float m = q1.w + q1.z;
-          float3 o; o.x = q1.y; o.y = m; o.z = q1.w;
-          *reinterpret_cast<float3*>(reg + (r * rp + cc) * 3) = o;
-          if (m < 0.5f && (unsigned int)(r - d) < (unsigned int)DH && (unsigned int)(cc - d) < (unsigned int)DW) holes[atomicAdd(&n_holes, 1u)] = (unsigned short)((r - d) * DW + (cc - d));
-        });
-    } else {
-      // Tiles along the map's edges (or next to rows a strip does not hold): the same walk with the flag bits of the row table (bit 31:
-      // no such row, bit 30: border row) and of the column (the same two bits + the flat-index row carry dr of the reference's
-      // addressing, :403-407: column -1 of row r is column C - 1 of row r - 1 -- such a lane reads the row table one row up or down).
-      // A cell that does not exist loads cell (0, 0) of the arrays and is masked afterwards: no branch around the loads.
-      auto col_terms = [&](int cc, int& dr, int& pc, int& flags) {     // region column -> row carry, physical column, flag bits
-        int cl = c0 + cc; dr = 0;
-        if (cl < 0) { cl += C; dr = -1; } else if (cl >= C) { cl -= C; dr = 1; }
-        flags = ((cl >= 1 && cl <= C - 2) ? 0 : 0x40000000) | (cl < C ? 0 : (int)0x80000000);      // (a region wider than the map: columns past the wrap are unused)
-        pc = cl < C ? phys_col(P, cl) : 0;
-      };
-      int ldr, lpc, lfl;
-      col_terms(tc, ldr, lpc, lfl);
-      const int* ltab = rtab + 1 + ldr;                              // the lane's view of the row table
-      post_stage_trips<U, PT_THREADS>(wv, tc, RH, EC, S.emagic,
-        [&](int r) { const int T = ltab[r]; return PostLd{cold_at(T, (unsigned int)lpc), T | lfl}; },
-        [&](int r, int cc) {
-          int dr, pc, fl;
-          col_terms(cc, dr, pc, fl);
-          const int T = rtab[r + 1 + dr];
-          return PostLd{cold_at(T, (unsigned int)pc), T | fl};
-        },
-        [&](int r, int cc, const PostLd& l) {
-          const float4& q1 = l.q;
-          const bool ok = l.tag >= 0, inside = (l.tag & 0x40000000) == 0;
-          const float m = q1.w + q1.z;
-          float3 o;
-          o.x = ok ? q1.y : 0.f;
-          o.y = ok ? (inside ? m : -m - 1.f) : -1.f;                  // mask >= 0; stored as -(mask) - 1 when the cell is not is_inside: never a source
-          o.z = ok ? q1.w : 0.f;
-          *reinterpret_cast<float3*>(reg + (r * rp + cc) * 3) = o;
-          // a hole of the region whose dilated value is needed (cells outside the map are never sources and never outputs: not listed)
-          if (ok && m < 0.5f && (unsigned int)(r - d) < (unsigned int)DH && (unsigned int)(cc - d) < (unsigned int)DW) holes[atomicAdd(&n_holes, 1u)] = (unsigned short)((r - d) * DW + (cc - d));
-        });
-    }
-  }
-  // The holes of the DW x DH region were COMPACTED into an LDS list by the staging loop and are searched one hole per lane -- a
-  // hole-containing wave would otherwise drag all 64 lanes through the neighbour search (measured: 11 of 33 us with 1.5 % holes), and
-  // a separate detection pass over the region with its two barriers cost 5.8 us of a 23-us kernel even when there was no hole at all.
-  // The dilated value replaces the raw one IN PLACE: only cells with mask > 0.5 are ever sources and the masks are not touched, so a
-  // filled hole cannot feed another hole (Jacobi semantics of the reference kernel), and the stencils below read one array.
-  __syncthreads();
-  const unsigned int nh = n_holes;
-  const bool sparse = 4 * (int)nh > 3 * DW * DH && RW <= 128 && d <= 15;       // (uniform) three cells of four are holes
-  if (sparse) {                                                     // mostly unknown tile: the search on bit masks (post_first_source)
-    post_source_masks<PT_THREADS>(hs, RH, RW, [&](int r, int cc) { return reg[(r * rp + min(cc, RW - 1)) * 3 + 1] > 0.5f; });
-    for (unsigned int hi = threadIdx.x; hi < nh; hi += PT_THREADS) {
-      const int pos = holes[hi], r = pos / DW, cc = pos - r * DW;
-      int dy, dx;
-      if (!post_first_source(hs, r + d, cc + d, d, dy, dx)) continue;      // no source within reach: the raw value stays
-      const int o0 = (r + d) * rp + (cc + d);
-      reg[o0 * 3] = reg[(o0 + dy * rp + dx) * 3];                    // a hole's slot is never read by another search (its mask is < 0.5)
-    }
-  } else
-  for (unsigned int hi = threadIdx.x; hi < nh; hi += PT_THREADS) {
-    const int pos = holes[hi], r = pos / DW, cc = pos - r * DW;
-    const int o0 = (r + d) * rp + (cc + d);
-    // first hit on ascending anti-diagonals == the reference's scan order with its signed dx+dy criterion (:429-436)
-    bool found = false;
-    for (int s2 = -2 * d; s2 <= 2 * d && !found; ++s2) {
-      const int dy0 = max(-d, s2 - d), dy1 = min(d, s2 + d);
-      for (int dy = dy0; dy <= dy1; ++dy) {
-        const int o = o0 + dy * rp + (s2 - dy);
-        if (reg[o * 3 + 1] > 0.5f) { reg[o0 * 3] = reg[o * 3]; found = true; break; }     // a hole's slot is never read by another search (its mask is < 0.5)
-      }
-    }
-  }
-  if (nh) __syncthreads();                       // (uniform: every thread read the same count)
-  const int col = tile_c + tc;                   // logical column
-  if (col >= C) return;
-  const int pcol = phys_col(P, col);
-  const float* dil = reg + (d * rp + d) * 3;     // dilated plane of the DW x DH region: element (row, column) at (row * dp + column) * 3
-  const int dp = rp;
-  // Every wave owns PT_R / 8 consecutive tile rows of its column.  The four channels of a dilated 3x3 filter go through packed
-  // fp32 FMAs in PAIRS (v_pk_fma_f32: the two channels' weights are one aligned scalar register pair, the tap is broadcast): each
-  // channel keeps the reference's tap order, and the 1x1 output convolution is the same scalar chain over (filter, channel) as the
-  // unfused stage -- half the vector instructions of the 12 x 9-tap filter bank, identical sums.
-  constexpr int RPW = PT_R >= PT_WAVES ? PT_R / PT_WAVES : 1;
-  const bool col_in = STAGE == 0 && col >= 3 && col <= C - 4;
-  const bool col_n = col >= 1 && col <= C - 3;
-#pragma unroll
-  for (int k = 0; k < RPW; ++k) {
-    const int tr = wv * RPW + k, gr = tile_r + tr;                 // scalar
-    if (tr >= PT_R || gr >= seg_e) break;
-    const float* t0 = &dil[((tr + 3) * dp + (tc + 3)) * 3];
-    const long c = (long)(rtab[tr + 4 + d] & 0xffffff) * C + pcol;
-    POST_CELL(Wt, 3, t0, dp, t0[2], col_in && gr >= 3 && gr <= C - 4, col_n && gr >= 1 && gr <= C - 3, c);
+#define POST_BX blockIdx.x
+#define POST_BY blockIdx.y
+#include "emap_post_tile.h"
+#undef POST_BX
+#undef POST_BY
+}
+
+// k_post_hist: the stencil pass of frame N and the histogram of frame N + 1's cloud in ONE grid.  The two ends of the frame are where the
+// chip is least busy -- k_bin_hist is one short latency chain per CU, k_post<32, 0> two issue-bound workgroups per CU with room for a
+// third -- and they do not depend on each other: the histogram reads the cloud, the pose and the map's geometry, the stencils read and
+// write map planes.  Workgroups [tile0, tile0 + n_tiles) take the stencil tile ((b - tile0) % tiles_x, (b - tile0) / tiles_x), workgroups
+// [hist0, hist0 + G.B) the chunk rho(b - hist0, G.B) of the cloud (emap_bin_hist.h), 8 points per thread in two batches; the rest of the grid is idle
+// padding.  No workgroup waits for another.  The host launches it only when all of them are resident at once (launch_post_hist) and keeps
+// hist0 a multiple of 8: workgroup b runs on XCD b % 8, so the histogram workgroup of a chunk then sits on the XCD of its twin in
+// k_bin_scatter (bin_chunk_of_block), as it does in k_bin_hist.  That placement is for speed only; nothing depends on it for the result.
+// The tiles stand in front of the histogram workgroups (hist0 = n_tiles rounded up to 8); the other order was measured
+// (EMAP_POST_HIST_FRONT).  Stage 0, one row interval, 512 threads.
+#ifndef POST_HIST_U
+#define POST_HIST_U 4      /* loads in flight per thread of a histogram workgroup: two batches of 4; one batch of 8 was measured slower */
+#endif
+template <int MODE, int PT_R>
+__global__ __launch_bounds__(512) void k_post_hist(KP P, TravW Wt, Cells cells, float* __restrict__ trav_in, float* __restrict__ normal,
+                                                   long plane_stride, int d, PostSegs S, int tiles_x, int n_tiles, int tile0, int hist0,
+                                                   Pose T, BinGeo G, const float* __restrict__ pts, long n, int stride,
+                                                   unsigned int* __restrict__ hist) {
+  static_assert(PT_R < 32 || POST_T32 == 512, "k_post_hist runs both bodies with 512 threads");
+  const int b = (int)blockIdx.x;                               // (uniform)
+  if ((unsigned int)(b - tile0) < (unsigned int)n_tiles) {
+    constexpr int STAGE = 0;
+    const unsigned int bx = (unsigned int)((b - tile0) % tiles_x), by = (unsigned int)((b - tile0) / tiles_x);
+#define POST_BX bx
+#define POST_BY by
+#include "emap_post_tile.h"
+#undef POST_BX
+#undef POST_BY
+  } else if ((unsigned int)(b - hist0) < (unsigned int)G.B) {
+    extern __shared__ float lds[];
+    bin_hist_chunk<MODE, 512, POST_HIST_U>(P, T, G, pts, n, stride, hist, reinterpret_cast<unsigned int*>(lds),
+                                           (unsigned int)(b - hist0), (unsigned int)G.B);
   }
 }
 
@@ -1841,8 +1736,7 @@ int post_tile_rows(const KP& P) {
 // outputs for up to four LOGICAL row intervals [seg_b[k], seg_e[k]) (owned by this strip, no circular seam inside); stage 1 = dilation only
 // tile_rows: 0 = the size post_tile_rows picks for the whole strip; else the tile height for THIS launch (the boundary bands of a strip
 // are dilation_size + 4 rows high: 32-row tiles would stage 44 region rows for 7 output rows)
-void launch_post(hipStream_t s, const KP& P, const float* w1, const float* w2, const float* w3, const float* wo, Cells cells,
-                 float* trav_in, float* normal, long plane_stride, int d, int nseg, const int* seg_b, const int* seg_e, int stage, int tile_rows) {
+static TravW post_weights(const float* w1, const float* w2, const float* w3, const float* wo) {
   TravW W;
   const float* wq[3] = {w1, w2, w3};                       // conv weights [channel][tap] -> [tap][channel]
   for (int q = 0; q < 3; ++q)
@@ -1850,19 +1744,29 @@ void launch_post(hipStream_t s, const KP& P, const float* w1, const float* w2, c
       for (int tap = 0; tap < 9; ++tap) W.w[q][tap][ch] = wq[q][ch * 9 + tap];
       W.wo[q][ch] = wo[q * 4 + ch];
     }
+  return W;
+}
+static unsigned int post_emagic(int d) { return (unsigned int)((0x100000000ull + (unsigned long long)(6 + 2 * d) - 1ull) / (unsigned long long)(6 + 2 * d)); }
+// the kernel launch_post picks for tile height R: the LDS-DMA one?
+static bool post_launch_dma(const KP& P, int R, int d) {
+  const long cells_ = (long)P.nrows * P.C;
+  static const bool win_forced = getenv("EMAP_POST_DMA_WINDOW") != nullptr || getenv("EMAP_POST_R") != nullptr;
+  return post_use_dma(R, d) && (win_forced || (R == 16 && cells_ >= 3072L * 3072L && cells_ < 5120L * 5120L && P.C < 5120));
+}
+void launch_post(hipStream_t s, const KP& P, const float* w1, const float* w2, const float* w3, const float* wo, Cells cells,
+                 float* trav_in, float* normal, long plane_stride, int d, int nseg, const int* seg_b, const int* seg_e, int stage, int tile_rows) {
+  const TravW W = post_weights(w1, w2, w3, wo);
   int R = post_tile_rows(P);
   if (tile_rows == 4 || tile_rows == 8 || tile_rows == 16 || tile_rows == 32) { if (tile_rows < R && post_lds_bytes(tile_rows, d) <= 150 * 1024) R = tile_rows; }
   PostSegs S; memset(&S, 0, sizeof S);
-  S.emagic = (unsigned int)((0x100000000ull + (unsigned long long)(6 + 2 * d) - 1ull) / (unsigned long long)(6 + 2 * d));
+  S.emagic = post_emagic(d);
   int tiles = 0;
   for (int k = 0; k < nseg && S.n < 4; ++k) {
     if (seg_e[k] <= seg_b[k]) continue;
     S.b[S.n] = seg_b[k]; S.e[S.n] = seg_e[k]; S.t0[S.n] = tiles; tiles += (seg_e[k] - seg_b[k] + R - 1) / R; S.n++;
   }
   if (!tiles) return;
-  const long cells_ = (long)P.nrows * P.C;
-  static const bool win_forced = getenv("EMAP_POST_DMA_WINDOW") != nullptr || getenv("EMAP_POST_R") != nullptr;
-  const bool dma = post_use_dma(R, d) && (win_forced || (R == 16 && cells_ >= 3072L * 3072L && cells_ < 5120L * 5120L && P.C < 5120));
+  const bool dma = post_launch_dma(P, R, d);
   dim3 g((P.C + PT_C - 1) / PT_C, tiles), b(dma ? 512 : (R >= 32 ? POST_T32 : 512));
   const size_t lds = dma ? post_dma_lds_bytes(R, d) : post_lds_bytes(R, d);
 #define POST_GO(KERN, RR, ST) do { auto kern = KERN<RR, ST>; static LdsRaised raised; \
@@ -1874,6 +1778,57 @@ void launch_post(hipStream_t s, const KP& P, const float* w1, const float* w2, c
   if (dma) POST_ALL(k_post_dma); else POST_ALL(k_post);
 #undef POST_ALL
 #undef POST_GO
+}
+// The whole map's stencil pass (launch_post: stage 0, the one interval [0, C), the tile height of post_tile_rows) as k_post_hist can run
+// it: the tile height when that launch is the plain k_post<16, 0> or k_post<32, 0>, else 0.
+int post_hist_tile_rows(const KP& P, int d) {
+  if (P.nrows != P.C) return 0;
+  const int R = post_tile_rows(P);
+  return (R == 16 || R == 32) && !post_launch_dma(P, R, d) && post_lds_bytes(R, d) <= 150 * 1024 ? R : 0;
+}
+// workgroups of k_post_hist that are resident at once: what the occupancy calculator gives per CU x the CUs (per instantiation, LDS size and device)
+template <class K> static long post_hist_resident(K kern, size_t lds, int dev) {
+  struct Memo { bool on; size_t lds; long wg; };
+  static Memo memo[EM_MAX_DEV];
+  Memo& m = memo[dev >= 0 && dev < EM_MAX_DEV ? dev : 0];
+  if (m.on && m.lds == lds) return m.wg;
+  int per_cu = 0, cus = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 512, lds) != hipSuccess) return 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+  m.on = true; m.lds = lds; m.wg = (long)per_cu * cus;
+  return m.wg;
+}
+// The stencil pass launch_post(.., whole map, stage 0) would run + launch_bin_hist of the next frame's cloud in one grid.  false: nothing
+// was launched -- the stencil tiles and the histogram chunks are not resident together (or more than max_wg workgroups: test hook), and
+// the caller runs the two launches.
+bool launch_post_hist(hipStream_t s, int dev, const KP& P, const float* w1, const float* w2, const float* w3, const float* wo, Cells cells,
+                      float* trav_in, float* normal, long plane_stride, int d, const Pose& T, const BinGeo& G, const float* pts, long n, int stride,
+                      unsigned int* hist, long max_wg) {
+  const int R = post_hist_tile_rows(P, d);
+  if (!R) return false;
+  const TravW W = post_weights(w1, w2, w3, wo);
+  PostSegs S; memset(&S, 0, sizeof S);
+  S.emagic = post_emagic(d);
+  S.n = 1; S.b[0] = 0; S.e[0] = P.C; S.t0[0] = 0;
+  // tiles in front, the histogram workgroups from the next multiple of 8 on (see k_post_hist); EMAP_POST_HIST_FRONT=1 (A/B knob): the
+  // histogram workgroups in front, the tiles from the next multiple of 8 on
+  static const bool hist_front = getenv("EMAP_POST_HIST_FRONT") && atoi(getenv("EMAP_POST_HIST_FRONT")) != 0;
+  const int tiles_x = (P.C + PT_C - 1) / PT_C, n_tiles = tiles_x * ((P.C + R - 1) / R);
+  const int tile0 = hist_front ? (G.B + 7) & ~7 : 0, hist0 = hist_front ? 0 : (n_tiles + 7) & ~7;
+  const long grid = hist_front ? (long)tile0 + n_tiles : (long)hist0 + G.B;
+  const size_t hist_lds = sizeof(unsigned int) * (size_t)G.pitch, lds = post_lds_bytes(R, d) > hist_lds ? post_lds_bytes(R, d) : hist_lds;
+  if (lds > 158 * 1024) return false;
+  bool ok = false;
+#define POST_HIST_GO(MODE, RR) do { auto kern = k_post_hist<MODE, RR>; static LdsRaised raised; \
+    if (!raise_lds(kern, raised, 158 * 1024) && lds > 64 * 1024) break; \
+    const long room = post_hist_resident(kern, lds, dev); \
+    if (grid > (max_wg > 0 && max_wg < room ? max_wg : room)) break; \
+    hipLaunchKernelGGL(kern, dim3((unsigned int)grid), dim3(512), lds, s, P, W, cells, trav_in, normal, plane_stride, d, S, tiles_x, n_tiles, tile0, hist0, \
+                       T, G, pts, n, stride, hist); ok = true; } while (0)
+  if (P.mode == 0) { if (R == 32) POST_HIST_GO(0, 32); else POST_HIST_GO(0, 16); }
+  else { if (R == 32) POST_HIST_GO(1, 32); else POST_HIST_GO(1, 16); }
+#undef POST_HIST_GO
+  return ok;
 }
 void launch_var_time(hipStream_t s, const KP& P, Cells cells, int do_var, int do_time) {
   hipLaunchKernelGGL(k_var_time, dim3(nblk((long)P.nrows * P.C)), dim3(EM_BLOCK), 0, s, P, cells, do_var, do_time);

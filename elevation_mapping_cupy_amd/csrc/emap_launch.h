@@ -91,6 +91,9 @@ void launch_overlap(hipStream_t, const KP&, Cells, int, int, float, float);
 void launch_var_time(hipStream_t, const KP&, Cells, int, int);
 int post_tile_rows(const KP&);
 void launch_post(hipStream_t, const KP&, const float*, const float*, const float*, const float*, Cells, float*, float*, long, int, int, const int*, const int*, int, int);
+int post_hist_tile_rows(const KP&, int);
+bool launch_post_hist(hipStream_t, int, const KP&, const float*, const float*, const float*, const float*, Cells, float*, float*, long, int,
+                      const Pose&, const BinGeo&, const float*, long, int, unsigned int*, long);
 void launch_get_plane(hipStream_t, const KP&, Cells, int, float*);
 void launch_publish(hipStream_t, const KP&, Cells, const float*, long, int, float, int, float*);
 void launch_set_plane(hipStream_t, const KP&, Cells, int, const float*);

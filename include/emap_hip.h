@@ -177,7 +177,16 @@ int emap_get_bound_points(emap_ctx* ctx, float* xyz_host, float* chan_host_or_nu
 /* tail of add_points_kernel (custom_kernels.py:260-262): per point cell idx, is_valid, is_inside */
 int emap_point_index(emap_ctx* ctx, const float R[9], const float t[3], int32_t* idx, uint8_t* valid, uint8_t* inside);
 
-/* ---- one frame = update_map_with_kernel (EM/elevation_mapping.py:316-391); t already centre-relative -- */
+/* ---- one frame = update_map_with_kernel (EM/elevation_mapping.py:316-391); t already centre-relative --
+ * After the call returns, the stream holds the frame up to its stencil pass (dilation, traversability filter, normals).  The pass is
+ * queued by the next call that needs it, or with the next frame.  Any library call that reads, changes or waits for the map sees the
+ * complete frame.
+ * (A whole-map frame on the tile-binned path leaves the pass pending; the next such frame runs it in one launch with its own
+ * histogram, k_post_hist.  The calls that do not queue it are the ones a frame is made of or that touch neither the map nor the stream:
+ * emap_set_points_device, emap_set_points_device_split, emap_frame_semantics, emap_update, emap_last_error, emap_last_update_path,
+ * emap_get_stage_times, emap_enable_stage_timing, emap_timer_begin.  A caller that enqueues work of its own on a stream it handed to
+ * emap_create orders it behind the frame with emap_sync or any other call.  EMAP_POST_DEFER=0 in the environment: every frame queues
+ * its own pass, as before.) */
 int emap_update(emap_ctx* ctx, const float R[9], const float t[3], double position_noise, double orientation_noise,
                 emap_stats* stats_or_null);
 /* individually callable stages (same order inside emap_update) */
@@ -562,6 +571,9 @@ int emap_last_update_path(emap_ctx* ctx, int32_t* path);
  * frames have been re-run this way since emap_create (normally 0).  Test hooks: EMAP_SF_TEST_ABORT=1|2 (workgroup 0 gives up at once
  * at that barrier), EMAP_SF_SPIN_LIMIT=<polls> (a waiter's patience). */
 int emap_small_frame_aborts(emap_ctx* ctx, uint32_t* frames);
+/* *launches = how many frames since emap_create ran the stencil pass of the frame before them in one launch with their own histogram
+ * (k_post_hist; see emap_update).  The call itself queues a pending pass, like every call that is not listed at emap_update. */
+int emap_post_fused_launches(emap_ctx* ctx, uint32_t* launches);
 
 #ifdef __cplusplus
 }
