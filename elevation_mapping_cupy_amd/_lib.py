@@ -90,7 +90,7 @@ GRID_MAX_LAYERS = 32                                # EMAP_GRID_MAX_LAYERS
 GRID_PLUGIN = 3                                     # EMAP_GRID_PLUGIN: a resident plugin plane (emap_publish_grid_map_ex)
 GRID_FILL_NAN, GRID_ADD_Z = 1, 2                    # EMAP_GRID_FILL_NAN / EMAP_GRID_ADD_Z
 PLUGIN_MAX_PLANES = PLUGIN_MAX_OPS = 32             # EMAP_PLUGIN_MAX_PLANES / EMAP_PLUGIN_MAX_OPS
-PLUGIN_OPS = {"min_filter": 0, "max_filter": 1, "smooth": 2, "erosion": 3, "robot_centric": 4}      # EMAP_PLUGIN_MIN_FILTER ..
+PLUGIN_OPS = {"min_filter": 0, "max_filter": 1, "smooth": 2, "erosion": 3, "robot_centric": 4, "inpaint_fronts": 6}      # EMAP_PLUGIN_MIN_FILTER .. (5: unassigned)
 PLUGIN_SRC_LAYER, PLUGIN_SRC_PLANE = 0, 1           # EMAP_PLUGIN_SRC_*
 PLUGIN_REVERSE, PLUGIN_THRESHOLD = 1, 2             # EMAP_PLUGIN_REVERSE / EMAP_PLUGIN_THRESHOLD
 

@@ -1,5 +1,5 @@
 // C ABI of the MI355X elevation-map fusion core, host side of the publish-time plugins on device-resident planes (kernels:
-// emap_plugchain.hip, emap_semantic.hip).  The reference keeps the plugins' outputs in PluginManager.layers on its device
+// emap_plugchain.hip, emap_semantic.hip, emap_inpaint_chain.hip, emap_inpaint_fronts.hip).  The reference keeps the plugins' outputs in PluginManager.layers on its device
 // (EM/plugins/plugin_manager.py:130, :181-236); the host route here (emap_api_plugins.hip) moves every plane over PCIe twice per plugin.
 // A chain enqueues the plugins of a publisher on the context's stream into planes the context owns and does not wait: k_grid_map
 // (emap_api_gridmsg.hip, kind EMAP_GRID_PLUGIN) reads them next to the cells, so a publisher's tick has one wait.
@@ -18,10 +18,18 @@ size_t op_planes(const emap_plugin_op& o) {
     case EMAP_PLUGIN_MIN_FILTER: case EMAP_PLUGIN_MAX_FILTER: return 5;       // orig mask, two (value, mask) pairs
     case EMAP_PLUGIN_SMOOTH: return o.src_kind == EMAP_PLUGIN_SRC_LAYER ? 1 : 0;
     case EMAP_PLUGIN_EROSION: return 2 + (o.src_kind == EMAP_PLUGIN_SRC_LAYER ? 1 : 0);
+    case EMAP_PLUGIN_INPAINT_FRONTS: return 0;                                  // byte images and fronts state: op_inpaint_bytes
     default: return 2;                                                          // ROBOT_CENTRIC: elevation, is_valid
   }
 }
 size_t op_counters(const emap_plugin_op& o) { return o.type <= EMAP_PLUGIN_MAX_FILTER ? (size_t)o.i1 + 1 : 0; }
+// INPAINT_FRONTS: fronts per launch, and the bytes of its own scratch -- the fronts pipeline's images and planes (emap_launch.h:
+// FrontsDev), behind them the partial range records and the folded one
+int inpaint_steps(const emap_plugin_op& o) { return o.i0 ? o.i0 : fronts_default_steps(); }
+size_t inpaint_range_bytes() { return ((EM_INP_PARTS + 1) * sizeof(InpRange) + 255) & ~(size_t)255; }
+size_t op_inpaint_bytes(const emap_ctx* ctx, const emap_plugin_op& o) {
+  return o.type == EMAP_PLUGIN_INPAINT_FRONTS ? fronts_bytes(ctx->prm.cell_n, ctx->prm.cell_n, inpaint_steps(o)) + inpaint_range_bytes() : 0;
+}
 
 }  // namespace
 
@@ -77,10 +85,10 @@ int emap_plugin_chain(emap_ctx* ctx, const emap_plugin_op* ops, int32_t n_ops, c
   CKARG(ops, "emap_plugin_chain: null argument");
   CKARG(n_ops >= 1 && n_ops <= EMAP_PLUGIN_MAX_OPS, "emap_plugin_chain: n_ops must lie in 1 .. 32");
   CKARG(full_map(ctx), "emap_plugin_chain: single-strip contexts only");
-  size_t planes = 0, counters = 0;
+  size_t planes = 0, counters = 0, inpaint = 0;
   for (int k = 0; k < n_ops; ++k) {
     const emap_plugin_op& o = ops[k];
-    CKARG(o.type >= EMAP_PLUGIN_MIN_FILTER && o.type <= EMAP_PLUGIN_ROBOT_CENTRIC, "emap_plugin_chain: unknown op type");
+    CKARG((o.type >= EMAP_PLUGIN_MIN_FILTER && o.type <= EMAP_PLUGIN_ROBOT_CENTRIC) || o.type == EMAP_PLUGIN_INPAINT_FRONTS, "emap_plugin_chain: unknown op type");
     CKARG(o.dst_plane >= 0 && o.dst_plane < ctx->plane_n, "emap_plugin_chain: dst_plane outside the reservation (emap_plugin_planes)");
     const bool reads_src = o.type == EMAP_PLUGIN_SMOOTH || o.type == EMAP_PLUGIN_EROSION;
     if (reads_src) {
@@ -94,10 +102,12 @@ int emap_plugin_chain(emap_ctx* ctx, const emap_plugin_op* ops, int32_t n_ops, c
       CKARG(o.i0 >= 0 && o.i0 <= 32 && o.i1 >= 0 && o.i1 <= 4096, "emap_plugin_chain: bad filter size / iteration count");
     if (o.type == EMAP_PLUGIN_EROSION)
       CKARG(o.i0 >= 1 && o.i0 <= 63 && o.i1 >= 0 && o.i1 <= 256, "emap_plugin_chain: bad erosion kernel size / iteration count");
+    if (o.type == EMAP_PLUGIN_INPAINT_FRONTS)
+      CKARG(o.i0 >= 0 && o.i0 <= EM_FRONTS_S_MAX && o.i1 == 0, "emap_plugin_chain: bad fronts per launch (i0 must lie in 0 .. 16, i1 must be 0)");
     const int allowed = o.type == EMAP_PLUGIN_EROSION ? EMAP_PLUGIN_REVERSE : (o.type == EMAP_PLUGIN_ROBOT_CENTRIC ? EMAP_PLUGIN_THRESHOLD : 0);
     CKARG((o.flags & ~allowed) == 0, "emap_plugin_chain: a flag the op does not know");
     CKARG(o.type != EMAP_PLUGIN_ROBOT_CENTRIC || rotation9, "emap_plugin_chain: null argument (rotation9)");
-    planes += op_planes(o); counters += op_counters(o);
+    planes += op_planes(o); counters += op_counters(o); inpaint += op_inpaint_bytes(ctx, o);
   }
 
   SF_CHECK();
@@ -107,9 +117,10 @@ int emap_plugin_chain(emap_ctx* ctx, const emap_plugin_op* ops, int32_t n_ops, c
   int rc = grow(ctx, &ctx->chain_buf, &ctx->chain_cap, planes * L); if (rc) return rc;
   rc = grow(ctx, &ctx->chain_cnt, &ctx->chain_cnt_cap, counters); if (rc) return rc;
   rc = grow(ctx, &ctx->chain_red, &ctx->chain_red_cap, (size_t)n_ops * EM_RANGE_FLOATS); if (rc) return rc;
+  rc = grow(ctx, &ctx->chain_inp, &ctx->chain_inp_cap, inpaint); if (rc) return rc;
   if (counters) CK(hipMemsetAsync(ctx->chain_cnt, 0, sizeof(unsigned int) * counters, ctx->stream));
 
-  float* buf = ctx->chain_buf; unsigned int* cnt = ctx->chain_cnt;
+  float* buf = ctx->chain_buf; unsigned int* cnt = ctx->chain_cnt; unsigned char* inp = ctx->chain_inp;
   for (int k = 0; k < n_ops; ++k) {
     const emap_plugin_op& o = ops[k];
     float* dst = ctx->plane_buf + L * o.dst_plane;
@@ -145,6 +156,19 @@ int emap_plugin_chain(emap_ctx* ctx, const emap_plugin_op* ops, int32_t n_ops, c
         launch_quantise(ctx->stream, (long)L, src, rev, red, a);
         for (int it = 0; it < o.i1; ++it) { launch_erode(ctx->stream, C, o.i0, a, b); float* t = a; a = b; b = t; }
         launch_dequantise(ctx->stream, (long)L, a, src, rev, red, dst);      // (src may be dst: element i is read before it is written, by one thread)
+      } break;
+      case EMAP_PLUGIN_INPAINT_FRONTS: {
+        // max d is not read back: d is the L1 distance to a known cell INSIDE the map, so max d <= 2 C - 2, and the launches behind the last
+        // front return at their first test (emap_inpaint_fronts.hip: k_fr_advance)
+        const int S = inpaint_steps(o);
+        const FrontsDev f = fronts_carve(inp, C, C, S);
+        InpRange* parts = reinterpret_cast<InpRange*>(inp + fronts_bytes(C, C, S));
+        InpRange* rec = parts + EM_INP_PARTS;
+        inp += op_inpaint_bytes(ctx, o);
+        launch_inpaint_range(ctx->stream, ctx->kp, ctx->cells, parts, rec);
+        launch_inpaint_quantise(ctx->stream, ctx->kp, ctx->cells, rec, f.in, f.mask);
+        launch_fronts(ctx->stream, f, C, C, S, (2 * C - 2 + S - 1) / S);
+        launch_inpaint_dequantise(ctx->stream, ctx->kp, ctx->cells, rec, f.out, dst);
       } break;
       default:
         launch_get_plane(ctx->stream, ctx->kp, ctx->cells, 0, scr);

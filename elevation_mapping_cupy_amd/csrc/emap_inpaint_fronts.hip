@@ -4,8 +4,12 @@
 //   fronts k = 1 .. max d run in order, every pixel of front k at once; "not INSIDE" in the host arithmetic means d(q) < k (the
 //   1-pixel frame outside the image counts as known); pixels with d >= k read as T = 1e6 and hold their input value; a known pixel
 //   4-adjacent to the hole starts at T = -0.0f (the host's empty outside march with radius 1), every other known pixel at 1e6.
+// The pipeline runs on images that are on the device (launch_fronts, emap_launch.h: the core an op of a plugin chain enqueues with the
+// geometric bound of max d as its launch count); emap_inpaint_telea_fronts_u8 is the host door around it: uploads, the
+// 4-byte read-back of max d, ceil(max d / S) launches, the download.
 // Pipeline per call, one stream, no grid-wide barrier:
-//   k_fr_dt_cols   exact separable L1 distance transform, column pass (one thread per column, two sweeps)
+//   k_fr_dt_cols_local, k_fr_dt_cols_carry   exact separable L1 distance transform, column pass: two sweeps per (column, block of 32
+//                  rows), then the carries of the blocks above and below
 //   k_fr_dt_rows   row pass (one wave per row: min-plus over |dj| as a prefix / suffix minimum of g -+ j)
 //   k_fr_init      per tile: initial T, output = input, min / max d of the tile, max d of the image (one 4-byte read-back)
 //   k_fr_advance   ceil(max d / S) launches; a workgroup loads its tile plus a halo of 2 S pixels into LDS (T f32, value u8,
@@ -15,6 +19,7 @@
 //                  Halo pixels another workgroup writes in the same launch have d > k0 and are read as (1e6, input value), which is
 //                  what they held before the launch: no race decides a result.
 #include "../../include/emap_hip.h"
+#include "emap_launch.h"
 #include <hip/hip_runtime.h>
 #include <climits>
 #include <cstdint>
@@ -26,7 +31,7 @@ constexpr int FW = 94;                 // LDS tile side: interior FW - 4 S plus 
 constexpr int FN = FW * FW;
 constexpr int FB = 256;                // threads per workgroup of every kernel here
 constexpr int FINF = 1 << 29;          // "no known pixel" distance
-constexpr int S_MAX = 16;              // fronts per launch: interior FW - 4 S >= 30
+constexpr int S_MAX = EM_FRONTS_S_MAX;  // fronts per launch: interior FW - 4 S >= 30
 constexpr int S_DEFAULT = 16;          // measured (tools/exp_inpaint_fronts.py): the fastest S at 202^2, within 4 % at 1024^2
 
 // Lanes of one wave hand cell indices to each other through LDS: a wave-scope release / acquire pair around the wave barrier orders the
@@ -40,35 +45,58 @@ __device__ __forceinline__ void fr_wave_sync() {
 __device__ inline float fr_min4(float a, float b, float c, float d) { a = a < b ? a : b; c = c < d ? c : d; return a < c ? a : c; }
 
 // ---- distance transform ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(FB) void k_fr_dt_cols(const uint8_t* __restrict__ mask, int32_t* __restrict__ g, int rows, int cols) {
-  const int j = blockIdx.x * FB + threadIdx.x;
+// Column pass in row blocks of DTB rows, one thread per (column, block): g(i, j) = distance along column j to the nearest known pixel, FINF
+// without one.  k_fr_dt_cols_local runs the two sweeps inside its block (the recurrence in registers, all loads issued together) and leaves
+// the block's summary: top = distance from the block's first row DOWN to its first known pixel, bot = from its last row UP to its last
+// known pixel (FINF: none).  k_fr_dt_cols_carry walks the summaries of the blocks above and below to the nearest one that holds a known
+// pixel -- every block but the last is full, so that pixel lies (blocks between) * DTB + 1 + bot (or top) rows beyond the block's edge --
+// and lowers its block's values by the two carries.  The result is the integer the one-thread-per-column sweeps gave.
+constexpr int DTB = 32;
+__global__ __launch_bounds__(FB) void k_fr_dt_cols_local(const uint8_t* __restrict__ mask, int32_t* __restrict__ g, int32_t* __restrict__ top,
+                                                         int32_t* __restrict__ bot, int rows, int cols) {
+  const int j = blockIdx.x * FB + threadIdx.x, i0 = blockIdx.y * DTB;
   if (j >= cols) return;
-  constexpr int B = 16;                                        // rows whose loads are issued together (the recurrence is in registers)
-  int h = FINF;
-  for (int i0 = 0; i0 < rows; i0 += B) {
-    uint8_t m[B];
+  const int n = rows - i0 < DTB ? rows - i0 : DTB;
+  const size_t p0 = (size_t)i0 * cols + j;
+  uint8_t m[DTB]; int32_t f[DTB];
 #pragma unroll
-    for (int u = 0; u < B; ++u) m[u] = i0 + u < rows ? mask[(size_t)(i0 + u) * cols + j] : 0;
+  for (int u = 0; u < DTB; ++u) m[u] = u < n ? mask[p0 + (size_t)u * cols] : 1;      // rows beyond the image: never known
+  int h = FINF, first = FINF, last = FINF;
 #pragma unroll
-    for (int u = 0; u < B; ++u) {
-      h = m[u] ? (h >= FINF ? FINF : h + 1) : 0;
-      if (i0 + u < rows) g[(size_t)(i0 + u) * cols + j] = h;
-    }
+  for (int u = 0; u < DTB; ++u) {
+    h = m[u] ? (h >= FINF ? FINF : h + 1) : 0;
+    f[u] = h;
+    if (!m[u]) { first = first < FINF ? first : u; last = n - 1 - u; }
   }
   h = FINF;
-  for (int i1 = rows - 1; i1 >= 0; i1 -= B) {
-    uint8_t m[B]; int32_t f[B];
 #pragma unroll
-    for (int u = 0; u < B; ++u) {
-      const bool ok = i1 - u >= 0;
-      m[u] = ok ? mask[(size_t)(i1 - u) * cols + j] : 0;
-      f[u] = ok ? g[(size_t)(i1 - u) * cols + j] : 0;
-    }
+  for (int u = DTB - 1; u >= 0; --u) {
+    h = m[u] ? (h >= FINF ? FINF : h + 1) : 0;
+    if (u < n) g[p0 + (size_t)u * cols] = f[u] < h ? f[u] : h;
+  }
+  top[(size_t)blockIdx.y * cols + j] = first;
+  bot[(size_t)blockIdx.y * cols + j] = last;
+}
+__global__ __launch_bounds__(FB) void k_fr_dt_cols_carry(int32_t* __restrict__ g, const int32_t* __restrict__ top, const int32_t* __restrict__ bot,
+                                                         int rows, int cols, int nb) {
+  const int j = blockIdx.x * FB + threadIdx.x, b = blockIdx.y, i0 = b * DTB;
+  if (j >= cols) return;
+  const int n = rows - i0 < DTB ? rows - i0 : DTB;
+  int cu = FINF, cd = FINF;      // from the block's first row up / from its last row down to the nearest known pixel outside the block
+  for (int q = b - 1; q >= 0; --q) { const int t = bot[(size_t)q * cols + j]; if (t < FINF) { cu = (b - q - 1) * DTB + 1 + t; break; } }
+  for (int q = b + 1; q < nb; ++q) { const int t = top[(size_t)q * cols + j]; if (t < FINF) { cd = (q - b - 1) * DTB + 1 + t; break; } }
+  if (cu >= FINF && cd >= FINF) return;
+  const size_t p0 = (size_t)i0 * cols + j;
+  int32_t v[DTB];
 #pragma unroll
-    for (int u = 0; u < B; ++u) {
-      h = m[u] ? (h >= FINF ? FINF : h + 1) : 0;
-      if (i1 - u >= 0) g[(size_t)(i1 - u) * cols + j] = f[u] < h ? f[u] : h;
-    }
+  for (int u = 0; u < DTB; ++u) v[u] = u < n ? g[p0 + (size_t)u * cols] : 0;
+#pragma unroll
+  for (int u = 0; u < DTB; ++u) {
+    if (u >= n) break;
+    int x = v[u];
+    if (cu < FINF) x = cu + u < x ? cu + u : x;
+    if (cd < FINF) x = cd + (n - 1 - u) < x ? cd + (n - 1 - u) : x;
+    g[p0 + (size_t)u * cols] = x;
   }
 }
 
@@ -268,16 +296,62 @@ __global__ __launch_bounds__(FB) void k_fr_advance(const uint8_t* __restrict__ i
 }
 }  // namespace
 
+// ---- the pipeline on device images (emap_launch.h: FrontsDev) ------------------------------------------------------------------------
+namespace {
+size_t fr_tiles(int rows, int cols, int S) { const int tw = FW - 4 * S; return (size_t)((cols + tw - 1) / tw) * ((rows + tw - 1) / tw); }
+size_t fr_up(size_t b) { return (b + 255) & ~(size_t)255; }
+size_t fr_blk(int rows, int cols) { return 2 * (size_t)((rows + DTB - 1) / DTB) * cols; }      // ints: top and bot of every (block, column)
+// distance transform and the tiles' initial state (k_fr_init leaves max d in *f.dmax, which the caller has zeroed if it reads it)
+void fr_begin(hipStream_t st, const FrontsDev& f, int rows, int cols, int S) {
+  const int tw = FW - 4 * S, ntx = (cols + tw - 1) / tw;
+  const int nb = (rows + DTB - 1) / DTB;
+  hipLaunchKernelGGL(k_fr_dt_cols_local, dim3((cols + FB - 1) / FB, nb), dim3(FB), 0, st, f.mask, f.g, f.blk, f.blk + (size_t)nb * cols, rows, cols);
+  if (nb > 1)      // (one block: its own sweeps are the whole column)
+    hipLaunchKernelGGL(k_fr_dt_cols_carry, dim3((cols + FB - 1) / FB, nb), dim3(FB), 0, st, f.g, f.blk, f.blk + (size_t)nb * cols, rows, cols, nb);
+  hipLaunchKernelGGL(k_fr_dt_rows, dim3((rows + FB / 64 - 1) / (FB / 64)), dim3(FB), 0, st, f.g, f.d, rows, cols);
+  hipLaunchKernelGGL(k_fr_init, dim3((unsigned)fr_tiles(rows, cols, S)), dim3(FB), 0, st, f.in, f.mask, f.d, f.T, f.out, f.tile_mm, f.dmax,
+                     rows, cols, tw, ntx);
+}
+// fronts 1 .. n_advance * S, S per launch
+void fr_advance(hipStream_t st, const FrontsDev& f, int rows, int cols, int S, int n_advance) {
+  const int tw = FW - 4 * S, ntx = (cols + tw - 1) / tw;
+  const unsigned ntiles = (unsigned)fr_tiles(rows, cols, S);
+  for (int k = 0; k < n_advance; ++k)
+    hipLaunchKernelGGL(k_fr_advance, dim3(ntiles), dim3(FB), 0, st, f.in, f.d, f.T, f.out, f.tile_mm, rows, cols, ntx, S, k * S);
+}
+}  // namespace
+
+int fronts_default_steps() { return S_DEFAULT; }
+size_t fronts_bytes(int rows, int cols, int S) {
+  const size_t n = (size_t)rows * cols;
+  return 3 * fr_up(n) + 3 * fr_up(4 * n) + fr_up(fr_tiles(rows, cols, S) * sizeof(int2)) + fr_up(sizeof(int)) + fr_up(fr_blk(rows, cols) * sizeof(int));
+}
+FrontsDev fronts_carve(unsigned char* b, int rows, int cols, int S) {
+  const size_t n = (size_t)rows * cols, n1 = fr_up(n), n4 = fr_up(4 * n);
+  FrontsDev f;
+  f.in = b; f.mask = b + n1; f.out = b + 2 * n1; b += 3 * n1;
+  f.g = (int*)b; f.d = (int*)(b + n4); f.T = (float*)(b + 2 * n4); b += 3 * n4;
+  f.tile_mm = (int2*)b; b += fr_up(fr_tiles(rows, cols, S) * sizeof(int2));
+  f.dmax = (int*)b; b += fr_up(sizeof(int));
+  f.blk = (int*)b;
+  return f;
+}
+void launch_fronts(hipStream_t st, const FrontsDev& f, int rows, int cols, int S, int n_advance) {
+  fr_begin(st, f, rows, cols, S);
+  fr_advance(st, f, rows, cols, S, n_advance);
+}
+
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
 struct emap_inpainter {
   int device = 0;
   hipStream_t stream = nullptr;
   int steps = S_DEFAULT;
-  size_t cap = 0, tcap = 0;            // pixels / tiles the scratch holds (grown to the largest image seen, never shrunk)
+  size_t cap = 0, tcap = 0, bcap = 0;  // pixels / tiles / block summaries the scratch holds (grown to the largest image seen, never shrunk)
   uint8_t *in = nullptr, *mask = nullptr, *out = nullptr;
   int32_t *g = nullptr, *d = nullptr;
   float* T = nullptr;
   int2* tile_mm = nullptr;
+  int* blk = nullptr;                  // top / bot of the column pass's row blocks
   int* dmax = nullptr;
   int* dmax_host = nullptr;            // pinned 4-byte landing slot
 };
@@ -311,7 +385,7 @@ extern "C" int emap_inpainter_destroy(emap_inpainter* ip) {
   if (!ip) return EMAP_OK;
   hipSetDevice(ip->device);            // (every call has synchronised its stream before returning: the caller's stream is not touched here)
   fr_free(ip);
-  hipFree(ip->tile_mm); hipFree(ip->dmax); hipHostFree(ip->dmax_host);
+  hipFree(ip->tile_mm); hipFree(ip->blk); hipFree(ip->dmax); hipHostFree(ip->dmax_host);
   delete ip;
   return EMAP_OK;
 }
@@ -328,8 +402,8 @@ extern "C" int emap_inpaint_telea_fronts_u8(emap_inpainter* ip, const uint8_t* i
   if (fronts_run) *fronts_run = 0;
   FR_CK(hipSetDevice(ip->device));
   const size_t n = (size_t)rows * cols;
-  const int S = ip->steps, tw = FW - 4 * S, ntx = (cols + tw - 1) / tw, nty = (rows + tw - 1) / tw;
-  const size_t ntiles = (size_t)ntx * nty;
+  const int S = ip->steps;
+  const size_t ntiles = fr_tiles(rows, cols, S);
   if (n > ip->cap) {
     FR_CK(hipStreamSynchronize(ip->stream));
     fr_free(ip);
@@ -344,14 +418,18 @@ extern "C" int emap_inpaint_telea_fronts_u8(emap_inpainter* ip, const uint8_t* i
     FR_CK(hipMalloc((void**)&ip->tile_mm, ntiles * sizeof(int2)));
     ip->tcap = ntiles;
   }
+  if (fr_blk(rows, cols) > ip->bcap) {
+    FR_CK(hipStreamSynchronize(ip->stream));
+    hipFree(ip->blk); ip->blk = nullptr; ip->bcap = 0;
+    FR_CK(hipMalloc((void**)&ip->blk, fr_blk(rows, cols) * sizeof(int)));
+    ip->bcap = fr_blk(rows, cols);
+  }
   hipStream_t st = ip->stream;
+  const FrontsDev f{ip->in, ip->mask, ip->out, ip->g, ip->d, ip->T, ip->tile_mm, ip->dmax, ip->blk};
   FR_CK(hipMemcpyAsync(ip->in, image, n, hipMemcpyHostToDevice, st));
   FR_CK(hipMemcpyAsync(ip->mask, mask, n, hipMemcpyHostToDevice, st));
   FR_CK(hipMemsetAsync(ip->dmax, 0, sizeof(int), st));
-  hipLaunchKernelGGL(k_fr_dt_cols, dim3((cols + FB - 1) / FB), dim3(FB), 0, st, ip->mask, ip->g, rows, cols);
-  hipLaunchKernelGGL(k_fr_dt_rows, dim3((rows + FB / 64 - 1) / (FB / 64)), dim3(FB), 0, st, ip->g, ip->d, rows, cols);
-  hipLaunchKernelGGL(k_fr_init, dim3((unsigned)ntiles), dim3(FB), 0, st, ip->in, ip->mask, ip->d, ip->T, ip->out, ip->tile_mm, ip->dmax,
-                     rows, cols, tw, ntx);
+  fr_begin(st, f, rows, cols, S);
   FR_CK(hipGetLastError());
   FR_CK(hipMemcpyAsync(ip->dmax_host, ip->dmax, sizeof(int), hipMemcpyDeviceToHost, st));
   FR_CK(hipStreamSynchronize(st));
@@ -360,8 +438,7 @@ extern "C" int emap_inpaint_telea_fronts_u8(emap_inpainter* ip, const uint8_t* i
     memcpy(out, image, n);
     return EMAP_OK;
   }
-  for (int k0 = 0; k0 < dmax; k0 += S)
-    hipLaunchKernelGGL(k_fr_advance, dim3((unsigned)ntiles), dim3(FB), 0, st, ip->in, ip->d, ip->T, ip->out, ip->tile_mm, rows, cols, ntx, S, k0);
+  fr_advance(st, f, rows, cols, S, (dmax + S - 1) / S);
   FR_CK(hipGetLastError());
   FR_CK(hipMemcpyAsync(out, ip->out, n, hipMemcpyDeviceToHost, st));
   FR_CK(hipStreamSynchronize(st));

@@ -154,3 +154,22 @@ void launch_range(hipStream_t, long, const float*, int, float*, float*);
 void launch_quantise(hipStream_t, long, const float*, int, const float*, float*);
 void launch_dequantise(hipStream_t, long, const float*, const float*, int, const float*, float*);
 void launch_robot_centric(hipStream_t, int, float, const float*, int, float, const float*, const float*, float*);
+
+// Inpainting on resident planes (EMAP_PLUGIN_INPAINT_FRONTS).  FrontsDev: the device images and planes of one run of the fronts pipeline
+// (emap_inpaint_fronts.hip) -- the handle of emap_inpaint_telea_fronts_u8 owns one, every inpaint op of a chain carves its own out of the
+// context's scratch (fronts_carve; fronts_bytes: what it takes).  launch_fronts enqueues the distance transform, k_fr_init and `n_advance`
+// launches of k_fr_advance (fronts 1 .. n_advance * S) on images that are on the device, and waits for nothing; a launch beyond the last
+// front finds no tile that holds one of its fronts and returns at its first test.
+struct FrontsDev { unsigned char *in, *mask, *out; int *g, *d; float* T; int2* tile_mm; int* dmax; int* blk; };
+#define EM_FRONTS_S_MAX 16
+int fronts_default_steps();
+size_t fronts_bytes(int rows, int cols, int S);
+FrontsDev fronts_carve(unsigned char* base, int rows, int cols, int S);
+void launch_fronts(hipStream_t, const FrontsDev&, int rows, int cols, int S, int n_advance);
+// the op's arithmetic around the fill (emap_inpaint_chain.hip); InpRange: lo / hi of elevation over the cells with is_valid >= 0.5 and
+// how many cells are known / unknown -- EM_INP_PARTS partial records and the folded one behind them
+struct InpRange { float lo, hi; unsigned int known, unknown; };
+#define EM_INP_PARTS 256
+void launch_inpaint_range(hipStream_t, const KP&, Cells, InpRange* parts, InpRange* rec);
+void launch_inpaint_quantise(hipStream_t, const KP&, Cells, const InpRange* rec, unsigned char* q8, unsigned char* mask);
+void launch_inpaint_dequantise(hipStream_t, const KP&, Cells, const InpRange* rec, const unsigned char* out8, float* dst);

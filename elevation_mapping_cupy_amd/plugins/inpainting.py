@@ -17,6 +17,11 @@ Same semantics around the fill as the reference: mask = ``is_valid < 0.5``, the 
   agreement figures).  Same quantisation around the fill as ``"telea"``.  Its handle is created on first use on the owning
   ElevationMap's device and stream (the manager injects ``emap``), else on the current device's null stream.  The reference has no
   such name and falls back to telea for it (reference plugins/inpainting.py:26-31), so a YAML naming it runs on both.
+  This method is also an op of ``emap_plugin_chain`` (``device_op``: ``EMAP_PLUGIN_INPAINT_FRONTS``, csrc/emap_inpaint_chain.hip): in a
+  publisher's list (``ElevationMap.get_grid_map_layers``) the range, the 8-bit image, the mask, the fill and the de-quantisation run on
+  the map's own cells into a resident plane, bit for bit what ``__call__`` returns, with no copy over PCIe and no wait; ``fronts_run``
+  is ``None`` afterwards (nothing waited for it).  ``steps`` (extra parameter, 1 .. 16; 0: the library's default of 16) sets the
+  fronts per launch on either route; the result does not depend on it.
 * ``method="ns"`` (``cv2.INPAINT_NS``, reference plugins/inpainting.py:33-38): the Navier-Stokes based method in its fast-marching form,
   HOST code as well (``emap_inpaint_ns_u8``): the same march as Telea's, a pixel = the mean of the known pixels within the radius
   weighted along the isophote direction.  Parity with OpenCV's values unpinned like "telea" (tests/test_inpaint_ns.py)."""
@@ -33,8 +38,9 @@ from .plugin_manager import PluginBase
 
 
 class Inpainting(PluginBase):
-    def __init__(self, cell_n: int = 100, method: str = "telea", emap=None, **kwargs):
+    def __init__(self, cell_n: int = 100, method: str = "telea", emap=None, steps: int = 0, **kwargs):
         super().__init__()
+        self.steps = int(steps)                    # "telea_fronts": fronts per launch (0: the library's default)
         self.method = method if method in ("telea", "ns", "front", "telea_fronts") else "telea"      # (the reference falls back to telea for unknown names, :37-38)
         self.cell_n = cell_n
         self.emap = emap
@@ -44,6 +50,11 @@ class Inpainting(PluginBase):
 
     def plugin_inputs(self, plugin_layer_names):
         return ()                                  # elevation and is_valid of the map only: no resident plane has to come back for it
+
+    def device_op(self, layer_names, plugin_layer_names, semantic_layer_names):
+        if self.method != "telea_fronts":
+            return None                            # "telea" / "ns" are host marches, "front" has its own host door
+        return dict(type="inpaint_fronts", src=None, i0=self.steps)
 
     def __call__(self, elevation_map: np.ndarray, layer_names: List[str], plugin_layers: np.ndarray,
                  plugin_layer_names: List[str], *args) -> np.ndarray:
@@ -92,6 +103,9 @@ class Inpainting(PluginBase):
             rc = lib.emap_inpainter_create(device, ct.c_void_p(stream or None), ct.byref(h))
             if rc != 0:
                 raise _lib.EmapError("emap_inpainter_create failed (%d): no usable HIP device %d" % (rc, device))
+            if self.steps and lib.emap_inpainter_set_steps(h, self.steps) != 0:
+                lib.emap_inpainter_destroy(h)
+                raise _lib.EmapError("Inpainting: steps must lie in 1 .. 16 (got %d)" % self.steps)
             self._ip = h
         return self._ip
 

@@ -4,7 +4,8 @@ extra_params[, type]``, discovery = first ``PluginBase`` subclass of module ``pl
 (5/7/8/9 parameters).  Arrays are NumPy (host copies of device layers); the manager injects ``emap`` (the owning
 ``ElevationMap``) into plugins that accept it so that they can run their arithmetic on the device.
 
-Resident planes.  A plugin may also describe itself as an op of ``emap_plugin_chain`` (``PluginBase.device_op``): its output then stays in
+Resident planes.  A plugin may also describe itself as an op of ``emap_plugin_chain`` (``PluginBase.device_op``: MinFilter, MaxFilter,
+SmoothFilter, Erosion, RobotCentricElevation, and Inpainting with ``method="telea_fronts"``): its output then stays in
 a plane the context owns, next plugins and the GridMap launch read it there, and nothing crosses PCIe (``ElevationMap.get_grid_map_layers``).
 ``PluginManager`` keeps the host array and the planes coherent: per layer it knows which side is newer, downloads a device-newer plane
 before the host looks at it (``layers``, ``get_map_with_name``; before a host plugin only the layers its ``plugin_inputs`` names) and
@@ -184,6 +185,8 @@ class PluginManager(object):
             p = self.plugins[op["dst_plane"]]
             if hasattr(p, "sweeps_run"):
                 p.sweeps_run = None            # nothing waited for the sweeps' counters (MinFilter / MaxFilter on the device route)
+            if hasattr(p, "fronts_run"):
+                p.fronts_run = None            # nor for the largest front (Inpainting with method "telea_fronts")
 
     def run_plan(self, steps, host_step, rotation=None):
         """Run the steps of ``plugin_chain_plan`` in order.  Device ops gather in one chain that is enqueued as late as their order allows:

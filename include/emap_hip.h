@@ -373,13 +373,25 @@ int emap_plugin_plane_read(emap_ctx* ctx, int32_t plane, float* host_out);
  *     plugin's own double reversal).
  *   EMAP_PLUGIN_ROBOT_CENTRIC (EM/plugins/robot_centric_elevation.py:54-57, :96-118): (R6 rx + R7 ry) + R8 h on valid cells, rx =
  *     (float)row * (float)resolution, rotation9 row-major; flag EMAP_PLUGIN_THRESHOLD: 1 / 0 for z >= f0 instead.  src_* ignored.
+ *   EMAP_PLUGIN_INPAINT_FRONTS (plugins/inpainting.py, method "telea_fronts"; EM/plugins/inpainting.py:53-61 around the fill): on the map's
+ *     own RAW elevation / is_valid, src_* ignored.  known = is_valid >= 0.5 (>=: this plugin's own comparison).  With no known cell, or
+ *     with every cell known, the plane is the elevation as it is.  Otherwise h_min / h_max over the known cells (on the device), span =
+ *     (float)((double)h_max - (double)h_min) if h_max > h_min else 1, the image clip((h - h_min) * 255 / span, 0, 255) truncated to 8
+ *     bits (every operation rounded to float32), the fill of emap_inpaint_telea_fronts_u8 with radius 1 on (image, !known) without its
+ *     copies and without its read-back -- ceil((2 cell_n - 2) / S) launches of S fronts, the geometric bound of the L1 distance, instead
+ *     of ceil(max d / S); the launches behind the last front do nothing -- and (float)out * span / 255 + h_min in three roundings.  i0 =
+ *     fronts per launch S, 1 .. 16, or 0 for the default (16); the plane does not depend on it.  i1 must be 0, f0 is ignored, no flag.
+ *     The fronts run is not reported (nothing waits).  The elevation is assumed finite in every cell: the cast of a NaN to 8 bits is
+ *     undefined on the plugin's host route as well, and no rule is made up for it here.
  * src_kind EMAP_PLUGIN_SRC_LAYER: src_index = RAW map layer 0 .. 6 (elevation, variance, is_valid, traversability, time, upper_bound,
  * is_upper_bound: emap_get_layer's planes); EMAP_PLUGIN_SRC_PLANE: a resident plane -- as it is when the op runs, i.e. what an earlier
  * op of the chain or an earlier call left.  Refused with EMAP_ERR_INVALID before anything is enqueued, planes and map untouched: a NULL
  * pointer (rotation9 may be NULL without a ROBOT_CENTRIC op), n_ops outside 1 .. 32, an unknown type / src_kind / flag, a plane outside
- * the reservation, a SMOOTH whose source is its own dst_plane, sizes outside the bounds above, a row-strip context. */
+ * the reservation, a SMOOTH whose source is its own dst_plane, sizes outside the bounds above, a row-strip context.  Every op of a chain
+ * has scratch of its own in the context (two inpaint ops share no image, distance plane or range record). */
 #define EMAP_PLUGIN_MAX_OPS 32
-enum { EMAP_PLUGIN_MIN_FILTER = 0, EMAP_PLUGIN_MAX_FILTER = 1, EMAP_PLUGIN_SMOOTH = 2, EMAP_PLUGIN_EROSION = 3, EMAP_PLUGIN_ROBOT_CENTRIC = 4 };
+enum { EMAP_PLUGIN_MIN_FILTER = 0, EMAP_PLUGIN_MAX_FILTER = 1, EMAP_PLUGIN_SMOOTH = 2, EMAP_PLUGIN_EROSION = 3, EMAP_PLUGIN_ROBOT_CENTRIC = 4,
+       EMAP_PLUGIN_INPAINT_FRONTS = 6 };      /* (5 is unassigned and refused) */
 enum { EMAP_PLUGIN_SRC_LAYER = 0, EMAP_PLUGIN_SRC_PLANE = 1 };
 enum { EMAP_PLUGIN_REVERSE = 1, EMAP_PLUGIN_THRESHOLD = 2 };
 typedef struct emap_plugin_op { int32_t type, dst_plane, src_kind, src_index, i0, i1, flags; float f0; } emap_plugin_op;
