@@ -216,6 +216,12 @@ int emap_host::flush_moves(emap_ctx* ctx) {
 
 // The last frame's stencil pass, left pending by frame_impl for the next frame's fused launch: launched now, exactly as the frame would
 // have launched it.  On an error the pass stays pending.
+// A pass that a frame took along LEAN (count_impl: only the outputs that frame reads, or no launch at all) is still pending, and what is
+// launched here is always the FULL k_post on the map as it is.  The invariant that makes the lean launch safe: between it and the next
+// full pass no entry point reads or changes the map, its planes, its origin or its parameters without passing through this function
+// (SF_CHECK; tests/test_post_settle_surface.py holds the list of the calls that pass by, none of which looks at a plane), the frame
+// that made the lean launch ends with a pass of its own -- pending again, or launched in full -- and a frame that fails in between
+// returns with the flag still set.  Every output is a pure function of the map, so the late full pass writes what an early one would have.
 static int post_part_impl(emap_ctx* ctx, int32_t part);
 int emap_host::post_settle(emap_ctx* ctx) {
   if (!ctx->post_pending) return EMAP_OK;
@@ -785,18 +791,38 @@ static int count_impl(emap_ctx* ctx, const float R[9], const float t[3], const F
     // The stencil pass the frame before left pending runs in ONE grid with this frame's histogram (k_post_hist) when the workgroups of
     // both are resident together -- the launcher asks the occupancy calculator; EMAP_POST_FUSE_MAX_WG (test hook, read per frame) lowers
     // the bound.  Otherwise the pass is launched first and the frame runs the launches it always ran.
+    // What the pass taken along WRITES is what this frame reads of it: traversability in the drift statistics (drift_inlier: k_tile_count,
+    // which runs when gate_possible, and the inlier plane of a frame with a visibility pass), the normals in the visibility pass,
+    // traversability_input nowhere; k_tile_fuse without a visibility pass copies the traversability word through untested, and the
+    // semantic kernels read counts and their own planes.  The frame ends with a pass of its own, pending or launched, that rewrites every
+    // output from the map as it is then, so a launch that wrote less than everything leaves the pass OWED (post_pending stays set), and a
+    // frame that reads nothing launches the plain histogram and leaves it owed as well.  EMAP_POST_LEAN=0 (read per frame: A/B knob and
+    // test hook): the full pass, as before.
     bool hist_done = false;
     if (ctx->post_pending) {
-      if (f && !tm && !own && ctx->kp.mv.n == 0) {
-        long max_wg = 0;
-        if (const char* e = getenv("EMAP_POST_FUSE_MAX_WG")) max_wg = atol(e);
-        hist_done = launch_post_hist(ctx->stream, ctx->device, ctx->kp, ctx->prm.w1, ctx->prm.w2, ctx->prm.w3, ctx->prm.w_out, ctx->cells, ctx->trav_in, ctx->normal,
-                                     ctx->ncells_alloc, ctx->prm.dilation_size, pose, ctx->bg, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->bin_hist, max_wg);
+      const bool along = f && !tm && !own && ctx->kp.mv.n == 0;
+      const bool rays_on = ctx->prm.enable_visibility_cleanup != 0;
+      int out = POST_OUT_FULL;
+      if (along) {
+        out = rays_on ? POST_OUT_TRAV_NORMALS : POST_OUT_TRAV;
+        if (const char* e = getenv("EMAP_POST_LEAN")) { if (atoi(e) == 0) out = POST_OUT_FULL; }
       }
-      if (hist_done) {
-        ctx->post_pending = false; ++ctx->post_fused;
-        ctx->kp.norg_r = ctx->torg_r = ctx->kp.org_r; ctx->kp.norg_c = ctx->torg_c = ctx->kp.org_c;      // outputs carry the current origin (post_part_impl)
-      } else if ((rc = post_settle(ctx))) return rc;
+      if (along && out == POST_OUT_TRAV && !gate_possible) ctx->post_took = 32;      // nothing of the pass is read: no stencil workgroup is launched
+      else {
+        if (along) {
+          long max_wg = 0;
+          if (const char* e = getenv("EMAP_POST_FUSE_MAX_WG")) max_wg = atol(e);
+          hist_done = launch_post_hist(ctx->stream, ctx->device, ctx->kp, ctx->prm.w1, ctx->prm.w2, ctx->prm.w3, ctx->prm.w_out, ctx->cells, ctx->trav_in, ctx->normal,
+                                       ctx->ncells_alloc, ctx->prm.dilation_size, pose, ctx->bg, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->bin_hist, max_wg, out);
+        }
+        if (hist_done) {
+          ++ctx->post_fused;
+          if (out == POST_OUT_FULL) ctx->post_pending = false; else ctx->post_took = 16;
+          // outputs carry the current origin (post_part_impl) -- the planes that were written
+          if (out != POST_OUT_TRAV) { ctx->kp.norg_r = ctx->kp.org_r; ctx->kp.norg_c = ctx->kp.org_c; }
+          if (out == POST_OUT_FULL) { ctx->torg_r = ctx->kp.org_r; ctx->torg_c = ctx->kp.org_c; }
+        } else if ((rc = post_settle(ctx))) return rc;
+      }
     }
     if (!hist_done) launch_bin_hist(ctx->stream, ctx->kp, pose, ctx->bg, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->bin_hist, own, ctx->bin_own_cnt);
     if (tm) CK(hipEventRecord(ctx->ev[ST_SCAN], ctx->stream));
@@ -1196,6 +1222,7 @@ static int frame_impl(emap_ctx* ctx, const float R[9], const float t[3], double 
   // The stencil pass of the frame before may be pending (below).  A binned whole-map frame takes it into its histogram launch
   // (count_impl); every other frame -- a small-frame launch, the atomic path, a sharded or timed frame -- launches it first.
   if (ctx->post_pending && !(!sharded && sf_grid == 0 && !tm && ctx->cloud.n > 0 && takes_bins(ctx, ctx->cloud.n_all)) && (rc = post_settle(ctx))) return rc;
+  ctx->post_took = 0;
   Frame fr; memset(&fr, 0, sizeof fr);
   if ((rc = frame_sem_begin(ctx, rays_on, &fr))) return rc;
   fr.gate_possible = p.enable_drift_compensation && (position_noise > p.position_noise_thresh || orientation_noise > p.orientation_noise_thresh);
@@ -1254,6 +1281,7 @@ static int frame_impl(emap_ctx* ctx, const float R[9], const float t[3], double 
     }
   }
   ctx->update_path = fused_small ? 2 : (ctx->frame_binned ? 1 : 0);
+  ctx->update_path |= ctx->post_took;      // 16: the pending pass was taken along lean, 32: left owed without a launch (count_impl)
   STAGE(ST_FUSE);
   // binned scatter: fusion, commit and averaging happen in ONE tile kernel; with the visibility pass it also writes the inert
   // bitmap and the inlier plane, and the ray effects are applied by k_ray_apply ("average" stage) afterwards
@@ -1293,7 +1321,7 @@ static int frame_impl(emap_ctx* ctx, const float R[9], const float t[3], double 
                  post_hist_tile_rows(ctx->kp, p.dilation_size) != 0;
     if (defer) { if (const char* e = getenv("EMAP_POST_DEFER")) defer = atoi(e) != 0; }
     if (defer) ctx->post_pending = true;
-    else if ((rc = post_part_impl(ctx, 0))) return rc;
+    else { if ((rc = post_part_impl(ctx, 0))) return rc; ctx->post_pending = false; }      // (a full pass: whatever a lean launch left owed is paid)
   }
   STAGE(ST_N);
 #undef STAGE

@@ -142,8 +142,10 @@ struct emap_ctx {
   // The stencil pass of the last frame, not launched yet (frame_impl): the next binned whole-map frame runs it in one grid with its own
   // histogram (k_post_hist); every other way into the library launches it first (post_settle, part of SF_CHECK).  Nothing that changes
   // the map, its origin or the parameters gets past it, so what is launched then is what post_part_impl(ctx, 0) would have launched when
-  // the frame ended.
+  // the frame ended.  A frame may take the pass along LEAN -- only the outputs it reads itself (count_impl) -- or, reading none, not
+  // launch it at all: the pass then stays pending, and the first FULL pass clears the flag (post_settle has the invariant).
   bool post_pending;
+  int post_took;                   // this frame and the pending pass, as bits of update_path: 16 taken along lean, 32 left owed without a launch
   unsigned int post_fused;         // fused launches since creation (emap_post_fused_launches)
   BinGeo bg; BinRec* bin_recs; size_t bin_recs_cap; bool bin_strip;
   float4* bin_own; size_t bin_own_cap; unsigned int* bin_own_cnt;   // staged 16-byte records (BinStg: emap_binned.hip) of the owned points per block (strip contexts without a visibility pass); bin_own_cnt: BIN_MAX_B words, sized once

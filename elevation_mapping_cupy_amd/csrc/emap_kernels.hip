@@ -1098,11 +1098,16 @@ __device__ __forceinline__ float exp_neg(float a) {
 // A MACRO, not a function: as an inlined function the compiler keeps all 120 weights live across the unrolled rows and spills them
 // through v_readlane / v_writelane (+370 instructions per wave, +2 us: measured in round 3); expanded in the row loop it reloads
 // them per row with scalar loads.
+// OUT (a constant of the kernel the macro expands in) is the pass's OUTPUT SET.  The full pass writes everything.  The pass a frame takes
+// along in its histogram launch (k_post_hist) writes what THAT frame reads -- traversability (its drift statistics), the normals too
+// when it runs a visibility pass -- and stays owed: a full pass rewrites every output before anything else can look (post_settle,
+// emap_api.hip).  POST_OUT_TRAV drops the store of traversability_input, the normal epilogue (five IEEE divisions, the square root)
+// and its three stores.  (The values: emap_launch.h.)
 #define POST_CELL(WT, ES, t0, dp, own_valid, do_trav, do_normal, c)                                                         \
   do {                                                                                                                    \
     typedef float v2f __attribute__((ext_vector_type(2)));                                                               \
     const float h = (t0)[0];                                                                                              \
-    trav_in[c] = h;                                                                                                       \
+    if (OUT == POST_OUT_FULL) trav_in[c] = h;                                                                             \
     if (STAGE == 1) break;                                                                                                \
     if (do_trav) {                                                                                                        \
       float acc = 0.f;                                                                                                    \
@@ -1124,6 +1129,7 @@ __device__ __forceinline__ float exp_neg(float a) {
       }                                                                                                                   \
       cells.hot[c].w = exp_neg(acc);                  /* trav: a 4-byte store into the 16-byte hot half */                \
     }                                                                                                                     \
+    if (OUT == POST_OUT_TRAV) break;                                                                                      \
     float nx = 0.f, ny = 0.f, nz = 0.f;                                                                                   \
     if ((do_normal) && (own_valid) > 0.5f) {                              /* (is_valid of the cell itself) */             \
       const float dzdx = (t0)[ES] - h, dzdy = (t0)[(ES) * (dp)] - h;                                                      \
@@ -1241,6 +1247,7 @@ __device__ const NullCold k_null_cold = {0.f, 0.f, 0.f, 1.f};
 template <int PT_R, int STAGE>
 __global__ __launch_bounds__(512) void k_post_dma(KP P, TravW Wt, Cells cells, float* __restrict__ trav_in,
                                                   float* __restrict__ normal, long plane_stride, int d, PostSegs S) {
+  constexpr int OUT = POST_OUT_FULL;
   int seg_b = S.b[0], seg_e = S.e[0], ty = blockIdx.y;
 #pragma unroll
   for (int k = 1; k < 4; ++k) if (k < S.n && (int)blockIdx.y >= S.t0[k]) { seg_b = S.b[k]; seg_e = S.e[k]; ty = blockIdx.y - S.t0[k]; }
@@ -1357,6 +1364,7 @@ __global__ __launch_bounds__(512) void k_post_dma(KP P, TravW Wt, Cells cells, f
 template <int PT_R, int STAGE>
 __global__ __launch_bounds__(PT_R >= 32 ? POST_T32 : 512) void k_post(KP P, TravW Wt, Cells cells, float* __restrict__ trav_in,
                                                     float* __restrict__ normal, long plane_stride, int d, PostSegs S) {
+  constexpr int OUT = POST_OUT_FULL;
 #define POST_BX blockIdx.x
 #define POST_BY blockIdx.y
 #include "emap_post_tile.h"
@@ -1373,11 +1381,11 @@ __global__ __launch_bounds__(PT_R >= 32 ? POST_T32 : 512) void k_post(KP P, Trav
 // hist0 a multiple of 8: workgroup b runs on XCD b % 8, so the histogram workgroup of a chunk then sits on the XCD of its twin in
 // k_bin_scatter (bin_chunk_of_block), as it does in k_bin_hist.  That placement is for speed only; nothing depends on it for the result.
 // The tiles stand in front of the histogram workgroups (hist0 = n_tiles rounded up to 8); the other order was measured
-// (EMAP_POST_HIST_FRONT).  Stage 0, one row interval, 512 threads.
+// (EMAP_POST_HIST_FRONT).  Stage 0, one row interval, 512 threads.  OUT: the output set of the stencil tiles (POST_CELL).
 #ifndef POST_HIST_U
 #define POST_HIST_U 4      /* loads in flight per thread of a histogram workgroup: two batches of 4; one batch of 8 was measured slower */
 #endif
-template <int MODE, int PT_R>
+template <int MODE, int PT_R, int OUT>
 __global__ __launch_bounds__(512) void k_post_hist(KP P, TravW Wt, Cells cells, float* __restrict__ trav_in, float* __restrict__ normal,
                                                    long plane_stride, int d, PostSegs S, int tiles_x, int n_tiles, int tile0, int hist0,
                                                    Pose T, BinGeo G, const float* __restrict__ pts, long n, int stride,
@@ -1786,24 +1794,25 @@ int post_hist_tile_rows(const KP& P, int d) {
   const int R = post_tile_rows(P);
   return (R == 16 || R == 32) && !post_launch_dma(P, R, d) && post_lds_bytes(R, d) <= 150 * 1024 ? R : 0;
 }
-// workgroups of k_post_hist that are resident at once: what the occupancy calculator gives per CU x the CUs (per instantiation, LDS size and device)
-template <class K> static long post_hist_resident(K kern, size_t lds, int dev) {
+// workgroups of k_post_hist that are resident at once: what the occupancy calculator gives per CU x the CUs (per instantiation, LDS size and device;
+// the kernel is a template VALUE: the instantiations share one pointer type, and a function per type would share one memo among them)
+template <auto KERN> static long post_hist_resident(size_t lds, int dev) {
   struct Memo { bool on; size_t lds; long wg; };
   static Memo memo[EM_MAX_DEV];
   Memo& m = memo[dev >= 0 && dev < EM_MAX_DEV ? dev : 0];
   if (m.on && m.lds == lds) return m.wg;
   int per_cu = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 512, lds) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(KERN), 512, lds) != hipSuccess) return 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
   m.on = true; m.lds = lds; m.wg = (long)per_cu * cus;
   return m.wg;
 }
 // The stencil pass launch_post(.., whole map, stage 0) would run + launch_bin_hist of the next frame's cloud in one grid.  false: nothing
 // was launched -- the stencil tiles and the histogram chunks are not resident together (or more than max_wg workgroups: test hook), and
-// the caller runs the two launches.
+// the caller runs the two launches.  out: the output set of the stencil tiles (POST_OUT_*); anything but POST_OUT_FULL leaves the pass owed.
 bool launch_post_hist(hipStream_t s, int dev, const KP& P, const float* w1, const float* w2, const float* w3, const float* wo, Cells cells,
                       float* trav_in, float* normal, long plane_stride, int d, const Pose& T, const BinGeo& G, const float* pts, long n, int stride,
-                      unsigned int* hist, long max_wg) {
+                      unsigned int* hist, long max_wg, int out) {
   const int R = post_hist_tile_rows(P, d);
   if (!R) return false;
   const TravW W = post_weights(w1, w2, w3, wo);
@@ -1819,14 +1828,17 @@ bool launch_post_hist(hipStream_t s, int dev, const KP& P, const float* w1, cons
   const size_t hist_lds = sizeof(unsigned int) * (size_t)G.pitch, lds = post_lds_bytes(R, d) > hist_lds ? post_lds_bytes(R, d) : hist_lds;
   if (lds > 158 * 1024) return false;
   bool ok = false;
-#define POST_HIST_GO(MODE, RR) do { auto kern = k_post_hist<MODE, RR>; static LdsRaised raised; \
+#define POST_HIST_GO(MODE, RR, OO) do { auto kern = k_post_hist<MODE, RR, OO>; static LdsRaised raised; \
     if (!raise_lds(kern, raised, 158 * 1024) && lds > 64 * 1024) break; \
-    const long room = post_hist_resident(kern, lds, dev); \
+    const long room = post_hist_resident<k_post_hist<MODE, RR, OO>>(lds, dev); \
     if (grid > (max_wg > 0 && max_wg < room ? max_wg : room)) break; \
     hipLaunchKernelGGL(kern, dim3((unsigned int)grid), dim3(512), lds, s, P, W, cells, trav_in, normal, plane_stride, d, S, tiles_x, n_tiles, tile0, hist0, \
                        T, G, pts, n, stride, hist); ok = true; } while (0)
-  if (P.mode == 0) { if (R == 32) POST_HIST_GO(0, 32); else POST_HIST_GO(0, 16); }
-  else { if (R == 32) POST_HIST_GO(1, 32); else POST_HIST_GO(1, 16); }
+#define POST_HIST_OUT(MODE, RR) do { if (out == POST_OUT_TRAV) POST_HIST_GO(MODE, RR, POST_OUT_TRAV); \
+    else if (out == POST_OUT_TRAV_NORMALS) POST_HIST_GO(MODE, RR, POST_OUT_TRAV_NORMALS); else POST_HIST_GO(MODE, RR, POST_OUT_FULL); } while (0)
+  if (P.mode == 0) { if (R == 32) POST_HIST_OUT(0, 32); else POST_HIST_OUT(0, 16); }
+  else { if (R == 32) POST_HIST_OUT(1, 32); else POST_HIST_OUT(1, 16); }
+#undef POST_HIST_OUT
 #undef POST_HIST_GO
   return ok;
 }

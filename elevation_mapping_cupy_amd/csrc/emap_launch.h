@@ -92,8 +92,10 @@ void launch_var_time(hipStream_t, const KP&, Cells, int, int);
 int post_tile_rows(const KP&);
 void launch_post(hipStream_t, const KP&, const float*, const float*, const float*, const float*, Cells, float*, float*, long, int, int, const int*, const int*, int, int);
 int post_hist_tile_rows(const KP&, int);
+// output set of the stencil pass a frame takes along (POST_CELL, emap_kernels.hip): everything | no traversability_input | traversability only
+enum { POST_OUT_FULL = 0, POST_OUT_TRAV_NORMALS = 1, POST_OUT_TRAV = 2 };
 bool launch_post_hist(hipStream_t, int, const KP&, const float*, const float*, const float*, const float*, Cells, float*, float*, long, int,
-                      const Pose&, const BinGeo&, const float*, long, int, unsigned int*, long);
+                      const Pose&, const BinGeo&, const float*, long, int, unsigned int*, long, int);
 void launch_get_plane(hipStream_t, const KP&, Cells, int, float*);
 void launch_publish(hipStream_t, const KP&, Cells, const float*, long, int, float, int, float*);
 void launch_set_plane(hipStream_t, const KP&, Cells, int, const float*);

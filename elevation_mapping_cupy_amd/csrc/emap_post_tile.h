@@ -1,7 +1,8 @@
 // The stencil pass of ONE tile, as TEXT: the body of k_post and of the stencil workgroups of k_post_hist (emap_kernels.hip), which
 // include this file inside the kernel with POST_BX / POST_BY defined -- the tile's column in the tile grid and its tile row counted over
 // the launch's row intervals (k_post: blockIdx.x / blockIdx.y; k_post_hist: derived from the linear workgroup index).  It reads the
-// kernel's own parameters P, Wt, cells, trav_in, normal, plane_stride, d, S and the constants PT_R, STAGE.
+// kernel's own parameters P, Wt, cells, trav_in, normal, plane_stride, d, S and the constants PT_R, STAGE and OUT (the output set of
+// POST_CELL: POST_OUT_FULL in k_post; in k_post_hist what the frame that takes the pass along reads).
 // Text and not a __device__ __forceinline__ function, for the reason POST_CELL is a macro: behind a function boundary -- parameters by
 // reference or by value, with or without __restrict__, all measured -- the compiler loads the 120 filter weights of Wt once and keeps
 // them live across the unrolled rows, spilling them through v_readlane / v_writelane: k_post<32, 0> 2973 -> 3589 instructions, 53 -> 56

@@ -572,7 +572,11 @@ int emap_get_stage_times(emap_ctx* ctx, float ms_out[10]);
  * EMAP_SMALL_FRAME=0 in the environment keeps such frames on path 0.
  * Bits 2-3 (the value & 3 is the path above): how the frame fused the channels declared by emap_frame_semantics -- 4 = inside the tile
  * kernel that fused the heights (32-byte sorted records), 8 = 32-byte records, stand-alone semantic kernel (a launch with heavy-tile
- * parts), neither = stand-alone kernels on 16-byte records / the atomic path.  EMAP_SEM_CARRY=0 keeps every frame on the last form. */
+ * parts), neither = stand-alone kernels on 16-byte records / the atomic path.  EMAP_SEM_CARRY=0 keeps every frame on the last form.
+ * Bits 4-5: what the frame did with the pending stencil pass of the frame before it (emap_update) -- 16 = ran it in its histogram launch
+ * with only the outputs the frame reads itself (traversability; the normals too in front of a visibility pass), 32 = read none of them
+ * (drift gate ruled out, no visibility pass) and launched no stencil workgroup; either way the pass stays pending and the next full pass
+ * writes every output.  EMAP_POST_LEAN=0 in the environment: a pass taken along writes everything, as before. */
 int emap_last_update_path(emap_ctx* ctx, int32_t* path);
 /* k_small_frame synchronises its own grid (two barriers inside ONE launch).  If foreign work on the device keeps part of that grid from
  * starting for ~0.1 s, the launch aborts -- one compare-and-swap decides for the whole grid -- and leaves the map, the frame
