@@ -84,6 +84,11 @@ class EmapPluginOp(ct.Structure):
     _fields_ = [(n, ct.c_int32) for n in ("type", "dst_plane", "src_kind", "src_index", "i0", "i1", "flags")] + [("f0", ct.c_float)]
 
 
+class EmapPluginSrc(ct.Structure):
+    """struct emap_plugin_src (include/emap_hip.h: emap_plugin_chain_ex): one entry of the side table of sources."""
+    _fields_ = [(n, ct.c_int32) for n in ("kind", "index", "flags", "reserved")] + [("f0", ct.c_float), ("f1", ct.c_float), ("d0", ct.c_double)]
+
+
 GRID_ORDERS = {"rows": 0, "message": 1}             # EMAP_GRID_ROWS / EMAP_GRID_MESSAGE
 GRID_BUILTIN, GRID_SEMANTIC, GRID_NORMAL_COLOR = 0, 1, 2
 GRID_MAX_LAYERS = 32                                # EMAP_GRID_MAX_LAYERS
@@ -91,8 +96,12 @@ GRID_PLUGIN = 3                                     # EMAP_GRID_PLUGIN: a reside
 GRID_FILL_NAN, GRID_ADD_Z = 1, 2                    # EMAP_GRID_FILL_NAN / EMAP_GRID_ADD_Z
 PLUGIN_MAX_PLANES = PLUGIN_MAX_OPS = 32             # EMAP_PLUGIN_MAX_PLANES / EMAP_PLUGIN_MAX_OPS
 PLUGIN_OPS = {"min_filter": 0, "max_filter": 1, "smooth": 2, "erosion": 3, "robot_centric": 4, "inpaint_fronts": 6}      # EMAP_PLUGIN_MIN_FILTER .. (5: unassigned)
-PLUGIN_SRC_LAYER, PLUGIN_SRC_PLANE = 0, 1           # EMAP_PLUGIN_SRC_*
-PLUGIN_REVERSE, PLUGIN_THRESHOLD = 1, 2             # EMAP_PLUGIN_REVERSE / EMAP_PLUGIN_THRESHOLD
+PLUGIN_OPS_EX = {"semantic_filter": 7, "semantic_trav": 8, "max_layer": 9, "features_pca": 10}      # EMAP_PLUGIN_SEMANTIC_FILTER ..: the ops of emap_plugin_chain_ex (a run of the side table)
+PLUGIN_SRC_LAYER, PLUGIN_SRC_PLANE, PLUGIN_SRC_SEMANTIC = 0, 1, 2      # EMAP_PLUGIN_SRC_*
+PLUGIN_REVERSE, PLUGIN_THRESHOLD, PLUGIN_MIN = 1, 2, 4      # EMAP_PLUGIN_REVERSE / EMAP_PLUGIN_THRESHOLD / EMAP_PLUGIN_MIN (op flags)
+PLUGIN_SRC_AT_MOST, PLUGIN_SRC_ZERO_DEFAULT, PLUGIN_SRC_REVERSE, PLUGIN_SRC_SCALE, PLUGIN_SRC_THRESHOLD = 1, 2, 4, 8, 16      # flags of a source
+PLUGIN_MAX_SRCS = 2048                              # EMAP_PLUGIN_MAX_SRCS
+PLUGIN_SRC_LIMITS = {7: (0, 64), 8: (1, 16), 9: (1, 16), 10: (3, 16)}      # sources an op of emap_plugin_chain_ex takes, by type
 
 MODE = {"reference_fp16": 0, "fp32": 1}
 PLANES = {"elevation": 0, "variance": 1, "is_valid": 2, "traversability": 3, "time": 4, "upper_bound": 5,
@@ -107,7 +116,7 @@ SYMBOLS = [
     "emap_local_drift_sums", "emap_set_scatter_mode", "emap_fuse", "emap_fuse_average", "emap_commit", "emap_rays", "emap_average", "emap_overlap_clear",
     "emap_dilate", "emap_traversability_normals", "emap_post", "emap_post_part", "emap_update_variance", "emap_update_time", "emap_get_stats",
     "emap_get_layer", "emap_set_layer", "emap_publish_layer", "emap_publish_grid_map", "emap_publish_grid_map_ex", "emap_shift", "emap_strip_logical_begin", "emap_semantic_configure", "emap_semantic_update", "emap_frame_semantics",
-    "emap_semantic_get_layer", "emap_semantic_set_layer", "emap_semantic_clear", "emap_semantic_get_alpha", "emap_semantic_set_alpha", "emap_semantic_class_max", "emap_semantic_accumulate", "emap_semantic_finalize", "emap_min_filter", "emap_max_filter", "emap_smooth_filter", "emap_erode", "emap_plugin_planes", "emap_plugin_plane_write", "emap_plugin_plane_read", "emap_plugin_chain", "emap_inpaint_u8", "emap_inpaint_telea_u8", "emap_inpaint_ns_u8", "emap_inpainter_create", "emap_inpainter_destroy", "emap_inpainter_set_steps", "emap_inpaint_telea_fronts_u8", "emap_image_correspondence", "emap_image_get_correspondence",
+    "emap_semantic_get_layer", "emap_semantic_set_layer", "emap_semantic_clear", "emap_semantic_get_alpha", "emap_semantic_set_alpha", "emap_semantic_class_max", "emap_semantic_accumulate", "emap_semantic_finalize", "emap_min_filter", "emap_max_filter", "emap_smooth_filter", "emap_erode", "emap_plugin_planes", "emap_plugin_plane_write", "emap_plugin_plane_read", "emap_plugin_chain", "emap_plugin_chain_ex", "emap_inpaint_u8", "emap_inpaint_telea_u8", "emap_inpaint_ns_u8", "emap_inpainter_create", "emap_inpainter_destroy", "emap_inpainter_set_steps", "emap_inpaint_telea_fronts_u8", "emap_image_correspondence", "emap_image_get_correspondence",
     "emap_image_fuse", "emap_image_set_tolerance", "emap_image_fuse_arrays", "emap_input_image_message", "emap_polygon_mask", "emap_dilate_planes", "emap_halo_bytes", "emap_halo_pack", "emap_halo_unpack", "emap_normal_row_lag", "emap_normal_halo_pack", "emap_normal_halo_unpack", "emap_normal_lag_plan",
     "emap_comm_unique_id", "emap_comm_init", "emap_comm_destroy", "emap_comm_selftest", "emap_comm_count", "emap_comm_wire_bytes", "emap_comm_allreduce_host", "emap_comm_gather_layer", "emap_update_sharded", "emap_set_ray_mode",
     "emap_timer_begin", "emap_timer_end", "emap_enable_stage_timing", "emap_get_stage_times", "emap_last_update_path", "emap_small_frame_aborts", "emap_post_fused_launches",
@@ -167,6 +176,8 @@ def load():
         lib.emap_plugin_plane_write.argtypes = [ct.c_void_p, ct.c_int32, fp]
         lib.emap_plugin_plane_read.argtypes = [ct.c_void_p, ct.c_int32, fp]
         lib.emap_plugin_chain.argtypes = [ct.c_void_p, ct.POINTER(EmapPluginOp), ct.c_int32, fp]
+    if hasattr(lib, "emap_plugin_chain_ex"):
+        lib.emap_plugin_chain_ex.argtypes = [ct.c_void_p, ct.POINTER(EmapPluginOp), ct.c_int32, ct.POINTER(ct.c_float), ct.POINTER(EmapPluginSrc), ct.c_int32]
     got = int(lib.emap_abi_version())
     if got != ABI_VERSION and not os.environ.get("EMAP_HIP_LIB"):
         raise EmapError("%s speaks ABI version %d, this binding expects %d (include/emap_hip.h: EMAP_ABI_VERSION) -- rebuild with "

@@ -12,7 +12,7 @@ LIB = os.path.join(os.path.dirname(HERE), "libemap_hip.so")
 OBJ = os.path.join(HERE, "_obj")
 SOURCES = ["emap_kernels.hip", "emap_binned.hip", "emap_semantic.hip", "emap_api.hip", "emap_api_semantic.hip", "emap_api_plugins.hip", "emap_api_comm.hip",
            "emap_depth.hip", "emap_api_depth.hip", "emap_cloudmsg.hip", "emap_api_cloudmsg.hip", "emap_image_msg.hip", "emap_api_image_msg.hip",
-           "emap_gridmsg.hip", "emap_api_gridmsg.hip", "emap_plugchain.hip", "emap_api_plugchain.hip",
+           "emap_gridmsg.hip", "emap_api_gridmsg.hip", "emap_plugchain.hip", "emap_pca.hip", "emap_api_plugchain.hip",
            "emap_inpaint_host.hip", "emap_inpaint_ns.cpp", "emap_inpaint_fronts.hip", "emap_inpaint_chain.hip"]      # (.cpp: host-only C++)
 HEADERS = ["emap_device.h", "emap_launch.h", "emap_bin_hist.h", "emap_post_tile.h", "emap_camera.h", "emap_host.h", os.path.join("..", "..", "include", "emap_hip.h")]
 DEPS = SOURCES + HEADERS

@@ -183,6 +183,7 @@ struct emap_ctx {
   float* plane_buf; int plane_n, plane_cap;
   float* chain_buf; size_t chain_cap; unsigned int* chain_cnt; size_t chain_cnt_cap; float* chain_red; size_t chain_red_cap;   // floats / words
   unsigned char* chain_inp; size_t chain_inp_cap;      // bytes: the byte images, fronts state and range records of the chain's inpaint ops, one set per op
+  double* chain_pca; size_t chain_pca_cap;            // doubles: partial sums, means, moments, eigenvectors and score ranges of the chain's FEATURES_PCA ops, one set per op
   // frame state
   bool use_override; double sum_override; unsigned int cnt_override;
   bool committed;

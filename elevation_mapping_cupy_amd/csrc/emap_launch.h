@@ -156,6 +156,29 @@ void launch_range(hipStream_t, long, const float*, int, float*, float*);
 void launch_quantise(hipStream_t, long, const float*, int, const float*, float*);
 void launch_dequantise(hipStream_t, long, const float*, const float*, int, const float*, float*);
 void launch_robot_centric(hipStream_t, int, float, const float*, int, float, const float*, const float*, float*);
+// The ops that read several layers (EMAP_PLUGIN_SEMANTIC_FILTER .. _FEATURES_PCA).  PlugSrcs: the op's run of the side table, by value --
+// code[k] = kind << 8 | index (kind 0: RAW map layer read in the cells, 1: resident plane `index` of `planes`, 2: semantic layer `index` of
+// `sem`, planes of sem_plane floats at the map's circular origin); PlugPars: the flags and constants of the ops with at most 16 sources.
+#define EM_PLUG_SRC_MAX 64
+#define EM_PLUG_PAR_MAX 16
+struct PlugSrcs { int n, pad_; long sem_plane; const float* sem; const float* planes; unsigned short code[EM_PLUG_SRC_MAX]; };
+struct PlugPars { int flags[EM_PLUG_PAR_MAX]; float f0[EM_PLUG_PAR_MAX], f1[EM_PLUG_PAR_MAX]; double d0[EM_PLUG_PAR_MAX]; };
+void launch_semantic_filter(hipStream_t, const KP&, Cells, const PlugSrcs&, float* dst);
+void launch_semantic_trav(hipStream_t, const KP&, Cells, const PlugSrcs&, const PlugPars&, float* dst);
+void launch_max_layer(hipStream_t, const KP&, Cells, const PlugSrcs&, const PlugPars&, int take_min, float* dst);
+// FEATURES_PCA (emap_pca.hip).  Scratch of one op, in doubles: per-workgroup partials of the means (16 each), of the moments (256 each)
+// and of the score ranges (6 each), behind them the folded means (16), moments (256), the three signed eigenvectors (48) and lo / hi (6)
+#define EM_PCA_PARTS 256
+#define EM_PCA_F 16
+#define EM_PCA_DOUBLES ((size_t)EM_PCA_PARTS * (EM_PCA_F + EM_PCA_F * EM_PCA_F + 6) + EM_PCA_F + EM_PCA_F * EM_PCA_F + 3 * EM_PCA_F + 6)
+void launch_features_pca(hipStream_t, const KP&, Cells, const PlugSrcs&, double* scratch, float* dst);
+// the value of source k of S at the logical cell li = r * C + c of a full map, ci = owned_cell(P, r, c)
+__device__ __forceinline__ float plug_src_read(const PlugSrcs& S, int k, const Cells& cells, long L, long li, long ci) {
+  const int code = S.code[k], kind = code >> 8, idx = code & 255;      // (uniform: the table travels in the kernel's arguments)
+  if (kind == 0) return idx < 4 ? reinterpret_cast<const float*>(cells.hot + ci)[idx] : reinterpret_cast<const float*>(cells.cold + ci)[idx - 4];
+  if (kind == 1) return S.planes[(long)idx * L + li];
+  return S.sem[(long)idx * S.sem_plane + ci];
+}
 
 // Inpainting on resident planes (EMAP_PLUGIN_INPAINT_FRONTS).  FrontsDev: the device images and planes of one run of the fronts pipeline
 // (emap_inpaint_fronts.hip) -- the handle of emap_inpaint_telea_fronts_u8 owns one, every inpaint op of a chain carves its own out of the

@@ -155,3 +155,92 @@ void launch_robot_centric(hipStream_t s, int C, float res, const float* R9, int 
   hipLaunchKernelGGL(k_robot_centric, dim3((unsigned int)(((long)C * C + EM_BLOCK - 1) / EM_BLOCK)), dim3(EM_BLOCK), 0, s, C, res, R9[6], R9[7], R9[8],
                      use_threshold, threshold, h, valid, out);
 }
+
+// ---- the plugins that read several layers: one thread per logical cell, every source read once, one store ---------------------------------
+// The table of sources travels in the kernel's arguments, so the walk over it is uniform and nothing is staged in scratch planes.  The
+// plugins run under NumPy 2 (NEP 50): a Python float beside a float32 array keeps the operation in float32, a NumPy float64 scalar
+// widens it to double -- which of the two each step is, is written at the step.
+__device__ __forceinline__ bool plug_cell(const KP& P, long& li, long& ci) {
+  li = (long)blockIdx.x * EM_BLOCK + threadIdx.x;
+  if (li >= (long)P.C * P.C) return false;
+  const int r = (int)(li / P.C), c = (int)(li - (long)r * P.C);
+  ci = owned_cell(P, r, c);      // (a full map owns every row)
+  return ci >= 0;
+}
+static unsigned int plug_grid(const KP& P) { return (unsigned int)(((long)P.C * P.C + EM_BLOCK - 1) / EM_BLOCK); }
+
+// SemanticFilter (EM/plugins/semantic_filter.py:128, :132): np.argmax over the sources -- the first NaN wins, otherwise the first maximum
+// (a later value replaces the best only when it is GREATER, so -0 and +0 tie) -- then entry id + 1 of the colour table (:42-62), dealt
+// from the bits of the index here: bit 3 j + ch -> bit 7 - j of channel ch; entries 1, 2 and 3 are the reference's overrides.
+__device__ __forceinline__ unsigned int sem_filter_colour(unsigned int i) {
+  unsigned int r = 0u, g = 0u, b = 0u;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    r |= ((i >> (3 * j)) & 1u) << (7 - j); g |= ((i >> (3 * j + 1)) & 1u) << (7 - j); b |= ((i >> (3 * j + 2)) & 1u) << (7 - j);
+  }
+  if (i == 1u || i == 2u) { r = 81u; g = 113u; b = 162u; }
+  if (i == 3u) { r = 188u; g = 63u; b = 59u; }
+  return (r << 16) | (g << 8) | b;
+}
+__global__ __launch_bounds__(EM_BLOCK) void k_semantic_filter(KP P, Cells cells, PlugSrcs S, float* __restrict__ dst) {
+  long li, ci;
+  if (!plug_cell(P, li, ci)) return;
+  const long L = (long)P.C * P.C;
+  int best = 0; float bv = 0.f; bool nan = false;
+  for (int k = 0; k < S.n; ++k) {
+    const float v = plug_src_read(S, k, cells, L, li, ci);
+    if (k == 0) { bv = v; nan = v != v; }
+    else if (!nan) {
+      if (v != v) { best = k; nan = true; } else if (v > bv) { best = k; bv = v; }
+    }
+  }
+  dst[li] = __uint_as_float(sem_filter_colour((unsigned int)best + 1u));
+}
+void launch_semantic_filter(hipStream_t s, const KP& P, Cells cells, const PlugSrcs& S, float* dst) {
+  hipLaunchKernelGGL(k_semantic_filter, dim3(plug_grid(P)), dim3(EM_BLOCK), 0, s, P, cells, S, dst);
+}
+
+// SemanticTraversability (EM/plugins/semantic_traversability.py:70-82): the plugin keeps its thresholds as np.float64 scalars, so
+// layer <= thresholds[it] compares in DOUBLE (0.3f <= 0.3 is false: the float is the larger); a NaN compares false both ways.  The
+// vote sum is a small integer, so `votes <= 0.9` is "nobody voted"; np.where(..., 0.1, 1.0) is float64 and the manager's cast to
+// float32 makes it 0.1f.
+__global__ __launch_bounds__(EM_BLOCK) void k_semantic_trav(KP P, Cells cells, PlugSrcs S, PlugPars R, float* __restrict__ dst) {
+  long li, ci;
+  if (!plug_cell(P, li, ci)) return;
+  const long L = (long)P.C * P.C;
+  bool any = false;
+  for (int k = 0; k < S.n; ++k) {
+    const double x = (double)plug_src_read(S, k, cells, L, li, ci);
+    any |= (R.flags[k] & 1) ? x <= R.d0[k] : x >= R.d0[k];      // (1: EMAP_PLUGIN_SRC_AT_MOST)
+  }
+  dst[li] = any ? 1.0f : 0.1f;
+}
+void launch_semantic_trav(hipStream_t s, const KP& P, Cells cells, const PlugSrcs& S, const PlugPars& R, float* dst) {
+  hipLaunchKernelGGL(k_semantic_trav, dim3(plug_grid(P)), dim3(EM_BLOCK), 0, s, P, cells, S, R, dst);
+}
+
+// MaxLayerFilter (EM/plugins/max_layer_filter.py:66-108).  Every step of a layer stays float32: np.where(layer == 0.0, float(d), layer),
+// 1.0 - layer, layer * float(s) and layer > float(t) all meet a Python float.  The thresholded layers are int64 and np.stack widens a
+// mixed stack to float64, but 0 / 1 and a float32 are exact there and the manager casts the result back, so the reduction runs in float32
+// on the same values.  np.max / np.min along the first axis of the stack: acc = acc > x ? acc : x (acc < x for the minimum) in stack
+// order -- of two equal values the LATER one is kept, which is what the sign of a zero shows -- and any NaN makes the result NaN.
+__global__ __launch_bounds__(EM_BLOCK) void k_max_layer(KP P, Cells cells, PlugSrcs S, PlugPars R, int take_min, float* __restrict__ dst) {
+  long li, ci;
+  if (!plug_cell(P, li, ci)) return;
+  const long L = (long)P.C * P.C;
+  float acc = 0.f; bool nan = false;
+  for (int k = 0; k < S.n; ++k) {
+    float x = plug_src_read(S, k, cells, L, li, ci);
+    const int fl = R.flags[k];
+    if ((fl & 2) && x == 0.0f) x = R.f0[k];                       // EMAP_PLUGIN_SRC_ZERO_DEFAULT (:75)
+    if (fl & 4) x = __fsub_rn(1.0f, x);                           // EMAP_PLUGIN_SRC_REVERSE (:88)
+    if (fl & 8) x = __fmul_rn(x, R.f1[k]);                        // EMAP_PLUGIN_SRC_SCALE (:90)
+    if (fl & 16) x = x > (float)R.d0[k] ? 1.0f : 0.0f;            // EMAP_PLUGIN_SRC_THRESHOLD (:92)
+    nan |= x != x;
+    if (k == 0) acc = x; else acc = take_min ? (acc < x ? acc : x) : (acc > x ? acc : x);
+  }
+  dst[li] = nan ? __uint_as_float(0x7fc00000u) : acc;
+}
+void launch_max_layer(hipStream_t s, const KP& P, Cells cells, const PlugSrcs& S, const PlugPars& R, int take_min, float* dst) {
+  hipLaunchKernelGGL(k_max_layer, dim3(plug_grid(P)), dim3(EM_BLOCK), 0, s, P, cells, S, R, take_min, dst);
+}

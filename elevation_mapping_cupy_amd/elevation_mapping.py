@@ -951,9 +951,12 @@ class ElevationMap:
 
         Plugin layers are computed in list order, as one ``get_map_with_name_ref`` per layer computes them.  A plugin that describes itself
         as a device op (``PluginBase.device_op``: MinFilter, MaxFilter, SmoothFilter, Erosion, RobotCentricElevation, Inpainting with
-        ``method="telea_fronts"``) joins a chain of launches that is enqueued without a wait and leaves its output in a resident plane
-        (``plugins/plugin_manager.py``); the others (Inpainting with a host method, the semantic plugins) take their host route and put
-        their plane into ``array`` on the host.  Then ONE device launch writes every
+        ``method="telea_fronts"``, and the semantic plugins SemanticFilter, SemanticTraversability, MaxLayerFilter and FeaturesPca, which read
+        map layers, plugin planes and semantic layers where they lie on the device) joins a chain of launches that is enqueued without a
+        wait and leaves its output in a resident plane (``plugins/plugin_manager.py``); the others (Inpainting with a host method, a
+        configuration a plugin declines: e.g. a PCA of fewer than 3 or more than 16 layers, a layer-name ``default_value``) take their host
+        route and put their plane into ``array`` on the host.  A device FeaturesPca has the host route's definition, not its last bit: a
+        colour level may differ by 1 in a few cells.  Then ONE device launch writes every
         built-in, semantic and resident plugin layer, with one copy and one wait (groups of 32 beyond 32 layers).  ``last_plugin_route`` tells
         which route each plugin layer took; ``EMAP_PLUGIN_RESIDENT=0`` in the environment sends every plugin through its host route.  The
         whole call runs under one ``map_lock``."""

@@ -52,3 +52,22 @@ class FeaturesPca(PluginBase):
         span = np.where(hi > lo, hi - lo, 1.0)
         img = ((comp - lo) / span * 255).astype(np.uint8).astype(np.uint32)
         return ((img[:, :, 0] << np.uint32(16)) | (img[:, :, 1] << np.uint32(8)) | img[:, :, 2]).view(np.float32)
+
+    def device_op(self, layer_names, plugin_layer_names, semantic_layer_names):
+        """``EMAP_PLUGIN_FEATURES_PCA``: means, centred moments, a Jacobi eigen-solve and the scaled scores on the device -- the same
+        definition as ``_pca3``, not the same last bit: a level may differ by 1 in a few cells.  Declined (host
+        route): fewer than 3 or more than 16 matching layers, a matching map layer beyond the 7 RAW ones."""
+        srcs = []
+        for group in (layer_names, plugin_layer_names, semantic_layer_names):
+            for i in self.get_layer_indices(list(group)):
+                q = self.source_entry(list(group)[i], group if group is layer_names else (), group if group is plugin_layer_names else (),
+                                      group if group is semantic_layer_names else ())
+                if q is None:
+                    return None
+                srcs.append(q)
+        if not 3 <= len(srcs) <= 16:
+            return None
+        return dict(type="features_pca", srcs=srcs, flags=0)
+
+    def plugin_inputs(self, plugin_layer_names):
+        return [plugin_layer_names[i] for i in self.get_layer_indices(list(plugin_layer_names))]

@@ -42,3 +42,36 @@ class MaxLayerFilter(PluginBase):
             return elevation_map[list(layer_names).index("traversability")]
         stack = np.stack(prepared, axis=0)
         return stack.min(axis=0) if self.min_or_max == "min" else stack.max(axis=0)
+
+    def device_op(self, layer_names, plugin_layer_names, semantic_layer_names):
+        """``EMAP_PLUGIN_MAX_LAYER``: the per-layer steps and the reduction on the device, the layers that exist in the plugin's order (a
+        missing one is skipped, as on the host).  Declined (host route): a layer-name ``default_value``, none of the layers found, a
+        found map layer beyond the 7 RAW ones, fewer ``reverse`` / ``thresholds`` entries than layers (the host route raises)."""
+        from .._lib import PLUGIN_MIN, PLUGIN_SRC_REVERSE, PLUGIN_SRC_SCALE, PLUGIN_SRC_THRESHOLD, PLUGIN_SRC_ZERO_DEFAULT
+        if isinstance(self.default_value, str) or len(self.reverse) < len(self.layers) or len(self.thresholds) < len(self.layers):
+            return None
+        srcs = []
+        for it, name in enumerate(self.layers):
+            if name not in layer_names and name not in plugin_layer_names and name not in semantic_layer_names:
+                continue
+            flags, f0, f1, d0 = 0, 0.0, 0.0, 0.0
+            if isinstance(self.default_value, float):
+                flags, f0 = flags | PLUGIN_SRC_ZERO_DEFAULT, float(self.default_value)
+            if self.reverse[it]:
+                flags |= PLUGIN_SRC_REVERSE
+            if len(self.scales) > it and isinstance(self.scales[it], float):
+                flags, f1 = flags | PLUGIN_SRC_SCALE, float(self.scales[it])
+            if isinstance(self.thresholds[it], float):
+                flags, d0 = flags | PLUGIN_SRC_THRESHOLD, float(self.thresholds[it])
+            q = self.source_entry(name, layer_names, plugin_layer_names, semantic_layer_names, flags=flags, f0=f0, f1=f1, d0=d0)
+            if q is None:
+                return None
+            srcs.append(q)
+        if not srcs:
+            return None
+        return dict(type="max_layer", srcs=srcs, flags=PLUGIN_MIN if self.min_or_max == "min" else 0)
+
+    def plugin_inputs(self, plugin_layer_names):
+        if isinstance(self.default_value, str):
+            return None
+        return [n for n in self.layers if n in plugin_layer_names]

@@ -5,7 +5,9 @@ extra_params[, type]``, discovery = first ``PluginBase`` subclass of module ``pl
 ``ElevationMap``) into plugins that accept it so that they can run their arithmetic on the device.
 
 Resident planes.  A plugin may also describe itself as an op of ``emap_plugin_chain`` (``PluginBase.device_op``: MinFilter, MaxFilter,
-SmoothFilter, Erosion, RobotCentricElevation, and Inpainting with ``method="telea_fronts"``): its output then stays in
+SmoothFilter, Erosion, RobotCentricElevation, Inpainting with ``method="telea_fronts"``, and the semantic plugins SemanticFilter,
+SemanticTraversability, MaxLayerFilter and FeaturesPca, which read a list of sources -- map layers, plugin planes and semantic layers -- from the
+side table of ``emap_plugin_chain_ex``): its output then stays in
 a plane the context owns, next plugins and the GridMap launch read it there, and nothing crosses PCIe (``ElevationMap.get_grid_map_layers``).
 ``PluginManager`` keeps the host array and the planes coherent: per layer it knows which side is newer, downloads a device-newer plane
 before the host looks at it (``layers``, ``get_map_with_name``; before a host plugin only the layers its ``plugin_inputs`` names) and
@@ -25,8 +27,8 @@ import ctypes as ct
 import numpy as np
 import yaml
 
-from .._lib import (PLUGIN_MAX_OPS, PLUGIN_MAX_PLANES, PLUGIN_OPS, PLUGIN_REVERSE, PLUGIN_SRC_LAYER, PLUGIN_SRC_PLANE, PLUGIN_THRESHOLD, EmapPluginOp,
-                    f32p)
+from .._lib import (PLUGIN_MAX_OPS, PLUGIN_MAX_PLANES, PLUGIN_OPS, PLUGIN_OPS_EX, PLUGIN_REVERSE, PLUGIN_SRC_LAYER, PLUGIN_SRC_LIMITS, PLUGIN_SRC_PLANE, PLUGIN_SRC_SEMANTIC,
+                    PLUGIN_THRESHOLD, EmapPluginOp, EmapPluginSrc, f32p)
 
 
 @dataclass
@@ -50,7 +52,9 @@ class PluginBase(ABC):
     def device_op(self, layer_names, plugin_layer_names, semantic_layer_names):
         """This plugin as an op of ``emap_plugin_chain`` (include/emap_hip.h), or ``None`` when this configuration cannot run on resident
         planes: ``dict(type=<key of _lib.PLUGIN_OPS>, src=None | ("layer", i) | ("plane", k), i0=0, i1=0, flags=0, f0=0.0)`` with ``i`` the
-        index in ``layer_names`` and ``k`` the index in ``plugin_layer_names``.  The op must leave, bit for bit, what ``__call__`` returns."""
+        index in ``layer_names`` and ``k`` the index in ``plugin_layer_names``.  An op that reads several layers (``emap_plugin_chain_ex``)
+        returns ``dict(type=<key of _lib.PLUGIN_OPS_EX>, srcs=[<source_entry>, ...], flags=0)`` instead: its sources in the order the plugin stacks them.  The op must
+        leave, bit for bit, what ``__call__`` returns."""
         return None
 
     def plugin_inputs(self, plugin_layer_names):
@@ -66,6 +70,23 @@ class PluginBase(ABC):
         if name in plugin_layer_names:
             return ("plane", plugin_layer_names.index(name))
         return None
+
+    @staticmethod
+    def source_entry(name, layer_names, plugin_layer_names, semantic_layer_names, flags=0, f0=0.0, f1=0.0, d0=0.0):
+        """One entry of the side table of ``emap_plugin_chain_ex`` for the input layer ``name``, looked up like ``get_layer_data`` does (map
+        layers, then plugin layers, then semantic layers): ``dict(kind=PLUGIN_SRC_LAYER | _PLANE | _SEMANTIC, index=, flags=, f0=, f1=,
+        d0=)``, or ``None`` for a name that exists nowhere or a map layer beyond the 7 RAW ones."""
+        if name in layer_names:
+            kind, index = PLUGIN_SRC_LAYER, list(layer_names).index(name)
+            if index > 6:
+                return None
+        elif name in plugin_layer_names:
+            kind, index = PLUGIN_SRC_PLANE, list(plugin_layer_names).index(name)
+        elif name in semantic_layer_names:
+            kind, index = PLUGIN_SRC_SEMANTIC, list(semantic_layer_names).index(name)
+        else:
+            return None
+        return dict(kind=kind, index=int(index), flags=int(flags), f0=float(f0), f1=float(f1), d0=float(d0))
 
     def get_layer_data(self, elevation_map, layer_names, plugin_layers, plugin_layer_names, semantic_map,
                        semantic_layer_names, name: str) -> Optional[np.ndarray]:
@@ -84,9 +105,15 @@ def plugin_chain_plan(names, plugins, plugin_layer_names, layer_names, semantic_
     ``plugin_layer_names[k]``.  Returns a list of steps in the order of ``names``: ``("device", name, op)`` -- ``op`` a dict with the fields of
     ``struct emap_plugin_op`` (``type, dst_plane, src_kind, src_index, i0, i1, flags, f0``; plane k = plugin layer k) -- or ``("host", name)``
     for a plugin without ``device_op``, a configuration its ``device_op`` declines (``None``), an op that would read its own plane, a layer
-    beyond the 32 planes (``PLUGIN_MAX_PLANES``), or everything with ``resident=False``.  Names that are no plugin layer are left out."""
+    beyond the 32 planes (``PLUGIN_MAX_PLANES``), or everything with ``resident=False``.  Names that are no plugin layer are left out.
+
+    An op with ``srcs`` (the semantic plugins) also carries ``srcs``, its run of the side table of ``emap_plugin_chain_ex`` as a list of
+    ``dict(kind, index, flags, f0, f1, d0)``; the runs of the plan's device steps lie one behind the other: ``src_index`` is the first entry of
+    the op's run in that table and ``i0`` its length (``side_table(steps)`` is the table; a chain that holds only some of the ops re-bases
+    the runs, ``PluginManager._enqueue``).  Such an op goes to the host when it has more or fewer sources than its type takes
+    (``PLUGIN_SRC_LIMITS``), when a source is its own plane or a plane beyond the 32, or when an entry is malformed."""
     plugin_layer_names, layer_names, semantic_layer_names = list(plugin_layer_names), list(layer_names), list(semantic_layer_names)
-    steps = []
+    steps, table_len = [], 0
     for n in names:
         if n not in plugin_layer_names:
             continue
@@ -98,6 +125,22 @@ def plugin_chain_plan(names, plugins, plugin_layer_names, layer_names, semantic_
             src = d.get("src")
             if src is not None and (src[0] not in ("layer", "plane") or (src[0] == "plane" and (src[1] == k or src[1] >= PLUGIN_MAX_PLANES))):
                 d = None
+        if d is not None and "srcs" in d:
+            t = PLUGIN_OPS_EX[d["type"]]
+            srcs = [dict(kind=int(q["kind"]), index=int(q["index"]), flags=int(q.get("flags", 0)), f0=float(q.get("f0", 0.0)), f1=float(q.get("f1", 0.0)),
+                         d0=float(q.get("d0", 0.0))) for q in d["srcs"]]
+            lo, hi = PLUGIN_SRC_LIMITS.get(t, (0, -1))
+            bad = not lo <= len(srcs) <= hi
+            for q in srcs:
+                bad = bad or q["kind"] not in (PLUGIN_SRC_LAYER, PLUGIN_SRC_PLANE, PLUGIN_SRC_SEMANTIC) or q["index"] < 0 \
+                    or (q["kind"] == PLUGIN_SRC_LAYER and q["index"] > 6) or (q["kind"] == PLUGIN_SRC_SEMANTIC and q["index"] >= len(semantic_layer_names)) \
+                    or (q["kind"] == PLUGIN_SRC_PLANE and (q["index"] == k or q["index"] >= min(PLUGIN_MAX_PLANES, len(plugin_layer_names))))
+            if not bad:
+                steps.append(("device", n, dict(type=t, dst_plane=k, src_kind=PLUGIN_SRC_LAYER, src_index=table_len, i0=len(srcs), i1=0,
+                                                flags=int(d.get("flags", 0)), f0=0.0, srcs=srcs)))
+                table_len += len(srcs)
+                continue
+            d = None
         if d is None:
             steps.append(("host", n))
             continue
@@ -107,6 +150,18 @@ def plugin_chain_plan(names, plugins, plugin_layer_names, layer_names, semantic_
                                         src_index=int(src[1]) if src is not None else 0, i0=int(d.get("i0", 0)), i1=int(d.get("i1", 0)),
                                         flags=int(d.get("flags", 0)), f0=float(d.get("f0", 0.0)))))
     return steps
+
+
+def side_table(steps):
+    """the side table of sources of a plan's device steps, in step order (``src_index`` / ``i0`` of the ops point into it)"""
+    return [q for st in steps if st[0] == "device" for q in st[2].get("srcs", ())]
+
+
+def op_source_planes(op):
+    """the resident planes an op reads"""
+    if "srcs" in op:
+        return [q["index"] for q in op["srcs"] if q["kind"] == PLUGIN_SRC_PLANE]
+    return [op["src_index"]] if op["src_kind"] == PLUGIN_SRC_PLANE else []
 
 
 class PluginManager(object):
@@ -172,14 +227,25 @@ class PluginManager(object):
         return self._host[idx]
 
     def _enqueue(self, ops, rotation):
-        """one ``emap_plugin_chain`` call (no wait); the planes it writes are then newer on the device"""
+        """one ``emap_plugin_chain`` call -- ``emap_plugin_chain_ex`` when an op brings sources: their runs are laid one behind the other into
+        the chain's own side table -- (no wait); the planes it writes are then newer on the device"""
         self._reserve()
         table = (EmapPluginOp * len(ops))()
+        srcs = []
         for t, op in zip(table, ops):
             for f, _ in EmapPluginOp._fields_:
                 setattr(t, f, op[f])
+            if "srcs" in op:
+                t.src_index, t.i0 = len(srcs), len(op["srcs"])
+                srcs += op["srcs"]
         R = np.ascontiguousarray(np.asarray(rotation if rotation is not None else np.eye(3), np.float32).reshape(-1))
-        self._call("emap_plugin_chain", table, len(ops), f32p(R))
+        if any("srcs" in op for op in ops):
+            side = (EmapPluginSrc * max(1, len(srcs)))()
+            for t, q in zip(side, srcs):
+                t.kind, t.index, t.flags, t.reserved, t.f0, t.f1, t.d0 = q["kind"], q["index"], q["flags"], 0, q["f0"], q["f1"], q["d0"]
+            self._call("emap_plugin_chain_ex", table, len(ops), f32p(R), side, len(srcs))
+        else:
+            self._call("emap_plugin_chain", table, len(ops), f32p(R))
         for op in ops:
             self._newer[op["dst_plane"]] = "device"
             p = self.plugins[op["dst_plane"]]
@@ -191,7 +257,8 @@ class PluginManager(object):
     def run_plan(self, steps, host_step, rotation=None):
         """Run the steps of ``plugin_chain_plan`` in order.  Device ops gather in one chain that is enqueued as late as their order allows:
         at the end, before a host plugin that reads (``plugin_inputs``) a plane the chain writes, before an upload a later op needs, or
-        when it holds 32 ops (``PLUGIN_MAX_OPS``).  ``host_step(name)`` runs a host plugin (``update_with_name``).  Returns
+        when it holds 32 ops (``PLUGIN_MAX_OPS``).  Every plane an op reads -- each plane source of a semantic op -- that is newer on the host goes
+        up first, unless an op waiting in the chain writes it.  ``host_step(name)`` runs a host plugin (``update_with_name``).  Returns
         ``{name: "device" | "host"}``."""
         route, pending = {}, []
 
@@ -204,10 +271,11 @@ class PluginManager(object):
             name = step[1]
             if step[0] == "device":
                 op = step[2]
-                if op["src_kind"] == PLUGIN_SRC_PLANE and self._newer[op["src_index"]] == "host" \
-                        and op["src_index"] not in [q["dst_plane"] for q in pending]:
-                    flush()                    # (an op waiting in the chain may read the plane as it is now)
-                    self._upload(op["src_index"])
+                stale = [p for p in op_source_planes(op) if self._newer[p] == "host" and p not in [q["dst_plane"] for q in pending]]
+                if stale:
+                    flush()                    # (an op waiting in the chain may read the planes as they are now)
+                    for p in sorted(set(stale)):
+                        self._upload(p)
                 if len(pending) == PLUGIN_MAX_OPS:
                     flush()
                 pending.append(op)

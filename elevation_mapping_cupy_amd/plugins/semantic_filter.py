@@ -44,3 +44,19 @@ class SemanticFilter(PluginBase):
         else:
             class_id = np.zeros(np.asarray(elevation_map[0]).shape, np.int64)
         return self.color_encoding[class_id]
+
+    def device_op(self, layer_names, plugin_layer_names, semantic_layer_names):
+        """``EMAP_PLUGIN_SEMANTIC_FILTER``: argmax and colour on the device.  Declined (host route): a matching map layer beyond the 7 RAW
+        ones.  More than 64 sources, or the plugin's own layer among them, is declined by ``plugin_chain_plan``."""
+        srcs = []
+        for group in (layer_names, plugin_layer_names, semantic_layer_names):      # (a name is looked up in ITS list: the same name may exist in two)
+            for i in self.get_layer_indices(list(group)):
+                q = self.source_entry(list(group)[i], group if group is layer_names else (), group if group is plugin_layer_names else (),
+                                      group if group is semantic_layer_names else ())
+                if q is None:
+                    return None
+                srcs.append(q)
+        return dict(type="semantic_filter", srcs=srcs, flags=0)
+
+    def plugin_inputs(self, plugin_layer_names):
+        return [plugin_layer_names[i] for i in self.get_layer_indices(list(plugin_layer_names))]

@@ -29,3 +29,22 @@ class SemanticTraversability(PluginBase):
             hit = layer <= self.thresholds[it] if self.type[it] == "traversability" else layer >= self.thresholds[it]
             votes += hit
         return np.where(votes <= 0.9, 0.1, 1.0)
+
+    def device_op(self, layer_names, plugin_layer_names, semantic_layer_names):
+        """``EMAP_PLUGIN_SEMANTIC_TRAV``: the votes on the device; the thresholds travel as the float64 the host compares with.  Declined
+        (host route): a layer that is neither a map layer nor a plugin layer (the host route prints and leaves the layer as it is), no
+        layer at all, fewer thresholds or types than layers (the host route raises)."""
+        from .._lib import PLUGIN_SRC_AT_MOST
+        if not self.layers or len(self.thresholds) < len(self.layers) or len(self.type) < len(self.layers):
+            return None
+        srcs = []
+        for it, name in enumerate(self.layers):
+            q = self.source_entry(name, layer_names, plugin_layer_names, (), flags=PLUGIN_SRC_AT_MOST if self.type[it] == "traversability" else 0,
+                                  d0=float(self.thresholds[it]))
+            if q is None:
+                return None
+            srcs.append(q)
+        return dict(type="semantic_trav", srcs=srcs, flags=0)
+
+    def plugin_inputs(self, plugin_layer_names):
+        return [n for n in self.layers if n in plugin_layer_names]

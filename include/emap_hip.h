@@ -396,6 +396,50 @@ enum { EMAP_PLUGIN_SRC_LAYER = 0, EMAP_PLUGIN_SRC_PLANE = 1 };
 enum { EMAP_PLUGIN_REVERSE = 1, EMAP_PLUGIN_THRESHOLD = 2 };
 typedef struct emap_plugin_op { int32_t type, dst_plane, src_kind, src_index, i0, i1, flags; float f0; } emap_plugin_op;
 int emap_plugin_chain(emap_ctx* ctx, const emap_plugin_op* ops, int32_t n_ops, const float* rotation9);
+/* emap_plugin_chain_ex: emap_plugin_chain with a side table of sources, for the ops that read SEVERAL layers -- the reference's four
+ * semantic plugins.  For such an op src_kind is ignored, src_index is the first entry of the op's run in srcs[0 .. n_srcs) and i0 the
+ * number of entries; i1 must be 0 and f0 is ignored.  An entry names its layer by kind / index -- EMAP_PLUGIN_SRC_LAYER (RAW map layer
+ * 0 .. 6), EMAP_PLUGIN_SRC_PLANE (resident plane, as it is when the op runs) or EMAP_PLUGIN_SRC_SEMANTIC (semantic layer `index`, read at
+ * the logical cell: the plane emap_semantic_get_layer returns) -- and carries the op's per-source flags and constants.  The table is read
+ * during the call (it travels in the kernels' arguments): the caller's array need not outlive it.  emap_plugin_chain is this call with
+ * an empty table; it refuses the four types below and names emap_plugin_chain_ex.  For the ops of emap_plugin_chain src_kind stays 0 or 1.
+ * Every op leaves, bit for bit, what the plugin's __call__ leaves in the float32 host array under NumPy 2 (NEP 50: a Python float beside a
+ * float32 array stays float32, a NumPy float64 scalar widens the operation to double):
+ *   EMAP_PLUGIN_SEMANTIC_FILTER (EM/plugins/semantic_filter.py:112-133): 0 .. 64 sources, in the order map layers, plugin layers, semantic
+ *     layers.  id = argmax over the sources (:128) as np.argmax takes it: the first NaN wins, otherwise the first maximum, -0 == +0.  The
+ *     plane is the colour of id (:132; table entry id + 1, :42-62): the bits of id + 1 dealt round-robin to r, g, b from the top bit down
+ *     (bit 3 j + ch of the index -> bit 7 - j of channel ch), entries 1 and 2 = (81, 113, 162), entry 3 = (188, 63, 59), packed 0x00RRGGBB
+ *     as the float's bits.  Computed in the kernel: no table is uploaded.  0 sources: the colour of id 0 everywhere.  No source flag.
+ *   EMAP_PLUGIN_SEMANTIC_TRAV (EM/plugins/semantic_traversability.py:70-82): 1 .. 16 sources, map layers or planes, d0 = the threshold.  A
+ *     source votes where layer >= d0, with flag EMAP_PLUGIN_SRC_AT_MOST (type "traversability") where layer <= d0 (:76, :79).  The plugin
+ *     keeps its thresholds as NumPy float64 scalars, so the comparison is (double)layer vs d0: 0.3f <= 0.3 is false.  A NaN never votes.
+ *     The plane is 1.0f where at least one source voted and 0.1f elsewhere (:81: the vote sum is a small integer, <= 0.9 means 0; the
+ *     double 0.1 is cast to float32 when the plane is stored).
+ *   EMAP_PLUGIN_MAX_LAYER (EM/plugins/max_layer_filter.py:66-108): 1 .. 16 sources of any kind.  Per source, in the plugin's order: flag
+ *     EMAP_PLUGIN_SRC_ZERO_DEFAULT: x == 0 ? f0 : x (:75; float32: f0 is float(default_value) rounded to float32; -0 counts as 0);
+ *     EMAP_PLUGIN_SRC_REVERSE: 1.0f - x (:88); EMAP_PLUGIN_SRC_SCALE: x * f1 (:90, float32); EMAP_PLUGIN_SRC_THRESHOLD: x > (float)d0 ? 1 : 0
+ *     (:92, float32 comparison; a NaN gives 0).  Then the maximum, with op flag EMAP_PLUGIN_MIN the minimum, over the sources in table
+ *     order as np.max / np.min reduce a stack along its first axis: any NaN gives NaN; among equal values the LATER source is kept (acc > x ?
+ *     acc : x), which decides the sign of a zero.  np.stack widens a mix of thresholded (int64) and other (float32) layers to float64
+ *     and the plane is cast back to float32 when stored: float32 -> float64 -> float32 changes no value, so the op stays in float32.
+ *   EMAP_PLUGIN_FEATURES_PCA (EM/plugins/features_pca.py:66-96): 3 .. 16 sources of any kind, no source flag.  In double on x clipped to
+ *     [-1, 1] (:74): per-feature means; the F x F matrix of centred second moments in a second pass; its eigenvectors by cyclic Jacobi in
+ *     one workgroup; eigenvalues sorted descending, the three leading eigenvectors kept, each signed so that its entry of largest
+ *     magnitude is positive (the first among equals: sklearn's v-based svd_flip, :80); scores (x - mean) . v; lo / hi per component
+ *     over the map (:84-85), span = hi > lo ? hi - lo : 1; level = (uint8)((score - lo) / span * 255) by truncation (:88), packed
+ *     0x00RRGGBB.  Every reduction is order-fixed (per-workgroup partials, then a fold): two runs give the same bits.  The definition is
+ *     pinned, the last ulp of an eigenvector is not: against the host's SVD a level may differ by 1 in a few cells.
+ * Refused before anything is enqueued, beyond emap_plugin_chain's cases: srcs NULL with n_srcs != 0, n_srcs outside 0 .. 2048, a run
+ * outside the table, a count outside the op's limits, a kind outside 0 .. 2 (SEMANTIC_TRAV: outside 0 .. 1), a map layer outside 0 .. 6, a
+ * semantic index >= the configured semantic layers, a plane outside the reservation, a source that is the op's own dst_plane, a source
+ * flag the op does not know, reserved != 0, i1 != 0. */
+enum { EMAP_PLUGIN_SEMANTIC_FILTER = 7, EMAP_PLUGIN_SEMANTIC_TRAV = 8, EMAP_PLUGIN_MAX_LAYER = 9, EMAP_PLUGIN_FEATURES_PCA = 10 };
+enum { EMAP_PLUGIN_SRC_SEMANTIC = 2 };
+enum { EMAP_PLUGIN_MIN = 4 };                    /* op flag of MAX_LAYER (beside EMAP_PLUGIN_REVERSE / _THRESHOLD of the other ops) */
+enum { EMAP_PLUGIN_SRC_AT_MOST = 1, EMAP_PLUGIN_SRC_ZERO_DEFAULT = 2, EMAP_PLUGIN_SRC_REVERSE = 4, EMAP_PLUGIN_SRC_SCALE = 8, EMAP_PLUGIN_SRC_THRESHOLD = 16 };
+#define EMAP_PLUGIN_MAX_SRCS 2048                /* entries of one side table: 32 ops x 64 */
+typedef struct emap_plugin_src { int32_t kind, index, flags, reserved; float f0, f1; double d0; } emap_plugin_src;
+int emap_plugin_chain_ex(emap_ctx* ctx, const emap_plugin_op* ops, int32_t n_ops, const float* rotation9, const emap_plugin_src* srcs, int32_t n_srcs);
 
 /* Inpainting plugin (EM/plugins/inpainting.py:53-61) -- DOCUMENTED SUBSTITUTE for the OpenCV Telea call it makes: fills
  * the pixels with known == 0 of a (cell_n, cell_n) image holding 8-bit values, front by front, with the distance-weighted
