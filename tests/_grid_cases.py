@@ -86,9 +86,10 @@ def semantic_frame(C, N, seed):
     return p
 
 
-def start(C, plugin_file=None, strip=None):
+def start(C, plugin_file=None, strip=None, move=True):
     """a terrain frame with visibility clean-up, several update_time calls, a semantic cloud (rgb: colour; s0 s1 c0: averages), then a
-    move that shifts both axes: the circular origin is off zero, a shift is pending, the normals lie at an older origin than the cells"""
+    move that shifts both axes: the circular origin is off zero, a shift is pending, the normals lie at an older origin than the cells
+    (move=False leaves the move out: the circular origin stays at zero, a cell's physical index is its logical one)"""
     from elevation_mapping_cupy_amd.elevation_mapping import ElevationMap
     p = make_parameter(config(), C)
     p.pointcloud_channel_fusions = {"rgb": "color", "default": "average"}
@@ -106,7 +107,8 @@ def start(C, plugin_file=None, strip=None):
         m.update_time()
     m.input_pointcloud(semantic_frame(C, 2 * N, 1), CHANNELS, R, t.copy(), 0.0, 0.0)
     m.update_time()
-    m.move_to(MOVE, np.eye(3, dtype=np.float32))
+    if move:
+        m.move_to(MOVE, np.eye(3, dtype=np.float32))
     return m
 
 

@@ -135,12 +135,12 @@ def manager(entries, cell_n, emap=None):
     return pm
 
 
-def twins(C, entries, path):
+def twins(C, entries, path, move=True):
     """two maps in the same state with the same plugins; the robot's base is tilted (the robot-centric elevation is not the elevation)"""
     path.write_text(yaml_of(entries))
     pair = []
     for _ in range(2):
-        m = gc.start(C, plugin_file=path)
+        m = gc.start(C, plugin_file=path, move=move)
         m.base_rotation = TILT.copy()
         pair.append(m)
     return pair
