@@ -89,6 +89,12 @@ class EmapPluginSrc(ct.Structure):
     _fields_ = [(n, ct.c_int32) for n in ("kind", "index", "flags", "reserved")] + [("f0", ct.c_float), ("f1", ct.c_float), ("d0", ct.c_double)]
 
 
+class EmapPolygonVerdict(ct.Structure):
+    """struct emap_polygon_verdict (include/emap_hip.h: emap_polygon_safety)."""
+    _fields_ = [("sum_valid", ct.c_double), ("sum_risk", ct.c_double), ("max_risk", ct.c_float)] + \
+               [(n, ct.c_int32) for n in ("n_inside", "n_risky", "flags", "row_begin", "n_rows", "col_begin", "n_cols")]
+
+
 GRID_ORDERS = {"rows": 0, "message": 1}             # EMAP_GRID_ROWS / EMAP_GRID_MESSAGE
 GRID_BUILTIN, GRID_SEMANTIC, GRID_NORMAL_COLOR = 0, 1, 2
 GRID_MAX_LAYERS = 32                                # EMAP_GRID_MAX_LAYERS
@@ -102,6 +108,10 @@ PLUGIN_REVERSE, PLUGIN_THRESHOLD, PLUGIN_MIN = 1, 2, 4      # EMAP_PLUGIN_REVERS
 PLUGIN_SRC_AT_MOST, PLUGIN_SRC_ZERO_DEFAULT, PLUGIN_SRC_REVERSE, PLUGIN_SRC_SCALE, PLUGIN_SRC_THRESHOLD = 1, 2, 4, 8, 16      # flags of a source
 PLUGIN_MAX_SRCS = 2048                              # EMAP_PLUGIN_MAX_SRCS
 PLUGIN_SRC_LIMITS = {7: (0, 64), 8: (1, 16), 9: (1, 16), 10: (3, 16)}      # sources an op of emap_plugin_chain_ex takes, by type
+
+POLY_MAX_BATCH, POLY_MAX_VERTS, POLY_MAX_TILES = 4096, 256, 262144      # EMAP_POLY_MAX_BATCH / _MAX_VERTS / _MAX_TILES (caps)
+POLY_MAP_LAYER, POLY_SEMANTIC, POLY_PLUGIN = 0, 1, 3      # EMAP_POLY_MAP_LAYER / _SEMANTIC / _PLUGIN: where the checker layer lies
+POLY_HAS_NAN, POLY_POISON = 1, 2                    # EMAP_POLY_HAS_NAN / EMAP_POLY_POISON (verdict flags)
 
 MODE = {"reference_fp16": 0, "fp32": 1}
 PLANES = {"elevation": 0, "variance": 1, "is_valid": 2, "traversability": 3, "time": 4, "upper_bound": 5,
@@ -117,7 +127,7 @@ SYMBOLS = [
     "emap_dilate", "emap_traversability_normals", "emap_post", "emap_post_part", "emap_update_variance", "emap_update_time", "emap_get_stats",
     "emap_get_layer", "emap_set_layer", "emap_publish_layer", "emap_publish_grid_map", "emap_publish_grid_map_ex", "emap_shift", "emap_strip_logical_begin", "emap_semantic_configure", "emap_semantic_update", "emap_frame_semantics",
     "emap_semantic_get_layer", "emap_semantic_set_layer", "emap_semantic_clear", "emap_semantic_get_alpha", "emap_semantic_set_alpha", "emap_semantic_class_max", "emap_semantic_accumulate", "emap_semantic_finalize", "emap_min_filter", "emap_max_filter", "emap_smooth_filter", "emap_erode", "emap_plugin_planes", "emap_plugin_plane_write", "emap_plugin_plane_read", "emap_plugin_chain", "emap_plugin_chain_ex", "emap_inpaint_u8", "emap_inpaint_telea_u8", "emap_inpaint_ns_u8", "emap_inpainter_create", "emap_inpainter_destroy", "emap_inpainter_set_steps", "emap_inpaint_telea_fronts_u8", "emap_image_correspondence", "emap_image_get_correspondence",
-    "emap_image_fuse", "emap_image_set_tolerance", "emap_image_fuse_arrays", "emap_input_image_message", "emap_polygon_mask", "emap_dilate_planes", "emap_halo_bytes", "emap_halo_pack", "emap_halo_unpack", "emap_normal_row_lag", "emap_normal_halo_pack", "emap_normal_halo_unpack", "emap_normal_lag_plan",
+    "emap_image_fuse", "emap_image_set_tolerance", "emap_image_fuse_arrays", "emap_input_image_message", "emap_polygon_mask", "emap_polygon_safety", "emap_dilate_planes", "emap_halo_bytes", "emap_halo_pack", "emap_halo_unpack", "emap_normal_row_lag", "emap_normal_halo_pack", "emap_normal_halo_unpack", "emap_normal_lag_plan",
     "emap_comm_unique_id", "emap_comm_init", "emap_comm_destroy", "emap_comm_selftest", "emap_comm_count", "emap_comm_wire_bytes", "emap_comm_allreduce_host", "emap_comm_gather_layer", "emap_update_sharded", "emap_set_ray_mode",
     "emap_timer_begin", "emap_timer_end", "emap_enable_stage_timing", "emap_get_stage_times", "emap_last_update_path", "emap_small_frame_aborts", "emap_post_fused_launches",
 ]
@@ -178,6 +188,9 @@ def load():
         lib.emap_plugin_chain.argtypes = [ct.c_void_p, ct.POINTER(EmapPluginOp), ct.c_int32, fp]
     if hasattr(lib, "emap_plugin_chain_ex"):
         lib.emap_plugin_chain_ex.argtypes = [ct.c_void_p, ct.POINTER(EmapPluginOp), ct.c_int32, ct.POINTER(ct.c_float), ct.POINTER(EmapPluginSrc), ct.c_int32]
+    if hasattr(lib, "emap_polygon_safety"):
+        lib.emap_polygon_safety.argtypes = [ct.c_void_p, ct.POINTER(ct.c_float), ct.POINTER(ct.c_int32), ct.c_int32, ct.c_float, ct.c_float, ct.c_int32, ct.c_int32,
+                                            ct.c_float, ct.POINTER(EmapPolygonVerdict), ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int64)]
     got = int(lib.emap_abi_version())
     if got != ABI_VERSION and not os.environ.get("EMAP_HIP_LIB"):
         raise EmapError("%s speaks ABI version %d, this binding expects %d (include/emap_hip.h: EMAP_ABI_VERSION) -- rebuild with "

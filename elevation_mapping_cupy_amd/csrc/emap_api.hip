@@ -324,6 +324,7 @@ int emap_destroy(emap_ctx* ctx) {
   hipFree(ctx->bin_recs); hipFree(ctx->bin_own); hipFree(ctx->bin_own_cnt); hipFree(ctx->bin_hist); hipFree(ctx->bin_tile_total); hipFree(ctx->bin_tile_start); hipFree(ctx->bin_sync); hipFree(ctx->split_mem); hipFree(ctx->sem_split_mem); if (ctx->split_need) hipHostFree((void*)ctx->split_need); if (ctx->sf_host) hipHostFree((void*)ctx->sf_host); hipFree(ctx->frame_save); hipFree(ctx->sf_poison);
   hipFree(ctx->img_uv); hipFree(ctx->img_valid); hipFree(ctx->img_buf);
   hipFree(ctx->grid_buf);
+  hipFree(ctx->poly_buf); if (ctx->poly_pin) hipHostFree(ctx->poly_pin);
   hipFree(ctx->plane_buf); hipFree(ctx->chain_buf); hipFree(ctx->chain_cnt); hipFree(ctx->chain_red); hipFree(ctx->chain_inp); hipFree(ctx->chain_pca);
   hipFree(ctx->sem_alpha); hipFree(ctx->sem); hipFree(ctx->sem_sums); hipFree(ctx->sem_col); hipFree(ctx->cnt_plane);
   emap_comm_destroy(ctx);

@@ -6,6 +6,25 @@
 
 using namespace emap_host;
 
+// ---- safety polygon (reference elevation_mapping.py:837-889, polygon_mask_kernel custom_kernels.py:509-651) -------------
+// get_idx of the polygon kernel (:587-603): float16 helper parameters, FLOAT resolution / width constants (unlike the map
+// kernels), index clamped through float16.
+int emap_host::polygon_cell(const emap_params& p, float x, float y, float cx, float cy, int* ix, int* iy) {
+  const bool h = p.mode == EMAP_MODE_REFERENCE_FP16;
+  auto Q = [&](float v) { return h ? q16(v) : v; };
+  auto axis = [&](float v, float c) {
+    const float q = (Q(v) - Q(c)) / (float)p.resolution;
+    const double val = (double)q + 0.5 * (double)(float)p.cell_n;
+    int i = (val != val) ? 0 : (int)fmin(fmax(val, -2147483648.0), 2147483647.0);
+    float fi = Q((float)i);
+    fi = fmaxf(fminf(fi, Q((float)(p.cell_n - 1))), Q(0.0f));
+    return (int)fi;
+  };
+  const int idx = p.cell_n * axis(x, cx) + axis(y, cy);
+  *ix = idx / p.cell_n; *iy = idx % p.cell_n;
+  return idx;
+}
+
 extern "C" {
 
 // ---- MinFilter plugin (EM/plugins/min_filter.py:84-118) on caller-provided planes ------------------------------------
@@ -123,24 +142,7 @@ int emap_inpaint_u8(emap_ctx* ctx, const float* host_image, const float* host_kn
   return EMAP_OK;
 }
 
-// ---- safety polygon (reference elevation_mapping.py:837-889, polygon_mask_kernel custom_kernels.py:509-651) -------------
-// get_idx of the polygon kernel (:587-603): float16 helper parameters, FLOAT resolution / width constants (unlike the map
-// kernels), index clamped through float16.
-static int polygon_cell(const emap_params& p, float x, float y, float cx, float cy, int* ix, int* iy) {
-  const bool h = p.mode == EMAP_MODE_REFERENCE_FP16;
-  auto Q = [&](float v) { return h ? q16(v) : v; };
-  auto axis = [&](float v, float c) {
-    const float q = (Q(v) - Q(c)) / (float)p.resolution;
-    const double val = (double)q + 0.5 * (double)(float)p.cell_n;
-    int i = (val != val) ? 0 : (int)fmin(fmax(val, -2147483648.0), 2147483647.0);
-    float fi = Q((float)i);
-    fi = fmaxf(fminf(fi, Q((float)(p.cell_n - 1))), Q(0.0f));
-    return (int)fi;
-  };
-  const int idx = p.cell_n * axis(x, cx) + axis(y, cy);
-  *ix = idx / p.cell_n; *iy = idx % p.cell_n;
-  return idx;
-}
+// ---- safety polygon: the mask alone (the statistics on the device: emap_api_polysafe.hip) ------------------------------
 int emap_polygon_mask(emap_ctx* ctx, const float* polygon_xy, int32_t n_vertices, float center_x, float center_y, float* host_mask) {
   CKARG(ctx && polygon_xy && host_mask && n_vertices >= 1 && n_vertices <= 4096, "bad polygon");
   CKARG(ctx->strip.halo_rows == 0 && ctx->strip.row_count == ctx->prm.cell_n, "emap_polygon_mask: single-strip contexts only"); SF_CHECK();

@@ -184,6 +184,10 @@ struct emap_ctx {
   float* chain_buf; size_t chain_cap; unsigned int* chain_cnt; size_t chain_cnt_cap; float* chain_red; size_t chain_red_cap;   // floats / words
   unsigned char* chain_inp; size_t chain_inp_cap;      // bytes: the byte images, fronts state and range records of the chain's inpaint ops, one set per op
   double* chain_pca; size_t chain_pca_cap;            // doubles: partial sums, means, moments, eigenvectors and score ranges of the chain's FEATURES_PCA ops, one set per op
+  // safety-polygon service on the device (emap_api_polysafe.hip): ONE device buffer -- the uploaded tables (flag word, polygons, vertex cells,
+  // work items), the part records, and the verdicts and row extremes that travel back -- and one pinned host buffer the tables are built in
+  // and the results land in; both grown on demand, no allocation per call
+  unsigned char* poly_buf; size_t poly_cap; unsigned char* poly_pin; size_t poly_pin_cap;      // bytes
   // frame state
   bool use_override; double sum_override; unsigned int cnt_override;
   bool committed;
@@ -242,6 +246,8 @@ int post_settle(emap_ctx* ctx);
 int normal_row_lag(const emap_ctx* ctx);
 int plugin_scratch(emap_ctx* ctx, size_t planes, int counters);
 bool takes_bins(const emap_ctx* ctx, long n);
+// emap_api_plugins.hip: get_idx of the reference's polygon kernel -- cell (*ix, *iy) of a world point, float16 quirk included
+int polygon_cell(const emap_params& p, float x, float y, float cx, float cy, int* ix, int* iy);
 // emap_api_semantic.hip: the frame's semantic fusion
 int frame_sem_begin(emap_ctx* ctx, bool rays_on, Frame* fr);
 int frame_sem_finish(emap_ctx* ctx, const float R[9], const float t[3], bool merged);

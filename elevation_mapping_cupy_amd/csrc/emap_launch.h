@@ -198,3 +198,23 @@ struct InpRange { float lo, hi; unsigned int known, unknown; };
 void launch_inpaint_range(hipStream_t, const KP&, Cells, InpRange* parts, InpRange* rec);
 void launch_inpaint_quantise(hipStream_t, const KP&, Cells, const InpRange* rec, unsigned char* q8, unsigned char* mask);
 void launch_inpaint_dequantise(hipStream_t, const KP&, Cells, const InpRange* rec, const unsigned char* out8, float* dst);
+
+// Safety-polygon service on the device (emap_polysafe.hip).  PolyDesc: one polygon of the batch -- its run of the vertex table (the nv
+// row indices at verts[2 vbeg], the nv column indices behind them), the bounding box in cells as the reference's kernel culls by it,
+// the box clipped to the interior (row0 / col0, nrows x ncols cells; ntr x ntc tiles of EM_POLY_TILE, enumerated row-major from
+// work item item0) and the first row of its per-row extremes (ext0, in rows).  PolyItem: one tile.  PolyPart: what one tile's workgroup
+// found inside the polygon -- rmin / rmax: per row of the tile the smallest and largest column of a risky cell (EM_POLY_EMPTY_MIN / -1:
+// none).  PolySrc: where the checker value lies -- kind 0: raw map layer `index` (0 .. 6), 1: semantic plane `index` of `base` (planes
+// of `plane` floats at the map's circular origin), 3: resident plugin plane `index` of `base` (logical order); thr: a cell is risky
+// above it.  PolyOut: struct emap_polygon_verdict (emap_hip.h; emap_api_polysafe.hip asserts the layout).
+#define EM_POLY_TILE 32
+#define EM_POLY_SWEEP_WG 256      /* workgroups of the poison sweep: a fixed number, one per CU */
+#define EM_POLY_MAX_VERTS 256
+#define EM_POLY_EMPTY_MIN 0x7fffffff
+struct PolyDesc { int vbeg, nv, bminx, bminy, bmaxx, bmaxy, item0, ntr, ntc, row0, nrows, col0, ncols, pad_; long ext0; };
+struct PolyItem { int poly, tr, tc, pad_; };
+struct PolyPart { double sum_valid, sum_risk; float max_risk; int n_inside, n_risky, has_nan; int rmin[EM_POLY_TILE], rmax[EM_POLY_TILE]; };
+struct PolySrc { int kind, index; long plane; const float* base; float thr; int pad_; };
+struct PolyOut { double sum_valid, sum_risk; float max_risk; int n_inside, n_risky, flags, row_begin, n_rows, col_begin, n_cols; };
+void launch_polysafe_tiles(hipStream_t, const KP&, Cells, const PolySrc&, const PolyDesc*, const int*, const PolyItem*, int, PolyPart*, unsigned int*);
+void launch_polysafe_fold(hipStream_t, int, const PolyDesc*, int, const PolyPart*, const unsigned int*, PolyOut*, int*);

@@ -16,8 +16,8 @@ from typing import List
 import numpy as np
 
 from . import _lib
-from ._lib import (EmapCloudMsgDesc, EmapDepthDesc, EmapError, EmapGridLayer, EmapGridLayerEx, EmapImageMsgDesc, EmapImageSpec, EmapParams, EmapStats, EmapStrip,
-                   GRID_ADD_Z, GRID_BUILTIN, GRID_FILL_NAN, GRID_MAX_LAYERS, GRID_NORMAL_COLOR, GRID_ORDERS, GRID_PLUGIN, GRID_SEMANTIC, PLANES, f32p)
+from ._lib import (EmapCloudMsgDesc, EmapDepthDesc, EmapError, EmapGridLayer, EmapGridLayerEx, EmapPolygonVerdict, EmapImageMsgDesc, EmapImageSpec, EmapParams, EmapStats, EmapStrip,
+                   GRID_ADD_Z, GRID_BUILTIN, GRID_FILL_NAN, GRID_MAX_LAYERS, GRID_NORMAL_COLOR, GRID_ORDERS, GRID_PLUGIN, GRID_SEMANTIC, PLANES, POLY_MAP_LAYER, POLY_MAX_BATCH, POLY_MAX_VERTS, POLY_PLUGIN, POLY_SEMANTIC, f32p)
 from .parameter import Parameter
 from .plugins.plugin_manager import plugin_chain_plan
 
@@ -336,6 +336,9 @@ class ElevationMap:
         self.semantic_map = None
         self.plugin_manager = None
         self._last_plugin_route = {}
+        self._mask = self._mask_polygon = None      # safety-polygon service: the mask is built when it is read
+        self.last_polygon_route = None              # "device" | "host": the route of the last safety check
+        self.untraversable_polygon = None
         from .semantic_map import SemanticMap
         self.semantic_map = SemanticMap(self.param, self)
         # plugins (reference :110-113): same YAML format; a missing file just means "no plugins"
@@ -1118,8 +1121,154 @@ class ElevationMap:
                                               ct.c_float(float(self.center[1])), f32p(mask)))
         return mask
 
+    @property
+    def mask(self):
+        """``(cell_n, cell_n)`` 0/1 mask of the last polygon a safety check clipped (the reference's ``self.mask``).  The device route
+        builds no mask: it is computed here, by ``polygon_mask``, when someone looks at it."""
+        if self._mask is None and self._mask_polygon is not None:
+            with self.map_lock:
+                self._mask = self.polygon_mask(self._mask_polygon)
+        return self._mask
+
+    @mask.setter
+    def mask(self, value):
+        self._mask, self._mask_polygon = value, None
+
+    def _clip_polygon(self, poly):
+        reach = self.map_length / 2 - self.resolution                  # the polygon is clipped to the map interior (:851-855)
+        return np.clip(poly.astype(np.float32), self.center[:2] - reach, self.center[:2] + reach).astype(np.float32)
+
+    def _polygon_checker(self, name):
+        """``(kind, index)`` of the checker layer ``name`` where it lies on the device -- a raw map layer, a semantic layer, or a plugin
+        layer that an op of the plugin chain computes into its resident plane now (``plugin_chain_plan`` / ``run_plan``, as
+        ``get_grid_map_layers``) -- or None: the host route.  The caller holds ``map_lock``."""
+        if os.environ.get("EMAP_POLYGON_RESIDENT", "1") == "0":
+            return None
+        if name in self.layer_names:
+            return POLY_MAP_LAYER, self.layer_names.index(name)
+        sem = self.semantic_map.layer_names if self.semantic_map is not None else []
+        if name in sem:
+            return POLY_SEMANTIC, sem.index(name)
+        pm = self.plugin_manager
+        if pm is not None and name in pm.layer_names:
+            steps = plugin_chain_plan([name], pm.plugins, pm.layer_names, self.layer_names, sem,
+                                      resident=os.environ.get("EMAP_PLUGIN_RESIDENT", "1") != "0")
+            if steps and steps[0][0] == "device":
+                pm.run_plan(steps, None, self.base_rotation)
+                return POLY_PLUGIN, pm.layer_names.index(name)
+        return None
+
+    def _polygons_device(self, clipped, src):
+        """one ``emap_polygon_safety`` call for the clipped polygons (at most ``POLY_MAX_BATCH``): the verdict records and, per polygon,
+        the risky cells at the ends of each row as (n, 2) indices of the border-stripped view.  The caller holds ``map_lock``."""
+        n = len(clipped)
+        begin = np.zeros(n + 1, np.int32)
+        begin[1:] = np.cumsum([c.shape[0] for c in clipped])
+        xy = np.ascontiguousarray(np.concatenate(clipped, axis=0), np.float32)
+        rows = self.cell_n - 2
+        ext_begin = np.arange(n + 1, dtype=np.int64) * rows
+        ext = np.empty((n * rows, 2), np.int32)                         # (room for every row of the map: only a polygon's own rows are written)
+        verdicts = (EmapPolygonVerdict * n)()
+        thr = np.float32(1.0 - self.param.safe_thresh)                  # what the host route's float32 plane is compared with
+        self._chk(self._lib.emap_polygon_safety(
+            self._ctx, f32p(xy), begin.ctypes.data_as(ct.POINTER(ct.c_int32)), n, ct.c_float(float(self.center[0])), ct.c_float(float(self.center[1])),
+            int(src[0]), int(src[1]), ct.c_float(float(thr)), verdicts, ext.ctypes.data_as(ct.POINTER(ct.c_int32)),
+            ext_begin.ctypes.data_as(ct.POINTER(ct.c_int64))))
+        cells = []
+        for k, v in enumerate(verdicts):
+            e = ext[k * rows:k * rows + v.n_rows]
+            q = np.nonzero(e[:, 1] >= 0)[0]
+            r = q + (v.row_begin - 1)
+            lo, hi = e[q, 0] - 1, e[q, 1] - 1
+            two = hi > lo
+            cells.append(np.concatenate([np.stack([r, lo], 1), np.stack([r[two], hi[two]], 1)]).astype(np.int64))
+        return verdicts, cells
+
+    _VERDICT = np.dtype([("is_safe", np.bool_), ("mean_risk", np.float64), ("area", np.float64), ("n_inside", np.int64), ("n_known", np.float64),
+                         ("n_risky", np.int64), ("max_risk", np.float32)])
+
+    def _polygons_on_device(self, polys, name):
+        """``(verdicts, rings)`` of ``get_polygons_traversability`` by the device route, or None when the batch has to take the host route"""
+        if not all(p.ndim == 2 and p.shape[1] == 2 and 1 <= p.shape[0] <= POLY_MAX_VERTS for p in polys):
+            return None
+        clipped = [self._clip_polygon(p) for p in polys]
+        with self.map_lock:
+            src = self._polygon_checker(name)
+            if src is None:
+                return None
+            verdicts, cells = [], []
+            for a in range(0, len(polys), POLY_MAX_BATCH):
+                v, c = self._polygons_device(clipped[a:a + POLY_MAX_BATCH], src)
+                verdicts += list(v); cells += c
+        out, rings = np.zeros(len(polys), self._VERDICT), [None] * len(polys)
+        limit = 1.0 - self.param.safe_min_thresh
+        for k, (v, c) in enumerate(zip(verdicts, cells)):
+            mean_risk = v.sum_risk / v.sum_valid if v.sum_valid > 0 else 0.0
+            safe = v.n_risky <= self.param.max_unsafe_n and float(v.max_risk) <= limit
+            if _shoelace_area(clipped[k]) < 0.001:
+                print("requested polygon is outside of the map")
+                safe = False
+            ring = _hull_ring(c)
+            if ring is not None:                                        # cell indices of the border-stripped view -> map frame
+                ring = self.center[:2].reshape(1, 2) + (ring - self.cell_n / 2.0) * self.resolution
+            rings[k] = ring
+            out[k] = (safe, mean_risk, _shoelace_area(polys[k]), v.n_inside, v.sum_valid, v.n_risky, v.max_risk)
+        self.untraversable_polygon = rings[-1]
+        self._mask, self._mask_polygon = None, clipped[-1]
+        return out, rings
+
+    def get_polygons_traversability(self, polygons, layer=None):
+        """The safety check of ``get_polygon_traversability`` for a BATCH of footprints -- a list of ``(M_i, 2)`` arrays in the map frame --
+        against ``layer`` (default: ``param.checker_layer``).  Returns ``(verdicts, rings)``: a structured array with the fields ``is_safe,
+        mean_risk, area`` (what ``result`` holds there), ``n_inside`` (cells inside), ``n_known`` (the sum of ``is_valid`` inside),
+        ``n_risky`` (cells with risk > 1 - ``safe_thresh``) and ``max_risk``; and per polygon the closed counter-clockwise hull ring around the
+        risky cells in the map frame, or ``None`` when they span no area.
+
+        Where the layer lies on the device -- a raw map layer, a semantic layer, or a plugin layer computed into a resident plane -- and no
+        polygon has more than 256 vertices, the batch is ONE call of ``emap_polygon_safety`` (groups of 4096 beyond 4096 polygons): the
+        statistics are reduced next to the cells, and a verdict record and the risky cells at the ends of each row -- all the hull needs --
+        come back; no mask is written, no plane downloaded.  Otherwise every polygon takes the host route.  ``last_polygon_route`` tells
+        which; ``EMAP_POLYGON_RESIDENT=0`` in the environment sends everything through the host route."""
+        self._require_full_map("get_polygons_traversability")
+        name = self.param.checker_layer if layer is None else layer
+        polys = [np.asarray(p, np.float64) for p in polygons]
+        if not polys:
+            return np.zeros(0, self._VERDICT), []
+        got = self._polygons_on_device(polys, name)
+        self.last_polygon_route = "host" if got is None else "device"
+        if got is not None:
+            return got
+        out, rings = np.zeros(len(polys), self._VERDICT), [None] * len(polys)
+        for k, p in enumerate(polys):                                   # the host route, one polygon at a time
+            res = np.zeros(3)
+            self._polygon_traversability_host(p, res, name)
+            out[k] = (bool(res[0]), res[1], res[2], int(self.mask[1:-1, 1:-1].sum())) + self._host_counts
+            rings[k] = self.untraversable_polygon
+        return out, rings
+
     def get_polygon_traversability(self, polygon, result):
-        """Safety check of a footprint polygon (node service; reference :837-889).  The cell mask comes from the device
+        """Safety check of a footprint polygon (node service; reference :837-889): ``result`` = (is_safe, mean untraversability of the
+        known cells inside, polygon area); the return value is the vertex count of the hull around the cells that are too untraversable
+        (``get_untraversable_polygon`` hands it out).
+
+        Where the checker layer lies on the device (``get_polygons_traversability`` says when) the call is a batch of one: the statistics
+        are reduced on the device.  ``result[0]``, ``result[2]`` and the vertex count are the host route's values exactly; ``result[1]`` is the
+        mean of a double-precision sum in a fixed order, where the host route divides a float32 pairwise sum (which lies further from
+        the exact mean); the ring has the host route's vertices in the same counter-clockwise order, but may start at another of them:
+        Qhull starts where it likes on a different point set (here the risky cells at the ends of each row, whose hull is that of all of
+        them).  Everything else -- a plugin on its host route, an unknown layer, more than 256 vertices, ``EMAP_POLYGON_RESIDENT=0`` --
+        takes the host route unchanged.  ``last_polygon_route`` tells which route the call took; ``mask`` is built when it is read."""
+        self._require_full_map("get_polygon_traversability")
+        got = self._polygons_on_device([np.asarray(polygon, np.float64)], self.param.checker_layer)
+        self.last_polygon_route = "host" if got is None else "device"
+        if got is None:
+            return self._polygon_traversability_host(polygon, result)
+        out, rings = got
+        result[...] = np.array([out["is_safe"][0], out["mean_risk"][0], out["area"][0]])
+        return 0 if rings[0] is None else int(rings[0].shape[0])
+
+    def _polygon_traversability_host(self, polygon, result, layer=None):
+        """The host route of ``get_polygon_traversability`` (reference :837-889).  The cell mask comes from the device
         (``emap_polygon_mask`` = the reference's polygon_mask_kernel, bit-exact); the statistics are a few reductions over the
         masked interior: ``result`` = (is_safe, mean untraversability of the known cells inside, polygon area); the return value is
         the vertex count of the hull around the cells that are too untraversable (``get_untraversable_polygon`` hands it out)."""
@@ -1130,7 +1279,7 @@ class ElevationMap:
         clipped = np.clip(poly.astype(np.float32), self.center[:2] - reach, self.center[:2] + reach).astype(np.float32)
         with self.map_lock:
             self.mask = self.polygon_mask(clipped)
-            layer = np.asarray(self.get_layer(self.param.checker_layer), np.float32)
+            layer = np.asarray(self.get_layer(self.param.checker_layer if layer is None else layer), np.float32)
             valid = self.get_layer_raw("is_valid")
         inner = (slice(1, -1), slice(1, -1))
         footprint, known = self.mask[inner], valid[inner]
@@ -1138,7 +1287,8 @@ class ElevationMap:
         n_known = float((known * footprint).sum())
         mean_risk = float(risk.sum()) / n_known if n_known > 0 else 0.0
         too_risky = risk > 1.0 - self.param.safe_thresh
-        safe = int(too_risky.sum()) <= self.param.max_unsafe_n and float(risk.max()) <= 1.0 - self.param.safe_min_thresh
+        n_risky, max_risk = int(too_risky.sum()), risk.max()
+        safe = n_risky <= self.param.max_unsafe_n and float(max_risk) <= 1.0 - self.param.safe_min_thresh
         if _shoelace_area(clipped) < 0.001:
             print("requested polygon is outside of the map")
             safe = False
@@ -1146,6 +1296,7 @@ class ElevationMap:
         if ring is not None:                                            # cell indices of the border-stripped view -> map frame
             ring = self.center[:2].reshape(1, 2) + (ring - self.cell_n / 2.0) * self.resolution
         self.untraversable_polygon = ring
+        self._host_counts = (n_known, n_risky, max_risk)               # (the batch door's extra fields: nothing is reduced twice)
         result[...] = np.array([safe, mean_risk, area])
         return 0 if ring is None else int(ring.shape[0])
 

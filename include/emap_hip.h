@@ -532,6 +532,49 @@ int emap_input_image_message(emap_ctx* ctx, const emap_image_msg_desc* desc, con
  * coordinates already clipped to the map (:851-855); writes the (cell_n, cell_n) 0/1 mask to host memory. */
 int emap_polygon_mask(emap_ctx* ctx, const float* polygon_xy, int32_t n_vertices, float center_x, float center_y, float* host_mask);
 
+/* ---- safety-polygon service on the device: what ElevationMap.get_polygon_traversability (EM/elevation_mapping.py:837-889)
+ * reduces from the mask of polygon_mask_kernel (EM/kernels/custom_kernels.py:509-651), the checker layer and is_valid, for a
+ * BATCH of footprints in one call: one upload, two launches, one copy back of a few hundred bytes per polygon, one wait.
+ * No mask is written and no plane is downloaded.
+ *
+ * `polygons_xy`: the vertices of all polygons one behind the other, (x, y) float32 world coordinates already clipped to the
+ * map (:851-855) as for emap_polygon_mask; polygon p holds the vertices vertex_begin[p] .. vertex_begin[p + 1] - 1
+ * (vertex_begin[0] = 0, increasing).  The checker value of a cell is read where it lies: layer_kind EMAP_POLY_MAP_LAYER = raw
+ * map layer `layer_index` 0 .. 6 (emap_get_layer), EMAP_POLY_SEMANTIC = semantic layer `layer_index`, EMAP_POLY_PLUGIN =
+ * resident plugin plane `layer_index` (emap_plugin_chain).  A cell inside a polygon has risk = is_valid > 0.5 ? 1 - value : 0
+ * in float32; it is risky when risk > risky_above (the float32 of 1 - safe_thresh).  Only the interior rows and columns
+ * 1 .. cell_n - 2 count.
+ *
+ * verdicts[p]: n_inside cells inside, sum_valid = the sum of is_valid over them and sum_risk = the sum of risk, both in
+ * double and in a fixed order (the same bytes wherever the polygon stands in a batch); n_risky; max_risk over the interior
+ * (a cell outside a polygon counts 0).  flags bit 0: a NaN risk inside; bit 1: a known cell ANYWHERE in the interior whose
+ * risk is not finite -- the reference multiplies the risk plane by the mask, so such a cell outside the polygon is
+ * inf * 0 = NaN in its sum and maximum; either bit makes sum_risk and max_risk NaN.  row_begin, n_rows, col_begin, n_cols:
+ * the polygon's bounding box in cells, clipped to the interior.
+ *
+ * row_extremes: for row q of polygon p's box (logical row row_begin + q) the smallest and the largest column of a risky cell
+ * at row_extremes[2 * (row_extremes_begin[p] + q)] and the word behind it, both -1 when the row has none -- the convex hull
+ * of the risky cells is the hull of these at most 2 n_rows cells.  row_extremes_begin[p + 1] - row_extremes_begin[p] rows
+ * are the caller's room for polygon p (cell_n - 2 always suffice); rows beyond n_rows are not written.
+ *
+ * Refused before any device is touched: null pointers, n_polygons outside 1 .. EMAP_POLY_MAX_BATCH, a polygon with fewer than
+ * 1 or more than EMAP_POLY_MAX_VERTS vertices, vertex_begin not increasing from 0, an unknown layer kind or an index outside
+ * its kind, a plugin plane that is not reserved, a strip context, too little room for a polygon's rows, and a batch of more
+ * than EMAP_POLY_MAX_TILES tiles of 32 x 32 cells.  The three limits are caps, not measurements: they bound the context's
+ * scratch (a part record of 288 bytes per tile), nothing in the kernels depends on them but the vertex stage in LDS. */
+#define EMAP_POLY_MAX_BATCH 4096
+#define EMAP_POLY_MAX_VERTS 256
+#define EMAP_POLY_MAX_TILES 262144
+#define EMAP_POLY_MAP_LAYER 0
+#define EMAP_POLY_SEMANTIC 1
+#define EMAP_POLY_PLUGIN 3
+#define EMAP_POLY_HAS_NAN 1
+#define EMAP_POLY_POISON 2
+typedef struct emap_polygon_verdict { double sum_valid, sum_risk; float max_risk; int32_t n_inside, n_risky, flags, row_begin, n_rows, col_begin, n_cols; } emap_polygon_verdict;
+int emap_polygon_safety(emap_ctx* ctx, const float* polygons_xy, const int32_t* vertex_begin /* n_polygons + 1 */, int32_t n_polygons,
+                        float center_x, float center_y, int32_t layer_kind, int32_t layer_index, float risky_above,
+                        emap_polygon_verdict* verdicts, int32_t* row_extremes, const int64_t* row_extremes_begin /* n_polygons + 1 */);
+
 /* dilation_filter_kernel (EM/kernels/custom_kernels.py:392-449) on host planes (cell_n x cell_n), `iterations` out-of-place
  * passes -- the two passes of ElevationMap.initialize_map (EM/elevation_mapping.py:914-921; in place, i.e. racy, there). */
 int emap_dilate_planes(emap_ctx* ctx, const float* host_plane, const float* host_mask, int32_t dilation_size, int32_t iterations,
