@@ -305,6 +305,15 @@ __device__ __forceinline__ float publish_value(int kind, const Cell& m, int r, i
   return v;
 }
 
+// addNormalColorLayer (elevation_mapping_wrapper.cpp:296-314) + grid_map::colorVectorToValue: x, y in -1 .. 1 -> 0 .. 255, z as it is;
+// the three integers packed as 0x00RRGGBB in an int whose bits are the float.  A component that is not finite or beyond int is undefined
+// there (a C++ cast); here the conversion saturates and NaN gives 0 (v_cvt_i32_f32).  Shared by k_grid_map and k_grid_windows.
+__device__ __forceinline__ float normal_color(float nx, float ny, float nz) {
+  const float cx = (float)(((double)nx + 1.0) / 2.0), cy = (float)(((double)ny + 1.0) / 2.0), cz = nz;
+  const unsigned int r = (unsigned int)__float2int_rz(cx * 255.0f), g = (unsigned int)__float2int_rz(cy * 255.0f), b = (unsigned int)__float2int_rz(cz * 255.0f);
+  return __uint_as_float((r << 16) | (g << 8) | b);
+}
+
 // effects of custom_kernels.py:174 and :189-192 on one cell (-> snapshot S1)
 __device__ __forceinline__ void commit_cell(const KP& P, Cell& c, const AccF& a) {
   unsigned int cnt = (unsigned int)(a.cnt_out & 0xffffffffull), n_out = (unsigned int)(a.cnt_out >> 32);

@@ -16,14 +16,7 @@
 // one barrier per layer.
 #include "emap_launch.h"
 
-// addNormalColorLayer (elevation_mapping_wrapper.cpp:296-314) + grid_map::colorVectorToValue: x, y in -1 .. 1 -> 0 .. 255, z as it is;
-// the three integers packed as 0x00RRGGBB in an int whose bits are the float.  A component that is not finite or beyond int is undefined
-// there (a C++ cast); here the conversion saturates and NaN gives 0 (v_cvt_i32_f32).
-__device__ __forceinline__ float normal_color(float nx, float ny, float nz) {
-  const float cx = (float)(((double)nx + 1.0) / 2.0), cy = (float)(((double)ny + 1.0) / 2.0), cz = nz;
-  const unsigned int r = (unsigned int)__float2int_rz(cx * 255.0f), g = (unsigned int)__float2int_rz(cy * 255.0f), b = (unsigned int)__float2int_rz(cz * 255.0f);
-  return __uint_as_float((r << 16) | (g << 8) | b);
-}
+// (the values: publish_value and normal_color, emap_device.h -- one definition with k_grid_windows, emap_submap.hip)
 
 template <int ORDER>
 __global__ __launch_bounds__(EM_BLOCK) void k_grid_map(KP P, Cells cells, GridArgs A) {

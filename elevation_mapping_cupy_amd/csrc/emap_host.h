@@ -188,6 +188,10 @@ struct emap_ctx {
   // work items), the part records, and the verdicts and row extremes that travel back -- and one pinned host buffer the tables are built in
   // and the results land in; both grown on demand, no allocation per call
   unsigned char* poly_buf; size_t poly_cap; unsigned char* poly_pin; size_t poly_pin_cap;      // bytes
+  // submap service on the device (emap_api_submap.hip): the uploaded tables (windows, work items) on the device and in the pinned buffer
+  // they are built in, and the packed planes k_grid_windows writes; all grown on demand, no allocation per call
+  unsigned char* sub_tab; size_t sub_tab_cap; unsigned char* sub_pin; size_t sub_pin_cap;      // bytes
+  float* sub_out; size_t sub_out_cap;                         // floats
   // frame state
   bool use_override; double sum_override; unsigned int cnt_override;
   bool committed;

@@ -218,3 +218,12 @@ struct PolySrc { int kind, index; long plane; const float* base; float thr; int 
 struct PolyOut { double sum_valid, sum_risk; float max_risk; int n_inside, n_risky, flags, row_begin, n_rows, col_begin, n_cols; };
 void launch_polysafe_tiles(hipStream_t, const KP&, Cells, const PolySrc&, const PolyDesc*, const int*, const PolyItem*, int, PolyPart*, unsigned int*);
 void launch_polysafe_fold(hipStream_t, int, const PolyDesc*, int, const PolyPart*, const unsigned int*, PolyOut*, int*);
+
+// Submap service on the device (emap_submap.hip): a batch of windows of the published index space from ONE launch.  GridWin: one window
+// -- element (i, j) of it is published element (i0 + i, j0 + j), i.e. logical source cell (M - (i0 + i), M - (j0 + j)) -- and the float
+// at which its planes begin in the packed output (base = n_layers * the cells of the windows before it; plane l of the layer table
+// follows at l * ni * nj: no slot indirection, GridArgs::pos is not read).  GridItem: one 32 x 32 tile of one window, a workgroup each.
+#define EM_GRID_MAX_WINDOWS 64
+struct GridWin { int i0, j0, ni, nj; long base; long pad_; };
+struct GridItem { int win, tr, tc, pad_; };
+void launch_grid_windows(hipStream_t, const KP&, Cells, const GridArgs&, const GridWin*, const GridItem*, int);

@@ -16,8 +16,8 @@ from typing import List
 import numpy as np
 
 from . import _lib
-from ._lib import (EmapCloudMsgDesc, EmapDepthDesc, EmapError, EmapGridLayer, EmapGridLayerEx, EmapPolygonVerdict, EmapImageMsgDesc, EmapImageSpec, EmapParams, EmapStats, EmapStrip,
-                   GRID_ADD_Z, GRID_BUILTIN, GRID_FILL_NAN, GRID_MAX_LAYERS, GRID_NORMAL_COLOR, GRID_ORDERS, GRID_PLUGIN, GRID_SEMANTIC, PLANES, POLY_MAP_LAYER, POLY_MAX_BATCH, POLY_MAX_VERTS, POLY_PLUGIN, POLY_SEMANTIC, f32p)
+from ._lib import (EmapCloudMsgDesc, EmapDepthDesc, EmapError, EmapGridLayer, EmapGridLayerEx, EmapGridWindow, EmapPolygonVerdict, EmapImageMsgDesc, EmapImageSpec, EmapParams, EmapStats, EmapStrip,
+                   GRID_ADD_Z, GRID_BUILTIN, GRID_FILL_NAN, GRID_MAX_LAYERS, GRID_MAX_WINDOWS, GRID_NORMAL_COLOR, GRID_ORDERS, GRID_PLUGIN, GRID_SEMANTIC, PLANES, POLY_MAP_LAYER, POLY_MAX_BATCH, POLY_MAX_VERTS, POLY_PLUGIN, POLY_SEMANTIC, f32p)
 from .parameter import Parameter
 from .plugins.plugin_manager import plugin_chain_plan
 
@@ -179,6 +179,86 @@ def grid_map_descriptor(layers, semantic_layers=(), normal_color=False, slots=No
     return table, names
 
 
+_SUBMAP_EPS = 10.0 * float(np.finfo(np.float64).eps)      # grid_map_core: 10 * numeric_limits<double>::epsilon()
+
+
+def submap_geometry(map_position_xy, map_length, resolution, M, position_xy, length_xy):
+    """The window of the published index space that a ``get_submap`` request covers (elevation_mapping_ros.cpp:507-553: ``GridMap::getSubmap``),
+    in double precision, without a context: ``None`` -- the node's ``isSuccess == false`` -- or ``(i0, j0, ni, nj, submap_position_xy,
+    submap_length_xy, index_in_submap)``.
+
+    The map is ``M x M`` cells of ``resolution`` around ``map_position_xy`` with sides ``map_length``; the request is centred at
+    ``position_xy`` with sides ``length_xy``, all in the map frame.  Indices are those of element ``(i, j)`` of what
+    ``get_map_with_name_ref`` leaves (``M = cell_n - 2``): grid_map's index space with both start indices 0, which holds for the node's map
+    because ``get_grid_map`` calls ``setGeometry`` on every tick.  The request is clipped to the map; ``index_in_submap`` is the cell of
+    the requested position inside the window.
+
+    grid_map is not available offline: this is a RESTATEMENT of grid_map_core's ``getSubmapInformation`` (``boundPositionToRange``,
+    ``getIndexFromPosition``), not pinned by a compiled reference.  The double arithmetic is fragile exactly on cell edges, as there: a
+    request whose corner falls on an edge may lose or gain a cell or come back ``None``, so callers and tests keep corners inside cells
+    (what the statement gives on edges is recorded in tests/_submap_cases.py, not asserted as grid_map's behaviour).  ``ValueError``: a
+    component that is not finite, a negative length, a window size below 1."""
+    mp = [float(v) for v in map_position_xy]
+    pos = [float(v) for v in position_xy]
+    ln = [float(v) for v in length_xy]
+    L, res, M = float(map_length), float(resolution), int(M)
+    if len(mp) != 2 or len(pos) != 2 or len(ln) != 2:
+        raise ValueError("positions and lengths have two components")
+    if not all(np.isfinite(v) for v in mp + pos + ln + [L, res]):
+        raise ValueError("submap request: a component is not finite")
+    if ln[0] < 0.0 or ln[1] < 0.0:
+        raise ValueError("submap request: a length is negative")
+    if not (L > 0.0 and res > 0.0 and M >= 1):
+        raise ValueError("the map needs a positive length, a positive resolution and at least one cell")
+
+    def bound(p):
+        out = []
+        for a in (0, 1):
+            s = p[a] - mp[a] + L / 2.0
+            eps = _SUBMAP_EPS * (abs(s) if abs(s) > 1.0 else 1.0)
+            if s <= 0.0:
+                s = eps
+            elif s >= L:
+                s = L - eps
+            out.append(s + mp[a] - L / 2.0)
+        return out
+
+    def index_of(p, length, centre, size):
+        idx = []
+        for a in (0, 1):
+            t = -(p[a] - centre[a] - length[a] / 2.0)
+            i = int(-(p[a] - length[a] / 2.0 - centre[a]) / res)      # truncating, like the C++ cast
+            if not (0.0 <= t < length[a]) or not (0 <= i < size[a]):
+                return None
+            idx.append(i)
+        return idx
+
+    top_left = index_of(bound([pos[0] + ln[0] / 2.0, pos[1] + ln[1] / 2.0]), (L, L), mp, (M, M))
+    bottom_right = index_of(bound([pos[0] - ln[0] / 2.0, pos[1] - ln[1] / 2.0]), (L, L), mp, (M, M))
+    if top_left is None or bottom_right is None:
+        return None
+    size = [bottom_right[a] - top_left[a] + 1 for a in (0, 1)]
+    if size[0] < 1 or size[1] < 1:
+        raise ValueError("submap request: window size %r is below 1" % (size,))
+    sub_len = [size[a] * res for a in (0, 1)]
+    corner = [mp[a] + L / 2.0 - res * top_left[a] for a in (0, 1)]
+    sub_pos = [corner[a] - sub_len[a] / 2.0 for a in (0, 1)]
+    inside = index_of(pos, sub_len, sub_pos, size)
+    if inside is None:
+        return None
+    return top_left[0], top_left[1], size[0], size[1], (sub_pos[0], sub_pos[1]), (sub_len[0], sub_len[1]), (inside[0], inside[1])
+
+
+def pack_windows(windows, n_layers):
+    """``(offsets, total)`` of the packed output of ``emap_publish_grid_windows``: window ``w`` = ``(i0, j0, ni, nj)`` starts at float
+    ``offsets[w] = n_layers * sum(ni * nj of the windows before it)``"""
+    offsets, total = [], 0
+    for _, _, ni, nj in windows:
+        offsets.append(total)
+        total += int(n_layers) * int(ni) * int(nj)
+    return offsets, total
+
+
 CAM_CELL_MAX = 65536      # EM_CAM_CELL_MAX (csrc/emap_launch.h): a cap, not a measurement -- 2.6 km at 4 cm cells, far beyond any map
 
 
@@ -336,6 +416,7 @@ class ElevationMap:
         self.semantic_map = None
         self.plugin_manager = None
         self._last_plugin_route = {}
+        self.last_submap_route = None               # "device" | "host": the route of the last submap call (EMAP_SUBMAP_RESIDENT)
         self._mask = self._mask_polygon = None      # safety-polygon service: the mask is built when it is read
         self.last_polygon_route = None              # "device" | "host": the route of the last safety check
         self.untraversable_polygon = None
@@ -966,58 +1047,228 @@ class ElevationMap:
         if order not in GRID_ORDERS:
             raise ValueError("order must be 'rows' or 'message'")
         self._require_full_map("get_grid_map_layers")
-        M = self.cell_n - 2
         with self.map_lock:
-            names = []
-            for n in layers:
-                if n not in names and self.exists_layer(n):
-                    names.append(n)
-            if normal_color:
-                names += [n for n in GRID_NORMAL_COLOR_LAYERS if n not in names]
-            sem = self.semantic_map.layer_names if self.semantic_map is not None else []
-            pm = self.plugin_manager
-            plug = pm.layer_names if pm is not None else []
-            plan = []                                   # (name, device entry or None)
-            for n in names:
-                if normal_color and n in GRID_NORMAL_COLOR_LAYERS:
-                    plan.append((n, (GRID_NORMAL_COLOR, 0) if n == "color" else (GRID_BUILTIN, GRID_BUILTIN_LAYERS.index(n))))
-                elif n in GRID_BUILTIN_LAYERS[:6]:
-                    plan.append((n, (GRID_BUILTIN, GRID_BUILTIN_LAYERS.index(n))))
-                elif n in sem:
-                    plan.append((n, (GRID_SEMANTIC, sem.index(n))))
-                elif n in plug:
-                    plan.append((n, None))
-                else:                                   # (is_valid: a layer of the map that get_map_with_name_ref does not publish either)
-                    print("Layer {} is not in the map".format(n))
-            names = [n for n, _ in plan]
-            if out is None:
-                out = np.empty((len(names), M, M), np.float32)
-            elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.shape == (len(names), M, M)):
-                raise ValueError("out must be a C-contiguous float32 array of shape (%d, %d, %d)" % (len(names), M, M))
-            slot_of = {n: slot for slot, (n, _) in enumerate(plan)}
+            return self._grid_map_layers_locked(layers, out, order, normal_color)
 
-            def host_step(n):                           # the plugin's host route, then _publish, the flips and the layout on the host
-                self._plugin_host_step(n)
+    def _grid_plan(self, layers, normal_color):
+        """the layer list of a publisher, filtered, ordered and extended as the wrapper's ``get_grid_map`` does: ``[(name, device entry or
+        None)]`` -- ``(kind, index)`` for a built-in, semantic or normal-colour layer, ``None`` for a plugin layer.  Shared by
+        ``get_grid_map_layers`` and ``get_submap_layers``; the caller holds ``map_lock``."""
+        names = []
+        for n in layers:
+            if n not in names and self.exists_layer(n):
+                names.append(n)
+        if normal_color:
+            names += [n for n in GRID_NORMAL_COLOR_LAYERS if n not in names]
+        sem = self.semantic_map.layer_names if self.semantic_map is not None else []
+        plug = self.plugin_manager.layer_names if self.plugin_manager is not None else []
+        plan = []                                   # (name, device entry or None)
+        for n in names:
+            if normal_color and n in GRID_NORMAL_COLOR_LAYERS:
+                plan.append((n, (GRID_NORMAL_COLOR, 0) if n == "color" else (GRID_BUILTIN, GRID_BUILTIN_LAYERS.index(n))))
+            elif n in GRID_BUILTIN_LAYERS[:6]:
+                plan.append((n, (GRID_BUILTIN, GRID_BUILTIN_LAYERS.index(n))))
+            elif n in sem:
+                plan.append((n, (GRID_SEMANTIC, sem.index(n))))
+            elif n in plug:
+                plan.append((n, None))
+            else:                                   # (is_valid: a layer of the map that get_map_with_name_ref does not publish either)
+                print("Layer {} is not in the map".format(n))
+        return plan
+
+    def _grid_plugins(self, plan, host_plane):
+        """the plugin layers of ``plan`` computed in list order, ONCE over the whole map: device-capable plugins as ops of the chain into
+        their resident planes, the others on the host -- ``host_plane(name, m)`` takes the published plane (float32, ``(M, M)``, what
+        ``get_map_with_name_ref`` leaves).  Sets ``last_plugin_route``; returns the device table ``[(kind, index, position in plan,
+        flags)]`` of everything a grid launch can write.  The caller holds ``map_lock``."""
+        sem = self.semantic_map.layer_names if self.semantic_map is not None else []
+        pm = self.plugin_manager
+        plug = pm.layer_names if pm is not None else []
+
+        def host_step(n):                           # the plugin's host route, then _publish and the flips on the host
+            self._plugin_host_step(n)
+            p = pm.get_param_with_name(n)
+            m = self._publish(np.asarray(pm.host_layer(n)), p.fill_nan, p.is_height_layer, self.get_layer_raw(2))
+            host_plane(n, np.flip(np.flip(m, 0), 1).astype(np.float32))
+
+        self._last_plugin_route = {}
+        if pm is not None and any(e is None for _, e in plan):
+            steps = plugin_chain_plan([n for n, e in plan if e is None], pm.plugins, plug, self.layer_names, sem,
+                                      resident=os.environ.get("EMAP_PLUGIN_RESIDENT", "1") != "0")
+            self._last_plugin_route = pm.run_plan(steps, host_step, self.base_rotation)
+        device = []
+        for slot, (n, e) in enumerate(plan):
+            if e is not None:
+                device.append((e[0], e[1], slot, 0))
+            elif self._last_plugin_route.get(n) == "device":
                 p = pm.get_param_with_name(n)
-                m = self._publish(np.asarray(pm.host_layer(n)), p.fill_nan, p.is_height_layer, self.get_layer_raw(2))
-                m = np.flip(np.flip(m, 0), 1).astype(np.float32)
-                out[slot_of[n]][...] = m.T if order == "message" else m
+                device.append((GRID_PLUGIN, plug.index(n), slot, (GRID_FILL_NAN if p.fill_nan else 0) | (GRID_ADD_Z if p.is_height_layer else 0)))
+        return device
 
-            self._last_plugin_route = {}
-            if pm is not None and any(e is None for _, e in plan):
-                steps = plugin_chain_plan([n for n, e in plan if e is None], pm.plugins, plug, self.layer_names, sem,
-                                          resident=os.environ.get("EMAP_PLUGIN_RESIDENT", "1") != "0")
-                self._last_plugin_route = pm.run_plan(steps, host_step, self.base_rotation)
-            device = []
-            for slot, (n, e) in enumerate(plan):
-                if e is not None:
-                    device.append((e[0], e[1], slot, 0))
-                elif self._last_plugin_route.get(n) == "device":
-                    p = pm.get_param_with_name(n)
-                    device.append((GRID_PLUGIN, plug.index(n), slot, (GRID_FILL_NAN if p.fill_nan else 0) | (GRID_ADD_Z if p.is_height_layer else 0)))
-            if device:
-                self._grid_launch(device, out, order)
+    def _grid_map_layers_locked(self, layers, out, order, normal_color):
+        M = self.cell_n - 2
+        plan = self._grid_plan(layers, normal_color)
+        names = [n for n, _ in plan]
+        if out is None:
+            out = np.empty((len(names), M, M), np.float32)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.shape == (len(names), M, M)):
+            raise ValueError("out must be a C-contiguous float32 array of shape (%d, %d, %d)" % (len(names), M, M))
+        slot_of = {n: slot for slot, (n, _) in enumerate(plan)}
+
+        def host_plane(n, m):                       # the layout on the host
+            out[slot_of[n]][...] = m.T if order == "message" else m
+
+        device = self._grid_plugins(plan, host_plane)
+        if device:
+            self._grid_launch(device, out, order)
         return names, out
+
+    # ---- submap service (include/emap_hip.h: emap_publish_grid_windows) -------------------------------------------------------------------
+    def _check_windows(self, windows):
+        M = self.cell_n - 2
+        wins = []
+        for w in windows:
+            i0, j0, ni, nj = (int(v) for v in w)
+            if ni < 1 or nj < 1 or i0 < 0 or j0 < 0 or i0 + ni > M or j0 + nj > M:
+                raise ValueError("window %r reaches outside the published map of %d x %d cells or is empty" % ((i0, j0, ni, nj), M, M))
+            wins.append((i0, j0, ni, nj))
+        return wins
+
+    def _windows_launch(self, device, wins, buf, order):
+        """``device``: ``(kind, index, flags)`` per layer (at most 32); ``buf``: flat float32 of the packed size.  ``GRID_MAX_WINDOWS`` windows
+        per call: the packed runs of consecutive windows are adjacent, so a longer batch goes in groups.  The caller holds ``map_lock``."""
+        table = (EmapGridLayerEx * len(device))()
+        for k, (g, (kind, index, flags)) in enumerate(zip(table, device)):
+            g.kind, g.index, g.slot, g.flags = kind, index, k, flags
+        offsets, total = pack_windows(wins, len(device))
+        offsets.append(total)
+        for a in range(0, len(wins), GRID_MAX_WINDOWS):
+            group = wins[a:a + GRID_MAX_WINDOWS]
+            wt = (EmapGridWindow * len(group))()
+            for g, (i0, j0, ni, nj) in zip(wt, group):
+                g.i0, g.j0, g.ni, g.nj = i0, j0, ni, nj
+            lo, hi = offsets[a], offsets[a + len(group)]
+            self._chk(self._lib.emap_publish_grid_windows(self._ctx, table, len(device), GRID_ORDERS[order], ct.c_float(float(self.center[2])),
+                                                          int(bool(self.param.use_only_above_for_upper_bound)), wt, len(group), f32p(buf[lo:hi]), hi - lo))
+
+    @staticmethod
+    def _window_views(buf, wins, n_layers, order):
+        offsets, _ = pack_windows(wins, n_layers)
+        return [buf[o:o + n_layers * ni * nj].reshape((n_layers, ni, nj) if order == "rows" else (n_layers, nj, ni))
+                for o, (_, _, ni, nj) in zip(offsets, wins)]
+
+    def _submap_layers_locked(self, wins, layers, out, order, normal_color):
+        M = self.cell_n - 2
+        resident = os.environ.get("EMAP_SUBMAP_RESIDENT", "1") != "0"
+        plan = self._grid_plan(layers, normal_color)
+        names = [n for n, _ in plan]
+        L = len(names)
+        _, total = pack_windows(wins, L)
+        if out is None:
+            out = np.empty(total, np.float32)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.ndim == 1 and out.size == total):
+            raise ValueError("out must be a C-contiguous float32 array of %d elements (the packed windows)" % total)
+        views = self._window_views(out, wins, L, order)
+        self.last_submap_route = "device" if resident else "host"
+        if not wins or not L:                       # nothing to answer: no plugin runs, nothing is launched
+            return names, views
+
+        def put(slot, full):                        # a whole published plane (rows order), sliced on the host
+            for v, (i0, j0, ni, nj) in zip(views, wins):
+                s = full[i0:i0 + ni, j0:j0 + nj]
+                v[slot][...] = s.T if order == "message" else s
+
+        if not resident:                            # A/B: the whole map through get_grid_map_layers, sliced on the host
+            _, full = self._grid_map_layers_locked(layers, None, "rows", normal_color)
+            for slot in range(L):
+                put(slot, full[slot])
+            return names, views
+        slot_of = {n: slot for slot, (n, _) in enumerate(plan)}
+        device = self._grid_plugins(plan, lambda n, m: put(slot_of[n], m))
+        if not device:
+            return names, views
+        if len(device) == L and L <= GRID_MAX_LAYERS:      # every layer from the launch: the packed result IS the output
+            self._windows_launch([(k, i, f) for k, i, _, f in device], wins, out, order)
+            return names, views
+        for a in range(0, len(device), GRID_MAX_LAYERS):   # host-route plugin layers in between, or more than 32 layers: planes are moved into place
+            group = device[a:a + GRID_MAX_LAYERS]
+            tmp = np.empty(pack_windows(wins, len(group))[1], np.float32)
+            self._windows_launch([(k, i, f) for k, i, _, f in group], wins, tmp, order)
+            for v, t in zip(views, self._window_views(tmp, wins, len(group), order)):
+                for k, (_, _, slot, _) in enumerate(group):
+                    v[slot][...] = t[k]
+        return names, views
+
+    def published_layers(self):
+        """every layer name a GridMap of this map can carry: the six cell layers, the semantic layers and the plugin layers"""
+        names = list(GRID_BUILTIN_LAYERS[:6])
+        names += [n for n in (self.semantic_map.layer_names if self.semantic_map is not None else []) if n not in names]
+        names += [n for n in (self.plugin_manager.layer_names if self.plugin_manager is not None else []) if n not in names]
+        return names
+
+    def get_submap_layers(self, windows, layers, out=None, order="rows", normal_color=False):
+        """``get_grid_map_layers`` for a batch of WINDOWS of the published map: ``(names, [array per window])``.  ``windows``: ``(i0, j0, ni,
+        nj)`` in the index space of ``get_map_with_name_ref`` (``submap_geometry`` makes them from metric requests); window ``w``'s array is
+        float32 ``(len(names), ni, nj)`` -- ``get_grid_map_layers(order="rows")[1][:, i0:i0 + ni, j0:j0 + nj]``, bit for bit -- or, with
+        ``order="message"``, ``(len(names), nj, ni)``: each plane's transpose stored C-contiguous.  All arrays are views into ONE flat
+        buffer (``out``, or a new one), packed window after window.  Names are filtered, ordered and extended as there.
+
+        One ``emap_publish_grid_windows`` call answers the batch (groups of 64 windows beyond 64): only the cells of the windows are read,
+        and only the windows travel to the host.  Plugin layers are computed as in ``get_grid_map_layers`` over the whole map -- stencils
+        need it -- ONCE per call: a device-capable plugin leaves a resident plane the window launch reads, a host-route plugin's plane is
+        sliced on the host (``last_plugin_route``).  ``EMAP_SUBMAP_RESIDENT=0`` in the environment sends the call through
+        ``get_grid_map_layers`` and host slices instead; ``last_submap_route`` tells which route ran.  One ``map_lock`` for the call."""
+        if order not in GRID_ORDERS:
+            raise ValueError("order must be 'rows' or 'message'")
+        self._require_full_map("get_submap_layers")
+        wins = self._check_windows(windows)
+        with self.map_lock:
+            return self._submap_layers_locked(wins, list(layers), out, order, normal_color)
+
+    def get_submap_messages(self, requests, layers=None, basic_layers=None, frame_id="", stamp=None, normal_color=False, out=None):
+        """The node's ``get_submap`` service (elevation_mapping_ros.cpp:507-553) for a batch of requests in the map frame: ``requests`` =
+        ``(position_xy, length_xy)`` pairs; returns a list of ``(msg, success)``.  ``msg`` is the duck-typed ``GridMap`` of
+        ``get_grid_map_message`` for the window ``submap_geometry`` gives: ``info.length_x / length_y`` = the window's sides, the pose at
+        its centre, ``dim[0] = column_index (nj, ni * nj)``, ``dim[1] = row_index (ni, ni)``, start indices 0, ``msg.index_in_submap`` = the
+        cell of the requested position; every ``data`` array of the call is a view into one buffer.  ``layers=None`` or empty: every
+        layer the map publishes (``published_layers``: the service's ``request.layers.empty()`` branch).  A request the geometry answers
+        with ``None`` -- its centre lies outside the map -- yields ``(a message without layers, False)`` and costs no device work; the
+        others are still answered.  The geometry sees what the node's grid map holds: the float32 resolution widened to double, sides of
+        ``(cell_n - 2)`` times that, the float32 centre.  A request in another frame is the caller's business (tf)."""
+        self._require_full_map("get_submap_messages")
+        layers = list(layers) if layers else self.published_layers()
+        M = self.cell_n - 2
+        res = float(np.float32(self.resolution))
+        centre = (float(self.center[0]), float(self.center[1]))
+        geo = [submap_geometry(centre, M * res, res, M, p, ln) for p, ln in requests]
+        wins = [g[:4] for g in geo if g is not None]
+        with self.map_lock:
+            names, views = self._submap_layers_locked(wins, layers, out, "message", normal_color)
+        ns = types.SimpleNamespace
+        if basic_layers is None:
+            basic_layers = ["elevation"] if "elevation" in layers else []
+        answers, views = [], iter(views)
+        for g in geo:
+            header = ns(frame_id=str(frame_id), stamp=stamp, seq=0)
+            if g is None:
+                pose = ns(position=ns(x=0.0, y=0.0, z=0.0), orientation=ns(x=0.0, y=0.0, z=0.0, w=1.0))
+                info = ns(header=header, resolution=float(self.resolution), length_x=0.0, length_y=0.0, pose=pose)
+                answers.append((ns(header=header, info=info, layers=[], basic_layers=[], data=[], outer_start_index=0, inner_start_index=0,
+                                   index_in_submap=None), False))
+                continue
+            _, _, ni, nj, sub_pos, sub_len, inside = g
+            flat = next(views).reshape(len(names), ni * nj)
+            pose = ns(position=ns(x=sub_pos[0], y=sub_pos[1], z=0.0), orientation=ns(x=0.0, y=0.0, z=0.0, w=1.0))
+            info = ns(header=header, resolution=float(self.resolution), length_x=sub_len[0], length_y=sub_len[1], pose=pose)
+            data = [ns(layout=ns(dim=[ns(label="column_index", size=nj, stride=ni * nj), ns(label="row_index", size=ni, stride=ni)], data_offset=0),
+                       data=flat[k]) for k in range(len(names))]
+            answers.append((ns(header=header, info=info, layers=list(names), basic_layers=list(basic_layers), data=data, outer_start_index=0,
+                               inner_start_index=0, index_in_submap=inside), True))
+        return answers
+
+    def get_submap_message(self, position_xy, length_xy, layers=None, **keywords):
+        """``get_submap_messages`` for one request: ``(msg, success)``"""
+        return self.get_submap_messages([(position_xy, length_xy)], layers, **keywords)[0]
 
     def get_grid_map_message(self, layers, basic_layers=None, frame_id="", stamp=None, normal_color=False, out=None):
         """A duck-typed ``grid_map_msgs/GridMap`` of ``layers`` (``types.SimpleNamespace``, no ROS import): ``info.resolution``,

@@ -263,6 +263,25 @@ enum { EMAP_GRID_FILL_NAN = 1, EMAP_GRID_ADD_Z = 2 };
 typedef struct emap_grid_layer_ex { int32_t kind, index, slot, flags; } emap_grid_layer_ex;
 int emap_publish_grid_map_ex(emap_ctx* ctx, const emap_grid_layer_ex* layers, int32_t n_layers, int32_t order,
                              float center_z, int32_t use_only_above_for_upper_bound, float* host_out, int64_t host_slots);
+/* Submap service: a batch of WINDOWS of the published map from one launch -- what the node's get_submap service
+ * (elevation_mapping_ros.cpp:507-553, grid_map_msgs/GetGridMap: GridMap::getSubmap, then toMessage) cuts out of the whole grid map on
+ * the host, here without reading, writing or copying anything of the size of the map.  Window w covers the published elements
+ * (i0 + i, j0 + j), 0 <= i < ni, 0 <= j < nj, of the index space emap_publish_grid_map_ex writes (M = cell_n - 2 a side).  Layers,
+ * kinds, flags, values, center_z, use_only_above_for_upper_bound and order are exactly those of emap_publish_grid_map_ex, bit for bit;
+ * the slot of an entry is NOT read.  host_out is packed: window w starts at float n_layers * (the sum of ni * nj over the windows
+ * before it); inside a window layer k of the table is plane k (ni * nj floats), and element (i, j) of the window lies at
+ *   order EMAP_GRID_ROWS     i * nj + j
+ *   order EMAP_GRID_MESSAGE  j * ni + i   dim[0] = {"column_index", nj, ni * nj}, dim[1] = {"row_index", ni, ni}
+ * Overlapping and repeated windows are legal.  One upload of the window table, one launch, ONE device-to-host copy, one wait; the
+ * buffers belong to the context and grow on demand.  Refused with EMAP_ERR_INVALID before anything is uploaded, launched or copied,
+ * host_out and the map untouched: everything emap_publish_grid_map_ex refuses of a layer table; a NULL windows; n_windows outside
+ * 1 .. EMAP_GRID_MAX_WINDOWS (a cap, not a measurement); a window with ni < 1, nj < 1, i0 < 0, j0 < 0, i0 + ni > M or j0 + nj > M;
+ * host_floats different from the packed total; a row-strip context. */
+#define EMAP_GRID_MAX_WINDOWS 64
+typedef struct emap_grid_window { int32_t i0, j0, ni, nj; } emap_grid_window;
+int emap_publish_grid_windows(emap_ctx* ctx, const emap_grid_layer_ex* layers, int32_t n_layers, int32_t order,
+                              float center_z, int32_t use_only_above_for_upper_bound, const emap_grid_window* windows, int32_t n_windows,
+                              float* host_out, int64_t host_floats);
 /* ElevationMap.shift_map_xy / shift_map_z (EM/elevation_mapping.py:200-226): roll by (dx rows, dy cols) with
  * padding (0; variance plane initial_variance), planes 0 and 5 += dz -- as a rotation of the map's circular origin plus a pending
  * entry that later kernels replay: no cell is moved, only the entering band of the semantic layers is cleared.  Works on strips
