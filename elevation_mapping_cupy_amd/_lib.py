@@ -84,6 +84,11 @@ class EmapGridWindow(ct.Structure):
     _fields_ = [(n, ct.c_int32) for n in ("i0", "j0", "ni", "nj")]
 
 
+class EmapCloudField(ct.Structure):
+    """struct emap_cloud_field (include/emap_hip.h: emap_publish_point_cloud)."""
+    _fields_ = [(n, ct.c_int32) for n in ("kind", "index", "flags", "cloud_flags")]
+
+
 class EmapPluginOp(ct.Structure):
     """struct emap_plugin_op (include/emap_hip.h: emap_plugin_chain)."""
     _fields_ = [(n, ct.c_int32) for n in ("type", "dst_plane", "src_kind", "src_index", "i0", "i1", "flags")] + [("f0", ct.c_float)]
@@ -106,6 +111,7 @@ GRID_MAX_LAYERS = 32                                # EMAP_GRID_MAX_LAYERS
 GRID_PLUGIN = 3                                     # EMAP_GRID_PLUGIN: a resident plugin plane (emap_publish_grid_map_ex)
 GRID_FILL_NAN, GRID_ADD_Z = 1, 2                    # EMAP_GRID_FILL_NAN / EMAP_GRID_ADD_Z
 GRID_MAX_WINDOWS = 64                               # EMAP_GRID_MAX_WINDOWS: windows per emap_publish_grid_windows call (a cap)
+CLOUD_POINT, CLOUD_TEST, CLOUD_HIDDEN, CLOUD_NORMAL_MIN, CLOUD_INDEX = 1, 2, 4, 8, 16      # EMAP_CLOUD_*: entry flags (POINT / TEST / HIDDEN), call flags
 PLUGIN_MAX_PLANES = PLUGIN_MAX_OPS = 32             # EMAP_PLUGIN_MAX_PLANES / EMAP_PLUGIN_MAX_OPS
 PLUGIN_OPS = {"min_filter": 0, "max_filter": 1, "smooth": 2, "erosion": 3, "robot_centric": 4, "inpaint_fronts": 6}      # EMAP_PLUGIN_MIN_FILTER .. (5: unassigned)
 PLUGIN_OPS_EX = {"semantic_filter": 7, "semantic_trav": 8, "max_layer": 9, "features_pca": 10}      # EMAP_PLUGIN_SEMANTIC_FILTER ..: the ops of emap_plugin_chain_ex (a run of the side table)
@@ -131,7 +137,7 @@ SYMBOLS = [
     "emap_set_drift_inputs", "emap_drift_sums_to_device", "emap_set_drift_inputs_device",
     "emap_local_drift_sums", "emap_set_scatter_mode", "emap_fuse", "emap_fuse_average", "emap_commit", "emap_rays", "emap_average", "emap_overlap_clear",
     "emap_dilate", "emap_traversability_normals", "emap_post", "emap_post_part", "emap_update_variance", "emap_update_time", "emap_get_stats",
-    "emap_get_layer", "emap_set_layer", "emap_publish_layer", "emap_publish_grid_map", "emap_publish_grid_map_ex", "emap_publish_grid_windows", "emap_shift", "emap_strip_logical_begin", "emap_semantic_configure", "emap_semantic_update", "emap_frame_semantics",
+    "emap_get_layer", "emap_set_layer", "emap_publish_layer", "emap_publish_grid_map", "emap_publish_grid_map_ex", "emap_publish_grid_windows", "emap_publish_point_cloud", "emap_shift", "emap_strip_logical_begin", "emap_semantic_configure", "emap_semantic_update", "emap_frame_semantics",
     "emap_semantic_get_layer", "emap_semantic_set_layer", "emap_semantic_clear", "emap_semantic_get_alpha", "emap_semantic_set_alpha", "emap_semantic_class_max", "emap_semantic_accumulate", "emap_semantic_finalize", "emap_min_filter", "emap_max_filter", "emap_smooth_filter", "emap_erode", "emap_plugin_planes", "emap_plugin_plane_write", "emap_plugin_plane_read", "emap_plugin_chain", "emap_plugin_chain_ex", "emap_inpaint_u8", "emap_inpaint_telea_u8", "emap_inpaint_ns_u8", "emap_inpainter_create", "emap_inpainter_destroy", "emap_inpainter_set_steps", "emap_inpaint_telea_fronts_u8", "emap_image_correspondence", "emap_image_get_correspondence",
     "emap_image_fuse", "emap_image_set_tolerance", "emap_image_fuse_arrays", "emap_input_image_message", "emap_polygon_mask", "emap_polygon_safety", "emap_dilate_planes", "emap_halo_bytes", "emap_halo_pack", "emap_halo_unpack", "emap_normal_row_lag", "emap_normal_halo_pack", "emap_normal_halo_unpack", "emap_normal_lag_plan",
     "emap_comm_unique_id", "emap_comm_init", "emap_comm_destroy", "emap_comm_selftest", "emap_comm_count", "emap_comm_wire_bytes", "emap_comm_allreduce_host", "emap_comm_gather_layer", "emap_update_sharded", "emap_set_ray_mode",
@@ -200,6 +206,10 @@ def load():
     if hasattr(lib, "emap_publish_grid_windows"):
         lib.emap_publish_grid_windows.argtypes = [ct.c_void_p, ct.POINTER(EmapGridLayerEx), ct.c_int32, ct.c_int32, ct.c_float, ct.c_int32,
                                                   ct.POINTER(EmapGridWindow), ct.c_int32, ct.POINTER(ct.c_float), ct.c_int64]
+    if hasattr(lib, "emap_publish_point_cloud"):
+        fp = ct.POINTER(ct.c_float)
+        lib.emap_publish_point_cloud.argtypes = [ct.c_void_p, ct.POINTER(EmapCloudField), ct.c_int32, ct.c_float, ct.c_int32, fp, fp, ct.c_double, ct.c_int32,
+                                                 ct.POINTER(ct.c_uint8), ct.c_int64, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int32)]
     got = int(lib.emap_abi_version())
     if got != ABI_VERSION and not os.environ.get("EMAP_HIP_LIB"):
         raise EmapError("%s speaks ABI version %d, this binding expects %d (include/emap_hip.h: EMAP_ABI_VERSION) -- rebuild with "

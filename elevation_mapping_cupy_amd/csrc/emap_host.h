@@ -192,6 +192,11 @@ struct emap_ctx {
   // they are built in, and the packed planes k_grid_windows writes; all grown on demand, no allocation per call
   unsigned char* sub_tab; size_t sub_tab_cap; unsigned char* sub_pin; size_t sub_pin_cap;      // bytes
   float* sub_out; size_t sub_out_cap;                         // floats
+  // point-cloud output on the device (emap_api_cloudout.hip): ONE device buffer -- the count word, the position tables, the mask words and
+  // their offsets --, the pinned buffer the tables are built in and the count lands in, and the records k_cloud_write packs; all grown
+  // on demand, no allocation per call
+  unsigned char* cloud_tab; size_t cloud_tab_cap; unsigned char* cloud_pin; size_t cloud_pin_cap;      // bytes
+  float* cloud_out; size_t cloud_out_cap;                     // floats
   // frame state
   bool use_override; double sum_override; unsigned int cnt_override;
   bool committed;

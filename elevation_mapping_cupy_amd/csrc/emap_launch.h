@@ -227,3 +227,23 @@ void launch_polysafe_fold(hipStream_t, int, const PolyDesc*, int, const PolyPart
 struct GridWin { int i0, j0, ni, nj; long base; long pad_; };
 struct GridItem { int win, tr, tc, pad_; };
 void launch_grid_windows(hipStream_t, const KP&, Cells, const GridArgs&, const GridWin*, const GridItem*, int);
+
+// Point-cloud output on the device (emap_cloudout.hip): the valid cells of the published map packed in grid_map's iterator order
+// (lin = j * M + i).  CloudArgs: a layer table as GridArgs carries it (kind / index / flags: emap_hip.h, EMAP_GRID_*; need: grid_need's
+// bits) -- the TESTED entries for k_cloud_count, the EMITTED ones for k_cloud_write, where field[l] is the first dword of entry l in a
+// record of n_fields dwords and cflags[l] & EM_CLOUD_POINT marks the entry that emits x, y, z.  call: EM_CLOUD_NORMAL_MIN -- a cell
+// passes only if !((nx nx + ny ny) + nz nz < sum_min) in double (sum_min: the smallest double whose square root is not below the
+// caller's bound, so the test IS the one on the norm) --, EM_CLOUD_INDEX -- the last dword of a record is lin.  nt = ceil(M / 32);
+// cap: the records the output buffer holds.  The scan takes EM_CLOUD_SCAN_TRIP mask words per trip of its one workgroup: the mask and
+// offset buffers are sized to a multiple of it.
+#define EM_CLOUD_POINT 1
+#define EM_CLOUD_NORMAL_MIN 8
+#define EM_CLOUD_INDEX 16
+#define EM_CLOUD_SCAN_BLOCK 1024
+#define EM_CLOUD_SCAN_TRIP (4 * EM_CLOUD_SCAN_BLOCK)
+struct CloudArgs { int n, need, only_above, call, nt, n_fields; float center_z; int pad_; long cap; double sum_min; long plane, sem_plane;
+                   const float* normal; const float* sem; const float* plug; int index[EM_GRID_MAX_LAYERS];
+                   unsigned char kind[EM_GRID_MAX_LAYERS], flags[EM_GRID_MAX_LAYERS], cflags[EM_GRID_MAX_LAYERS], field[EM_GRID_MAX_LAYERS]; };
+void launch_cloud_count(hipStream_t, const KP&, Cells, const CloudArgs&, unsigned int* masks);
+void launch_cloud_scan(hipStream_t, const unsigned int* masks, unsigned int* offs, long W, unsigned int* total);
+void launch_cloud_write(hipStream_t, const KP&, Cells, const CloudArgs&, const float* xs, const float* ys, const unsigned int* masks, const unsigned int* offs, float* out);

@@ -16,7 +16,7 @@ from typing import List
 import numpy as np
 
 from . import _lib
-from ._lib import (EmapCloudMsgDesc, EmapDepthDesc, EmapError, EmapGridLayer, EmapGridLayerEx, EmapGridWindow, EmapPolygonVerdict, EmapImageMsgDesc, EmapImageSpec, EmapParams, EmapStats, EmapStrip,
+from ._lib import (CLOUD_HIDDEN, CLOUD_INDEX, CLOUD_NORMAL_MIN, CLOUD_POINT, CLOUD_TEST, EmapCloudField, EmapCloudMsgDesc, EmapDepthDesc, EmapError, EmapGridLayer, EmapGridLayerEx, EmapGridWindow, EmapPolygonVerdict, EmapImageMsgDesc, EmapImageSpec, EmapParams, EmapStats, EmapStrip,
                    GRID_ADD_Z, GRID_BUILTIN, GRID_FILL_NAN, GRID_MAX_LAYERS, GRID_MAX_WINDOWS, GRID_NORMAL_COLOR, GRID_ORDERS, GRID_PLUGIN, GRID_SEMANTIC, PLANES, POLY_MAP_LAYER, POLY_MAX_BATCH, POLY_MAX_VERTS, POLY_PLUGIN, POLY_SEMANTIC, f32p)
 from .parameter import Parameter
 from .plugins.plugin_manager import plugin_chain_plan
@@ -259,6 +259,95 @@ def pack_windows(windows, n_layers):
     return offsets, total
 
 
+def grid_cell_positions(center_xy, resolution, M):
+    """``(x_of_i, y_of_j)``: the float64 positions of the rows ``i`` and the columns ``j`` of the published index space, as grid_map's
+    ``getPositionFromIndex`` gives them for a map of ``M x M`` cells of ``resolution`` around ``center_xy`` with both start indices 0:
+    ``x(i) = (p_x + (0.5 * L - 0.5 * resolution)) + resolution * (-i)``, ``L = M * resolution``, and ``y(j)`` likewise -- IEEE double, every
+    operation rounded on its own.  The conventions are those of ``submap_geometry``: a caller that speaks for a map hands in the float32
+    resolution and the float32 centre widened to double.  grid_map is not available offline: a RESTATEMENT, not pinned by a compiled
+    reference.  ``ValueError``: a component that is not finite, a resolution that is not positive, ``M < 1``."""
+    p = [float(v) for v in center_xy]
+    res, M = float(resolution), int(M)
+    if len(p) != 2:
+        raise ValueError("the centre has two components")
+    if not all(np.isfinite(v) for v in p + [res]):
+        raise ValueError("cell positions: a component is not finite")
+    if not (res > 0.0 and M >= 1):
+        raise ValueError("the map needs a positive resolution and at least one cell")
+    L = M * res
+    off = 0.5 * L - 0.5 * res
+    steps = res * (-np.arange(M, dtype=np.float64))
+    return (p[0] + off) + steps, (p[1] + off) + steps
+
+
+POINT_FIELD_FLOAT32 = 7      # sensor_msgs/PointField.FLOAT32
+
+
+def point_cloud_descriptor(layers, point_layer):
+    """``(fields, point_step)`` of the ``sensor_msgs/PointCloud2`` that ``GridMapRosConverter::toPointCloud(map, layers, point_layer, msg)``
+    builds (restated: grid_map is not available offline); needs no context.  Fields follow ``layers``: the point layer gives ``x``, ``y``,
+    ``z``, a layer named ``color`` gives ``rgb`` (the float's bits as they are), every other layer a field of its own name; all ``FLOAT32``
+    (datatype 7), ``count`` 1, offsets 4 apart; ``point_step = 4 * len(fields)``.  ``fields``: namespaces with ``name, offset, datatype, count``.
+    ``ValueError``: no layer, a layer named twice, ``point_layer`` not in ``layers`` (a decision: grid_map would emit a cloud without
+    coordinates)."""
+    names = [str(n) for n in layers]
+    if not names:
+        raise ValueError("no layer asked for")
+    if len(set(names)) != len(names):
+        raise ValueError("a layer is named twice: %s" % ", ".join(sorted(n for n in set(names) if names.count(n) > 1)))
+    if point_layer not in names:
+        raise ValueError("point_layer %r is not one of the layers %s" % (point_layer, names))
+    out = []
+    for n in names:
+        out += ["x", "y", "z"] if n == point_layer else ["rgb" if n == "color" else n]
+    fields = [types.SimpleNamespace(name=n, offset=4 * k, datatype=POINT_FIELD_FLOAT32, count=1) for k, n in enumerate(out)]
+    return fields, 4 * len(fields)
+
+
+def _cloud_compact(planes, emit, point_layer, tested, xs, ys, index=False, normals=None, normal_min=None):
+    """The host route of the point-cloud output: ``planes`` = ``{name: (M, M) float32 in message order}`` (its ``ravel()`` is the iterator's
+    order); a cell passes if every ``tested`` plane is finite there and, with ``normal_min``, ``not (norm < normal_min)`` in double on the
+    three ``normals`` planes.  Returns the ``(n, fields)`` float32 records: ``emit`` in order, ``x, y, z`` for the point layer, ``lin`` as an
+    int32 behind them with ``index``.  Values are moved, never computed: NaN bits stay."""
+    M = xs.size
+    ok = np.ones((M, M), bool)
+    for n in tested:
+        ok &= np.isfinite(planes[n])
+    if normal_min is not None:
+        nx, ny, nz = (planes[n].astype(np.float64) for n in normals)
+        with np.errstate(invalid="ignore"):
+            ok &= ~(np.sqrt((nx * nx + ny * ny) + nz * nz) < normal_min)
+    lin = np.flatnonzero(ok.ravel())
+    j, i = np.divmod(lin, M)
+    cols = []
+    for n in emit:
+        if n == point_layer:
+            cols += [xs[i], ys[j]]
+        cols.append(planes[n].ravel()[lin])
+    rec = np.empty((lin.size, len(cols) + (1 if index else 0)), np.float32)
+    for k, c in enumerate(cols):
+        rec.view(np.uint32)[:, k] = np.ascontiguousarray(c, np.float32).view(np.uint32)
+    if index:
+        rec.view(np.int32)[:, -1] = lin
+    return rec
+
+
+def normal_arrow_markers(arrows, frame_id="", stamp=None):
+    """The duck-typed ``visualization_msgs/MarkerArray`` of the node's ``normal`` publisher (elevation_mapping_ros.cpp:751-809,
+    ``vectorToArrowMarker``) for what ``ElevationMap.get_normal_arrows`` returns: per arrow ``ns "normal"``, ``id`` = the cell's linear
+    index, type ARROW (0), action ADD (0), ``points = [start, end]``, ``scale`` 0.01 three times, colour ``(0, 1, 0, 1)``, orientation
+    ``w = 1``.  Built here, off the hot path."""
+    ns = types.SimpleNamespace
+    header = ns(frame_id=str(frame_id), stamp=stamp, seq=0)
+    markers = []
+    for k, s, e in zip(arrows.ids.tolist(), arrows.starts.tolist(), arrows.ends.tolist()):
+        markers.append(ns(header=header, ns="normal", id=k, type=0, action=0,
+                          pose=ns(position=ns(x=0.0, y=0.0, z=0.0), orientation=ns(x=0.0, y=0.0, z=0.0, w=1.0)),
+                          scale=ns(x=0.01, y=0.01, z=0.01), color=ns(r=0.0, g=1.0, b=0.0, a=1.0),
+                          points=[ns(x=s[0], y=s[1], z=s[2]), ns(x=e[0], y=e[1], z=e[2])]))
+    return ns(markers=markers)
+
+
 CAM_CELL_MAX = 65536      # EM_CAM_CELL_MAX (csrc/emap_launch.h): a cap, not a measurement -- 2.6 km at 4 cm cells, far beyond any map
 
 
@@ -417,6 +506,7 @@ class ElevationMap:
         self.plugin_manager = None
         self._last_plugin_route = {}
         self.last_submap_route = None               # "device" | "host": the route of the last submap call (EMAP_SUBMAP_RESIDENT)
+        self.last_point_cloud_route = None          # "device" | "host": the route of the last point-cloud / arrow call (EMAP_CLOUD_RESIDENT)
         self._mask = self._mask_polygon = None      # safety-polygon service: the mask is built when it is read
         self.last_polygon_route = None              # "device" | "host": the route of the last safety check
         self.untraversable_polygon = None
@@ -1269,6 +1359,146 @@ class ElevationMap:
     def get_submap_message(self, position_xy, length_xy, layers=None, **keywords):
         """``get_submap_messages`` for one request: ``(msg, success)``"""
         return self.get_submap_messages([(position_xy, length_xy)], layers, **keywords)[0]
+
+    # ---- point-cloud output (include/emap_hip.h: emap_publish_point_cloud) ----------------------------------------------------------------
+    def _cell_positions(self):
+        """what the node's grid map holds: the float32 resolution widened to double, the float32 centre"""
+        return grid_cell_positions((float(self.center[0]), float(self.center[1])), float(np.float32(self.resolution)), self.cell_n - 2)
+
+    @staticmethod
+    def _cloud_buffer(out, M, point_step):
+        """``(uint8 view, capacity in points)`` of the caller's buffer, or of a new one that holds every cell (untouched pages cost nothing)"""
+        if out is None:
+            return np.empty(M * M * point_step, np.uint8), M * M
+        if not (isinstance(out, np.ndarray) and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.dtype in (np.uint8, np.float32)):
+            raise ValueError("out must be a writeable C-contiguous uint8 or float32 array")
+        buf = out.reshape(-1).view(np.uint8)
+        return buf, buf.size // point_step
+
+    def _cloud_device(self, table, n_dwords, xs, ys, call_flags, normal_min, buf, capacity):
+        """one ``emap_publish_point_cloud`` call: ``table`` = ``(kind, index, flags, cloud_flags)`` per entry; returns the number of points.
+        ``ValueError`` if ``buf`` is too small: it is left as it was.  The caller holds ``map_lock``."""
+        t = (EmapCloudField * len(table))()
+        for g, (kind, index, flags, cf) in zip(t, table):
+            g.kind, g.index, g.flags, g.cloud_flags = int(kind), int(index), int(flags), int(cf)
+        xs32, ys32 = np.ascontiguousarray(xs, np.float32), np.ascontiguousarray(ys, np.float32)
+        n, step = ct.c_int64(-1), ct.c_int32(0)
+        keep = buf if buf.size else np.empty(1, np.uint8)      # (a pointer the entry point accepts: nothing is written through it at capacity 0)
+        rc = self._lib.emap_publish_point_cloud(self._ctx, t, len(t), ct.c_float(float(self.center[2])), int(bool(self.param.use_only_above_for_upper_bound)),
+                                                f32p(xs32), f32p(ys32), ct.c_double(float(normal_min)), int(call_flags),
+                                                keep.ctypes.data_as(ct.POINTER(ct.c_uint8)), int(capacity), ct.byref(n), ct.byref(step))
+        if rc == -1 and n.value > capacity:
+            raise ValueError("out holds %d points of %d bytes, the cloud has %d" % (capacity, 4 * n_dwords, n.value))
+        self._chk(rc)
+        assert step.value == 4 * n_dwords
+        return int(n.value)
+
+    def _cloud_host_planes(self, layers, normal_color):
+        """the host route's planes: ``get_grid_map_layers(order="message")`` of ``layers`` as a dictionary.  The caller holds ``map_lock``."""
+        names, planes = self._grid_map_layers_locked(layers, None, "message", normal_color)
+        return dict(zip(names, planes))
+
+    def _any_host_plugin(self, plan):
+        pm = self.plugin_manager
+        want = [n for n, e in plan if e is None]
+        if pm is None or not want:
+            return False
+        sem = self.semantic_map.layer_names if self.semantic_map is not None else []
+        steps = plugin_chain_plan(want, pm.plugins, pm.layer_names, self.layer_names, sem, resident=os.environ.get("EMAP_PLUGIN_RESIDENT", "1") != "0")
+        return any(s[0] == "host" for s in steps)
+
+    def get_point_cloud_message(self, layers=("elevation",), point_layer="elevation", basic_layers=None, frame_id="", stamp=None, normal_color=False, out=None):
+        """The node's ``elevation_map_points`` publisher (elevation_mapping_ros.cpp:501-505: ``GridMapRosConverter::toPointCloud``) without a
+        host walk of the map: a duck-typed ``sensor_msgs/PointCloud2`` (``types.SimpleNamespace``, no ROS import) of the VALID cells of the
+        published map, in grid_map's iterator order (``lin = j * M + i``: the flat order of ``get_grid_map_layers(order="message")``).  A cell
+        is skipped if a basic layer or the point layer is not finite there.  ``fields``, ``point_step``: ``point_cloud_descriptor``; ``height``
+        1, ``width`` = the number of points, ``row_step = width * point_step``, ``is_dense`` and ``is_bigendian`` False; ``data`` is a uint8 view
+        of exactly ``row_step`` bytes into ``out`` (uint8 or float32, C-contiguous) or a new buffer.  Positions: ``grid_cell_positions`` of
+        the float32 resolution and centre, computed in double and rounded to float32; ``z`` is the point layer's float.  grid_map is
+        RESTATED here, not pinned by a compiled reference.
+
+        ``layers`` are filtered, ordered and extended as in ``get_grid_map_layers`` (``normal_color``: the normals and ``color``, whose field
+        is ``rgb``).  ``basic_layers=None``: the wrapper's rule, ``["elevation"]`` if it was asked for; a basic layer outside ``layers`` is
+        tested and not emitted; one the map does not hold is dropped like a layer.  ``ValueError``: ``point_layer`` not in the kept layers (a
+        decision: grid_map would emit a cloud without coordinates), an ``out`` that is too small (it is left untouched).
+
+        One ``emap_publish_point_cloud`` call packs the records on the device: three launches, a 4-byte copy of the count, then exactly
+        ``row_step`` bytes.  Device-capable plugin layers run in the chain and are read as resident planes; if any layer takes a plugin's
+        host route, or the table exceeds 32 entries, or ``EMAP_CLOUD_RESIDENT=0`` is in the environment, the whole call takes the host route:
+        ``get_grid_map_layers(order="message")`` and a NumPy compaction, the same bits.  ``last_point_cloud_route`` tells which ran.  One
+        ``map_lock`` for the call."""
+        self._require_full_map("get_point_cloud_message")
+        layers = list(layers)
+        if basic_layers is None:
+            basic_layers = ["elevation"] if "elevation" in layers else []
+        basic_layers = list(basic_layers)
+        M = self.cell_n - 2
+        xs, ys = self._cell_positions()
+        with self.map_lock:
+            asked = layers + [b for b in basic_layers if b not in layers]
+            plan = self._grid_plan(asked, normal_color)
+            hidden = [n for n, _ in plan if n not in layers and not (normal_color and n in GRID_NORMAL_COLOR_LAYERS)]
+            names = [n for n, _ in plan if n not in hidden]
+            if point_layer not in names:
+                raise ValueError("point_layer %r is not one of the layers %s of this map" % (point_layer, names))
+            fields, point_step = point_cloud_descriptor(names, point_layer)
+            tested = [n for n, _ in plan if n in basic_layers or n == point_layer]
+            buf, capacity = self._cloud_buffer(out, M, point_step)
+            resident = os.environ.get("EMAP_CLOUD_RESIDENT", "1") != "0" and len(plan) <= GRID_MAX_LAYERS and not self._any_host_plugin(plan)
+            self.last_point_cloud_route = "device" if resident else "host"
+            if resident:
+                device = self._grid_plugins(plan, None)      # (no host step: checked above)
+                table = [(kind, index, flags, (CLOUD_POINT if plan[slot][0] == point_layer else 0) | (CLOUD_TEST if plan[slot][0] in tested else 0)
+                          | (CLOUD_HIDDEN if plan[slot][0] in hidden else 0)) for kind, index, slot, flags in device]
+                n = self._cloud_device(table, point_step // 4, xs, ys, 0, 0.0, buf, capacity)
+            else:
+                rec = _cloud_compact(self._cloud_host_planes(asked, normal_color), names, point_layer, tested, xs.astype(np.float32), ys.astype(np.float32))
+                n = rec.shape[0]
+                if n > capacity:
+                    raise ValueError("out holds %d points of %d bytes, the cloud has %d" % (capacity, point_step, n))
+                buf[:n * point_step] = rec.reshape(-1).view(np.uint8)
+        ns = types.SimpleNamespace
+        return ns(header=ns(frame_id=str(frame_id), stamp=stamp, seq=0), height=1, width=n, fields=fields, is_bigendian=False, point_step=point_step,
+                  row_step=n * point_step, data=buf[:n * point_step], is_dense=False)
+
+    def get_point_cloud(self, layers=("elevation",), point_layer="elevation", basic_layers=None, normal_color=False, out=None):
+        """``get_point_cloud_message`` as ``(field_names, array)``: ``array`` float32 ``(n, len(field_names))``, a view into the message's
+        ``data`` (a colour field holds bit patterns)"""
+        msg = self.get_point_cloud_message(layers, point_layer, basic_layers, normal_color=normal_color, out=out)
+        names = [f.name for f in msg.fields]
+        return names, msg.data.view(np.float32).reshape(msg.width, len(names))
+
+    def get_normal_arrows(self, scale=0.1, min_norm=0.1):
+        """The node's ``normal`` publisher (elevation_mapping_ros.cpp:751-809) without a host walk: one arrow per cell, in iterator order,
+        whose elevation is finite and whose normal is not shorter than ``min_norm`` (``sqrt((nx nx + ny ny) + nz nz) < min_norm`` in double
+        skips; a NaN normal is not skipped).  Returns a namespace: ``ids (n,) int32`` -- the cell's linear index ``j * M + i``, the marker
+        id --, ``starts (n, 3) float64`` -- the double position ``(x(i), y(j), (double) z)``, not rounded to float -- and ``ends = starts +
+        normal * scale``, unfused.  ONE ``emap_publish_point_cloud`` call with the fields elevation (the point layer), ``normal_x``,
+        ``normal_y``, ``normal_z`` and the cell index; the double positions are recomputed here from the ids.  ``EMAP_CLOUD_RESIDENT=0``: the
+        host route.  ``normal_arrow_markers`` makes the ``MarkerArray``.  ``ValueError``: a ``scale`` or ``min_norm`` that is not finite."""
+        self._require_full_map("get_normal_arrows")
+        scale, min_norm = float(scale), float(min_norm)
+        if not (np.isfinite(scale) and np.isfinite(min_norm)):
+            raise ValueError("scale and min_norm must be finite")
+        M = self.cell_n - 2
+        xs, ys = self._cell_positions()
+        normals = ["normal_x", "normal_y", "normal_z"]
+        with self.map_lock:
+            resident = os.environ.get("EMAP_CLOUD_RESIDENT", "1") != "0"
+            self.last_point_cloud_route = "device" if resident else "host"
+            if resident:
+                table = [(GRID_BUILTIN, 0, 0, CLOUD_POINT)] + [(GRID_BUILTIN, GRID_BUILTIN_LAYERS.index(n), 0, 0) for n in normals]
+                buf = np.empty(M * M * 28, np.uint8)
+                n = self._cloud_device(table, 7, xs, ys, CLOUD_NORMAL_MIN | CLOUD_INDEX, min_norm, buf, M * M)
+                rec = buf[:n * 28].view(np.float32).reshape(n, 7)
+            else:
+                planes = self._cloud_host_planes(["elevation"], True)      # elevation, the normals (and their colour, not used)
+                rec = _cloud_compact(planes, ["elevation"] + normals, "elevation", ["elevation"], xs.astype(np.float32), ys.astype(np.float32),
+                                     index=True, normals=normals, normal_min=min_norm)
+        ids = rec.view(np.int32)[:, 6].copy()
+        starts = np.stack([xs[ids % M], ys[ids // M], rec[:, 2].astype(np.float64)], axis=1)
+        ends = starts + rec[:, 3:6].astype(np.float64) * scale
+        return types.SimpleNamespace(ids=ids, starts=starts, ends=ends)
 
     def get_grid_map_message(self, layers, basic_layers=None, frame_id="", stamp=None, normal_color=False, out=None):
         """A duck-typed ``grid_map_msgs/GridMap`` of ``layers`` (``types.SimpleNamespace``, no ROS import): ``info.resolution``,

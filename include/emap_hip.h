@@ -282,6 +282,32 @@ typedef struct emap_grid_window { int32_t i0, j0, ni, nj; } emap_grid_window;
 int emap_publish_grid_windows(emap_ctx* ctx, const emap_grid_layer_ex* layers, int32_t n_layers, int32_t order,
                               float center_z, int32_t use_only_above_for_upper_bound, const emap_grid_window* windows, int32_t n_windows,
                               float* host_out, int64_t host_floats);
+/* Point-cloud output: the VALID cells of the published map as the records of a sensor_msgs/PointCloud2, packed on the device in
+ * grid_map's iterator order -- what the node's elevation_map_points publisher (elevation_mapping_ros.cpp:501-505,
+ * GridMapRosConverter::toPointCloud) and its normal arrows (:751-809) walk the whole grid map for on the host.  The index space is
+ * that of emap_publish_grid_map_ex (M = cell_n - 2 a side, element (i, j) = logical source cell (M - i, M - j)); GridMapIterator runs
+ * lin = j * M + i, j outer: the flat order of an EMAP_GRID_MESSAGE plane.  Record k is the k-th cell of that order that passes; the bytes
+ * are unique for a map state (no atomic decides a position).  grid_map is restated here, not pinned by a compiled reference.
+ * fields: kind / index / flags of an entry are those of emap_grid_layer_ex, the values bit for bit.  cloud_flags: EMAP_CLOUD_POINT --
+ * exactly one entry: it emits x, y, z (x = x_of_i[i], y = y_of_j[j], z = its value) and a cell passes only if its value is finite;
+ * EMAP_CLOUD_TEST -- a cell passes only if the entry's value is finite (a basic layer); EMAP_CLOUD_HIDDEN (with TEST) -- tested, not
+ * emitted.  Every entry that is not HIDDEN emits one float32 (POINT: three), in table order, 4 bytes apart.  call_flags:
+ * EMAP_CLOUD_NORMAL_MIN -- a cell passes only if !(sqrt((nx nx + ny ny) + nz nz) < normal_min) in double on its normal (a NaN normal
+ * passes); EMAP_CLOUD_INDEX -- lin is appended to every record as a 4-byte integer.  x_of_i, y_of_j: M floats each, computed by the
+ * caller (in double, then rounded).  *point_step = 4 * the dwords of a record; *n_points = the cells that pass.
+ * One upload of the position tables, three launches (count, scan, write), a 4-byte copy of the count and a wait; then ONE copy of
+ * exactly *n_points * *point_step bytes to host_out and a second wait (none when no cell passes).  If more than capacity_points
+ * cells pass, *n_points and *point_step are set, host_out is NOT written and EMAP_ERR_INVALID is returned (a caller tells it from a
+ * refusal by *n_points > capacity_points).  The buffers belong to the context and grow on demand.
+ * Refused with EMAP_ERR_INVALID before anything is uploaded, launched or copied, host_out, *n_points, *point_step and the map
+ * untouched: a NULL pointer; n_fields outside 1 .. EMAP_GRID_MAX_LAYERS; everything emap_publish_grid_map_ex refuses of an entry; an
+ * unknown cloud or call flag; no or more than one POINT entry; HIDDEN without TEST or with POINT; a negative capacity_points; a
+ * normal_min that is not finite with NORMAL_MIN; a row-strip context. */
+enum { EMAP_CLOUD_POINT = 1, EMAP_CLOUD_TEST = 2, EMAP_CLOUD_HIDDEN = 4, EMAP_CLOUD_NORMAL_MIN = 8, EMAP_CLOUD_INDEX = 16 };
+typedef struct emap_cloud_field { int32_t kind, index, flags, cloud_flags; } emap_cloud_field;
+int emap_publish_point_cloud(emap_ctx* ctx, const emap_cloud_field* fields, int32_t n_fields, float center_z,
+                             int32_t use_only_above_for_upper_bound, const float* x_of_i, const float* y_of_j, double normal_min,
+                             int32_t call_flags, uint8_t* host_out, int64_t capacity_points, int64_t* n_points, int32_t* point_step);
 /* ElevationMap.shift_map_xy / shift_map_z (EM/elevation_mapping.py:200-226): roll by (dx rows, dy cols) with
  * padding (0; variance plane initial_variance), planes 0 and 5 += dz -- as a rotation of the map's circular origin plus a pending
  * entry that later kernels replay: no cell is moved, only the entering band of the semantic layers is cleared.  Works on strips
