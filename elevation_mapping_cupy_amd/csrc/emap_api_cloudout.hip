@@ -44,11 +44,7 @@ int emap_publish_point_cloud(emap_ctx* ctx, const emap_cloud_field* fields, int3
   int n_point = 0;
   for (int k = 0; k < n_fields; ++k) {
     const emap_cloud_field& g = fields[k];
-    CKARG(g.kind >= EMAP_GRID_BUILTIN && g.kind <= EMAP_GRID_PLUGIN, std::string(w) + "kind must be 0 (built-in), 1 (semantic), 2 (normal colour) or 3 (plugin plane)");
-    CKARG(g.kind != EMAP_GRID_BUILTIN || (g.index >= 0 && g.index <= 8), std::string(w) + "a built-in index must lie in 0 .. 8");
-    CKARG(g.kind != EMAP_GRID_SEMANTIC || (g.index >= 0 && g.index < ctx->sem_layers), std::string(w) + "semantic layer is not configured");
-    CKARG(g.kind != EMAP_GRID_PLUGIN || (g.index >= 0 && g.index < ctx->plane_n), std::string(w) + "plugin plane is not reserved (emap_plugin_planes)");
-    CKARG(g.kind == EMAP_GRID_PLUGIN ? (g.flags & ~(EMAP_GRID_FILL_NAN | EMAP_GRID_ADD_Z)) == 0 : g.flags == 0, std::string(w) + "flags: FILL_NAN / ADD_Z, on a plugin plane only");
+    { const int rc = check_layer_entry(ctx, w, g.kind, g.index, g.flags, true); if (rc) return rc; }
     CKARG((g.cloud_flags & ~(EMAP_CLOUD_POINT | EMAP_CLOUD_TEST | EMAP_CLOUD_HIDDEN)) == 0, std::string(w) + "cloud_flags: POINT / TEST / HIDDEN");
     CKARG(!(g.cloud_flags & EMAP_CLOUD_HIDDEN) || (g.cloud_flags & EMAP_CLOUD_TEST), std::string(w) + "a HIDDEN entry must be a TEST entry");
     CKARG(!(g.cloud_flags & EMAP_CLOUD_HIDDEN) || !(g.cloud_flags & EMAP_CLOUD_POINT), std::string(w) + "the POINT entry cannot be HIDDEN");
@@ -59,29 +55,22 @@ int emap_publish_point_cloud(emap_ctx* ctx, const emap_cloud_field* fields, int3
   // the two tables: what the count kernel tests, what the write kernel emits
   const int M = ctx->prm.cell_n - 2, NT = (M + EM_GRID_TILE - 1) / EM_GRID_TILE;
   CloudArgs Tst, Emt; memset(&Tst, 0, sizeof Tst);
-  Tst.only_above = use_only_above_for_upper_bound ? 1 : 0; Tst.center_z = center_z; Tst.call = call_flags; Tst.nt = NT;
-  Tst.plane = ctx->ncells_alloc; Tst.sem_plane = ctx->ncells_alloc; Tst.normal = ctx->normal; Tst.sem = ctx->sem; Tst.plug = ctx->plane_buf;
+  Tst.tab = tab_init(ctx, center_z, use_only_above_for_upper_bound); Tst.call = call_flags; Tst.nt = NT;
   Tst.sum_min = (call_flags & EMAP_CLOUD_NORMAL_MIN) ? sum_min(normal_min) : 0.0;
   Emt = Tst;
-  bool fill_t = false, fill_e = false;
   int n_dwords = 0;
   for (int k = 0; k < n_fields; ++k) {
     const emap_cloud_field& g = fields[k];
-    const int index = g.kind == EMAP_GRID_NORMAL_COLOR ? 0 : g.index;
-    auto put = [&](CloudArgs& A, bool& fill) {
-      const int l = A.n++;
-      A.kind[l] = (unsigned char)g.kind; A.index[l] = index; A.flags[l] = (unsigned char)g.flags; A.cflags[l] = (unsigned char)g.cloud_flags;
-      A.field[l] = (unsigned char)n_dwords;
-      A.need |= grid_need(g.kind, g.index);
-      fill = fill || (g.flags & EMAP_GRID_FILL_NAN);
+    auto put = [&](CloudArgs& A) {
+      const int l = tab_put(A.tab, g.kind, g.index, g.flags);
+      A.cflags[l] = (unsigned char)g.cloud_flags; A.field[l] = (unsigned char)n_dwords;
     };
-    if (g.cloud_flags & (EMAP_CLOUD_POINT | EMAP_CLOUD_TEST)) put(Tst, fill_t);
-    if (!(g.cloud_flags & EMAP_CLOUD_HIDDEN)) { put(Emt, fill_e); n_dwords += (g.cloud_flags & EMAP_CLOUD_POINT) ? 3 : 1; }
+    if (g.cloud_flags & (EMAP_CLOUD_POINT | EMAP_CLOUD_TEST)) put(Tst);
+    if (!(g.cloud_flags & EMAP_CLOUD_HIDDEN)) { put(Emt); n_dwords += (g.cloud_flags & EMAP_CLOUD_POINT) ? 3 : 1; }
   }
   if (call_flags & EMAP_CLOUD_INDEX) n_dwords += 1;
-  if (call_flags & EMAP_CLOUD_NORMAL_MIN) Tst.need |= 4 | 8 | 16;
-  if (fill_t && !(Tst.need & 3)) Tst.need |= 1;      // FILL_NAN reads is_valid: the hot half, unless the cold half (w mirrors it) is loaded anyway
-  if (fill_e && !(Emt.need & 3)) Emt.need |= 1;
+  if (call_flags & EMAP_CLOUD_NORMAL_MIN) Tst.tab.need |= 4 | 8 | 16;
+  tab_finish(Tst.tab); tab_finish(Emt.tab);
   const long cells = (long)M * M;
   const long cap = capacity_points < cells ? (long)capacity_points : cells;      // records the device buffer holds: never more than cells pass
   Tst.n_fields = Emt.n_fields = n_dwords; Tst.cap = Emt.cap = cap;

@@ -26,12 +26,7 @@ static int grid_publish(emap_ctx* ctx, const emap_grid_layer_ex* layers, int32_t
   int by_slot[EMAP_GRID_MAX_LAYERS];
   for (int k = 0; k < n_layers; ++k) {
     const emap_grid_layer_ex& g = layers[k];
-    if (plugin_ok) CKARG(g.kind >= EMAP_GRID_BUILTIN && g.kind <= EMAP_GRID_PLUGIN, w + "kind must be 0 (built-in), 1 (semantic), 2 (normal colour) or 3 (plugin plane)");
-    else CKARG(g.kind >= EMAP_GRID_BUILTIN && g.kind <= EMAP_GRID_NORMAL_COLOR, w + "kind must be 0 (built-in), 1 (semantic) or 2 (normal colour)");
-    CKARG(g.kind != EMAP_GRID_BUILTIN || (g.index >= 0 && g.index <= 8), w + "a built-in index must lie in 0 .. 8");
-    CKARG(g.kind != EMAP_GRID_SEMANTIC || (g.index >= 0 && g.index < ctx->sem_layers), w + "semantic layer is not configured");
-    CKARG(g.kind != EMAP_GRID_PLUGIN || (g.index >= 0 && g.index < ctx->plane_n), w + "plugin plane is not reserved (emap_plugin_planes)");
-    CKARG(g.kind == EMAP_GRID_PLUGIN ? (g.flags & ~(EMAP_GRID_FILL_NAN | EMAP_GRID_ADD_Z)) == 0 : g.flags == 0, w + "flags: FILL_NAN / ADD_Z, on a plugin plane only");
+    { const int rc = check_layer_entry(ctx, w, g.kind, g.index, g.flags, plugin_ok); if (rc) return rc; }
     CKARG(g.slot >= 0 && (int64_t)g.slot < host_slots, w + "slot outside [0, host_slots)");
     by_slot[k] = k;
   }
@@ -46,17 +41,10 @@ static int grid_publish(emap_ctx* ctx, const emap_grid_layer_ex* layers, int32_t
   const size_t MM = (size_t)(ctx->prm.cell_n - 2) * (ctx->prm.cell_n - 2);
   { const int rc = grow(ctx, &ctx->grid_buf, &ctx->grid_cap, (size_t)n_layers * MM); if (rc) return rc; }
   GridArgs A; memset(&A, 0, sizeof A);
-  A.n = n_layers; A.order = order; A.only_above = use_only_above_for_upper_bound ? 1 : 0; A.center_z = center_z;
-  A.plane = ctx->ncells_alloc; A.sem_plane = ctx->ncells_alloc; A.normal = ctx->normal; A.sem = ctx->sem; A.out = ctx->grid_buf; A.plug = ctx->plane_buf;
-  bool fill_nan = false;
-  for (int p = 0; p < n_layers; ++p) {
-    const int k = by_slot[p];
-    A.kind[k] = (unsigned char)layers[k].kind; A.index[k] = layers[k].kind == EMAP_GRID_NORMAL_COLOR ? 0 : layers[k].index; A.pos[k] = (unsigned char)p;
-    A.flags[k] = (unsigned char)layers[k].flags;
-    A.need |= grid_need(layers[k].kind, layers[k].index);
-    fill_nan = fill_nan || (layers[k].flags & EMAP_GRID_FILL_NAN);
-  }
-  if (fill_nan && !(A.need & 3)) A.need |= 1;      // FILL_NAN reads is_valid: the hot half, unless the cold half (w mirrors it) is loaded anyway
+  A.tab = tab_init(ctx, center_z, use_only_above_for_upper_bound); A.order = order; A.out = ctx->grid_buf;
+  for (int k = 0; k < n_layers; ++k) tab_put(A.tab, layers[k].kind, layers[k].index, layers[k].flags);
+  tab_finish(A.tab);
+  for (int p = 0; p < n_layers; ++p) A.pos[by_slot[p]] = (unsigned char)p;      // the planes packed in ascending slot order
   launch_grid_map(ctx->stream, ctx->kp, ctx->cells, A);
   CK(hipGetLastError());
   for (int p = 0; p < n_layers;) {             // one copy per maximal run of adjacent slots

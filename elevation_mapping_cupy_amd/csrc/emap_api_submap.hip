@@ -27,11 +27,7 @@ int emap_publish_grid_windows(emap_ctx* ctx, const emap_grid_layer_ex* layers, i
   CKARG(ctx->strip.halo_rows == 0 && ctx->strip.row_count == ctx->prm.cell_n, std::string(w) + "single-strip contexts only");
   for (int k = 0; k < n_layers; ++k) {      // (the slot of an entry is not read: layer k is plane k of every window)
     const emap_grid_layer_ex& g = layers[k];
-    CKARG(g.kind >= EMAP_GRID_BUILTIN && g.kind <= EMAP_GRID_PLUGIN, std::string(w) + "kind must be 0 (built-in), 1 (semantic), 2 (normal colour) or 3 (plugin plane)");
-    CKARG(g.kind != EMAP_GRID_BUILTIN || (g.index >= 0 && g.index <= 8), std::string(w) + "a built-in index must lie in 0 .. 8");
-    CKARG(g.kind != EMAP_GRID_SEMANTIC || (g.index >= 0 && g.index < ctx->sem_layers), std::string(w) + "semantic layer is not configured");
-    CKARG(g.kind != EMAP_GRID_PLUGIN || (g.index >= 0 && g.index < ctx->plane_n), std::string(w) + "plugin plane is not reserved (emap_plugin_planes)");
-    CKARG(g.kind == EMAP_GRID_PLUGIN ? (g.flags & ~(EMAP_GRID_FILL_NAN | EMAP_GRID_ADD_Z)) == 0 : g.flags == 0, std::string(w) + "flags: FILL_NAN / ADD_Z, on a plugin plane only");
+    { const int rc = check_layer_entry(ctx, w, g.kind, g.index, g.flags, true); if (rc) return rc; }
   }
   const int M = ctx->prm.cell_n - 2, T = EM_GRID_TILE;
   int64_t cells_total = 0, n_items = 0;
@@ -65,16 +61,9 @@ int emap_publish_grid_windows(emap_ctx* ctx, const emap_grid_layer_ex* layers, i
   }
   CK(hipMemcpyAsync(ctx->sub_tab, ctx->sub_pin, up_bytes, hipMemcpyHostToDevice, ctx->stream));
   GridArgs A; memset(&A, 0, sizeof A);
-  A.n = n_layers; A.order = order; A.only_above = use_only_above_for_upper_bound ? 1 : 0; A.center_z = center_z;
-  A.plane = ctx->ncells_alloc; A.sem_plane = ctx->ncells_alloc; A.normal = ctx->normal; A.sem = ctx->sem; A.out = ctx->sub_out; A.plug = ctx->plane_buf;
-  bool fill_nan = false;
-  for (int k = 0; k < n_layers; ++k) {
-    A.kind[k] = (unsigned char)layers[k].kind; A.index[k] = layers[k].kind == EMAP_GRID_NORMAL_COLOR ? 0 : layers[k].index; A.pos[k] = (unsigned char)k;
-    A.flags[k] = (unsigned char)layers[k].flags;
-    A.need |= grid_need(layers[k].kind, layers[k].index);
-    fill_nan = fill_nan || (layers[k].flags & EMAP_GRID_FILL_NAN);
-  }
-  if (fill_nan && !(A.need & 3)) A.need |= 1;      // FILL_NAN reads is_valid: the hot half, unless the cold half (w mirrors it) is loaded anyway
+  A.tab = tab_init(ctx, center_z, use_only_above_for_upper_bound); A.order = order; A.out = ctx->sub_out;
+  for (int k = 0; k < n_layers; ++k) A.pos[k] = (unsigned char)tab_put(A.tab, layers[k].kind, layers[k].index, layers[k].flags);      // layer k is plane k of every window
+  tab_finish(A.tab);
   launch_grid_windows(ctx->stream, ctx->kp, ctx->cells, A, reinterpret_cast<const GridWin*>(ctx->sub_tab), reinterpret_cast<const GridItem*>(ctx->sub_tab + o_item), (int)n_items);
   CK(hipGetLastError());
   CK(hipMemcpyAsync(host_out, ctx->sub_out, sizeof(float) * (size_t)host_floats, hipMemcpyDeviceToHost, ctx->stream));

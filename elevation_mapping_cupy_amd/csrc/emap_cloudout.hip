@@ -6,7 +6,7 @@
 // no atomic decides a position, so the bytes are unique for a map state.  Three launches:
 //
 //   k_cloud_count  one workgroup of 256 threads per 32 x 32 tile (tr: 32 rows i, tc: 32 columns j); thread (x, y) = (tid % 32, tid / 32)
-//                  holds the cells (32 tr + y + 8 k, 32 tc + x), k = 0 .. 3: lanes run along j, as the loads of k_grid_windows.  Only the
+//                  holds the cells (32 tr + y + 8 k, 32 tc + x), k = 0 .. 3: lanes run along j (tile_load, emap_publish_tile.h).  Only the
 //                  halves and planes the TESTED entries need are loaded.  A wave's ballot holds two rows of 32 column bits; the 32 row
 //                  words go through LDS and 32 threads regroup them into one word per column: bit b of masks[j * NT + tr] = cell
 //                  (32 tr + b, j) passes.  In memory order (j major, tr minor) the words ARE the iteration order.
@@ -14,103 +14,18 @@
 //                  words per trip (a uint4 per thread, wave shuffles, 16 wave totals through LDS), the carry in a register; the total
 //                  goes to a device word.  Integer sums: the order of summation is free, the result is not.
 //   k_cloud_write  one workgroup per tile.  It reads its 32 mask and offset words first and leaves if no cell of the tile passes.  Then
-//                  every half and plane the EMITTED entries need is loaded once, the table is walked as k_grid_windows walks it, each
-//                  layer goes through the padded 32 x 33 LDS tile so that lanes run along i, and the lane of bit b stores its value at
+//                  every half and plane the EMITTED entries need is loaded once, the table is walked (tile_value), each layer goes
+//                  through the padded 32 x 33 LDS tile (tile_transpose) so that lanes run along i, and the lane of bit b stores its value at
 //                  record rank = offs[j * NT + tr] + popcount(mask & ((1 << b) - 1)), field `field[l]`: the valid cells of a column
 //                  segment are consecutive records.  A rank at or beyond `cap` (the records the output buffer holds) is not stored.
 //
-// A lane outside the map loads nothing, stores nothing and reaches every barrier.  The values are publish_value / normal_color
-// (emap_device.h): the same definitions as k_grid_map, and ONE walk of the table (cloud_value) for the count and the write kernel.
+// A lane outside the map loads nothing, stores nothing and reaches every barrier.  The loads and the walk of the table are those of
+// k_grid_map / k_grid_windows over the window (0, 0, M, M): one definition (emap_publish_tile.h) for every door and for both kernels here.
 #include "emap_launch.h"
 
+using namespace publish_tile;
+
 namespace {
-constexpr int T = EM_GRID_TILE, NK = T * T / EM_BLOCK;      // 4 cells per thread
-
-// the four cells of a thread, lanes along j: addresses, and every half and plane `need` names (grid_need's bits)
-// (separate arrays, not one struct: each stays in registers)
-#define CLOUD_CELLS long ci[NK], ni[NK]; bool in[NK]; int rr[NK]; int c; float4 hot[NK], cold[NK]; float nx[NK], ny[NK], nz[NK]
-#define CLOUD_CELLS_PARAMS long (&ci)[NK], long (&ni)[NK], bool (&in)[NK], int (&rr)[NK], int& c, float4 (&hot)[NK], float4 (&cold)[NK], float (&nx)[NK], float (&ny)[NK], float (&nz)[NK]
-#define CLOUD_CELLS_CONST const long (&ci)[NK], const long (&ni)[NK], const bool (&in)[NK], const int (&rr)[NK], const int& c, const float4 (&hot)[NK], const float4 (&cold)[NK], const float (&nx)[NK], const float (&ny)[NK], const float (&nz)[NK]
-#define CLOUD_CELLS_ARGS ci, ni, in, rr, c, hot, cold, nx, ny, nz
-
-__device__ __forceinline__ void cloud_load(const KP& P, const Cells& cells, const CloudArgs& A, int tr, int tc, CLOUD_CELLS_PARAMS) {
-  const int C = P.C, M = C - 2;
-  const int x = threadIdx.x & (T - 1), y = threadIdx.x / T;
-  const int j = tc * T + x;
-  const bool jin = j < M;
-  c = jin ? M - j : 1;                                       // logical source column in [1, M]
-  const int pcol = phys_col(P, c), ncol = wrap_up(c + P.norg_c, C);
-#pragma unroll
-  for (int k = 0; k < NK; ++k) {
-    const int i = tr * T + y + (T / NK) * k;
-    in[k] = jin && i < M;
-    const int r = in[k] ? M - i : 1;                         // logical source row in [1, M]
-    rr[k] = r;
-    ci[k] = (long)(phys_row(P, r) + P.halo) * C + pcol;     // cells and semantic planes: the map's origin
-    ni[k] = (long)wrap_up(r + P.norg_r, C) * C + ncol;      // normal planes: the origin they were written with
-    hot[k] = make_float4(0.f, 0.f, 0.f, 0.f); cold[k] = hot[k];
-    nx[k] = ny[k] = nz[k] = 0.f;
-  }
-  if (A.need & 1) {
-#pragma unroll
-    for (int k = 0; k < NK; ++k) if (in[k]) hot[k] = cells.hot[ci[k]];
-  }
-  if (A.need & 2) {
-#pragma unroll
-    for (int k = 0; k < NK; ++k) if (in[k]) cold[k] = cells.cold[ci[k]];
-  }
-  if (A.need & 4) {
-#pragma unroll
-    for (int k = 0; k < NK; ++k) if (in[k]) nx[k] = A.normal[ni[k]];
-  }
-  if (A.need & 8) {
-#pragma unroll
-    for (int k = 0; k < NK; ++k) if (in[k]) ny[k] = A.normal[A.plane + ni[k]];
-  }
-  if (A.need & 16) {
-#pragma unroll
-    for (int k = 0; k < NK; ++k) if (in[k]) nz[k] = A.normal[2 * A.plane + ni[k]];
-  }
-}
-
-// entry l of the table at the thread's four cells: the layer walk of k_grid_windows
-__device__ __forceinline__ void cloud_value(const CloudArgs& A, int l, CLOUD_CELLS_CONST, int C, float (&v)[NK]) {
-  const int kind = A.kind[l], index = A.index[l];              // uniform
-  const bool have_hot = A.need & 1;
-  if (kind == 1) {
-    const float* __restrict__ sp = A.sem + (long)index * A.sem_plane;
-#pragma unroll
-    for (int k = 0; k < NK; ++k) v[k] = in[k] ? sp[ci[k]] : 0.f;
-  } else if (kind == 2) {
-#pragma unroll
-    for (int k = 0; k < NK; ++k) v[k] = normal_color(nx[k], ny[k], nz[k]);
-  } else if (kind == 3) {                                      // resident plugin plane, then _publish's order: FILL_NAN, ADD_Z
-    const float* __restrict__ pp = A.plug + (long)index * C * C;
-    const int fl = A.flags[l];
-#pragma unroll
-    for (int k = 0; k < NK; ++k) v[k] = in[k] ? pp[(long)rr[k] * C + c] : 0.f;      // the LOGICAL cell (no circular origin)
-    if (fl & EM_GRID_FILL_NAN) {
-#pragma unroll
-      for (int k = 0; k < NK; ++k) if (!((have_hot ? hot[k].z : cold[k].w) > 0.5f)) v[k] = __uint_as_float(0x7fc00000u);
-    }
-    if (fl & EM_GRID_ADD_Z) {
-#pragma unroll
-      for (int k = 0; k < NK; ++k) v[k] = v[k] + A.center_z;
-    }
-  } else if (index >= 6) {
-#pragma unroll
-    for (int k = 0; k < NK; ++k) v[k] = index == 6 ? nx[k] : (index == 7 ? ny[k] : nz[k]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {
-      Cell m;
-      m.h = hot[k].x; m.v = hot[k].y; m.valid = have_hot ? hot[k].z : cold[k].w; m.trav = hot[k].w;      // cold.w mirrors valid
-      m.time = cold[k].x; m.upper = cold[k].y; m.is_upper = cold[k].z; m.pad = 0.f;
-      v[k] = publish_value(index, m, rr[k], c, C, A.center_z, A.only_above);
-    }
-  }
-}
-
 __device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 }  // namespace
 
@@ -119,21 +34,21 @@ __global__ __launch_bounds__(EM_BLOCK) void k_cloud_count(KP P, Cells cells, Clo
   __shared__ unsigned int rowbits[T];
   const int C = P.C, M = C - 2, NT = A.nt;
   const int tc = blockIdx.x / NT, tr = blockIdx.x - tc * NT;   // tiles in mask order: column tile major
-  CLOUD_CELLS;
-  cloud_load(P, cells, A, tr, tc, CLOUD_CELLS_ARGS);
+  TileCells q;
+  tile_load(P, cells, A.tab, 0, 0, M, M, tr, tc, q);
   bool ok[NK];
 #pragma unroll
-  for (int k = 0; k < NK; ++k) ok[k] = in[k];
-  for (int l = 0; l < A.n; ++l) {
+  for (int k = 0; k < NK; ++k) ok[k] = q.in[k];
+  for (int l = 0; l < A.tab.n; ++l) {
     float v[NK];
-    cloud_value(A, l, CLOUD_CELLS_ARGS, C, v);
+    tile_value(A.tab, l, q, C, v);
 #pragma unroll
     for (int k = 0; k < NK; ++k) ok[k] = ok[k] && finite_bits(v[k]);
   }
   if (A.call & EM_CLOUD_NORMAL_MIN) {                          // !(sqrt((x x + y y) + z z) < normal_min) in double; the host turned the bound into one on the sum (sum_min)
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
-      const double dx = nx[k], dy = ny[k], dz = nz[k];
+      const double dx = q.nrm[0][k], dy = q.nrm[1][k], dz = q.nrm[2][k];
       const double s = (dx * dx + dy * dy) + dz * dz;          // squares of floats are exact in double; -ffp-contract=off: no fused step
       ok[k] = ok[k] && !(s < A.sum_min);                       // a NaN normal is not skipped
     }
@@ -206,29 +121,22 @@ __global__ __launch_bounds__(EM_BLOCK) void k_cloud_write(KP P, Cells cells, Clo
   }
   if (!__syncthreads_or(any)) return;                           // uniform: no record of this tile is stored, nothing of it is loaded
 
-  CLOUD_CELLS;
-  cloud_load(P, cells, A, tr, tc, CLOUD_CELLS_ARGS);
-  for (int l = 0; l < A.n; ++l) {
+  TileCells q;
+  tile_load(P, cells, A.tab, 0, 0, M, M, tr, tc, q);
+  for (int l = 0; l < A.tab.n; ++l) {
     float v[NK];
-    cloud_value(A, l, CLOUD_CELLS_ARGS, C, v);
-    float (*tb)[T + 1] = tile[l & 1];
-#pragma unroll
-    for (int k = 0; k < NK; ++k) tb[x][y + (T / NK) * k] = v[k];
-    __syncthreads();       // (two buffers: whoever writes this one again, for entry l + 2, has passed the barrier of entry l + 1, which every reader of entry l reaches after its reads)
+    tile_value(A.tab, l, q, C, v);
+    transpose_put(tile[l & 1], v);
     const int f = A.field[l];
     if (A.cflags[l] & EM_CLOUD_POINT) {                        // x, y, z
       const float px = ii < M ? xs[ii] : 0.f;
 #pragma unroll
       for (int k = 0; k < NK; ++k) {
-        const int jl = y + (T / NK) * k;
-        if (live[k]) { float* o = out + rec[k] + f; o[0] = px; o[1] = ys[tc * T + jl]; o[2] = tb[jl][x]; }
+        if (live[k]) { float* o = out + rec[k] + f; o[0] = px; o[1] = ys[tc * T + y + (T / NK) * k]; o[2] = transpose_get(tile[l & 1], k); }
       }
     } else {
 #pragma unroll
-      for (int k = 0; k < NK; ++k) {
-        const int jl = y + (T / NK) * k;
-        if (live[k]) out[rec[k] + f] = tb[jl][x];
-      }
+      for (int k = 0; k < NK; ++k) if (live[k]) out[rec[k] + f] = transpose_get(tile[l & 1], k);
     }
   }
   if (A.call & EM_CLOUD_INDEX) {                               // lin = j * M + i, the iterator's linear index, as a 4-byte integer

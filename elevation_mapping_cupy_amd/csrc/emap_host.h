@@ -9,6 +9,7 @@
 #include "emap_launch.h"
 #include "../../include/emap_hip.h"
 #include <condition_variable>
+#include <cstring>
 #include <functional>
 #include <mutex>
 #include <string>
@@ -298,6 +299,36 @@ template <class T> int grow(emap_ctx* ctx, T** buf, size_t* cap, size_t need, Gr
 inline void bind_split_cloud(emap_ctx* ctx, const float* xyz, const float* chan, long n, long n_all, int K) {
   ctx->cloud = BoundCloud{xyz, n, 3, n_all, ChanView{K ? chan : xyz, K ? K : 3, K ? 3 : 0}, 3 + K};
   ctx->pts_bucketed = false;
+}
+
+// The layer table of the output doors on the published map (LayerTab, emap_publish_tile.h).  check_layer_entry: one entry of a caller's
+// table, refused with the caller's name (`who` ends in ": ") in front; plugin_ok admits EMAP_GRID_PLUGIN.
+inline int check_layer_entry(emap_ctx* ctx, const std::string& who, int kind, int index, int flags, bool plugin_ok) {
+  if (plugin_ok) CKARG(kind >= EMAP_GRID_BUILTIN && kind <= EMAP_GRID_PLUGIN, who + "kind must be 0 (built-in), 1 (semantic), 2 (normal colour) or 3 (plugin plane)");
+  else CKARG(kind >= EMAP_GRID_BUILTIN && kind <= EMAP_GRID_NORMAL_COLOR, who + "kind must be 0 (built-in), 1 (semantic) or 2 (normal colour)");
+  CKARG(kind != EMAP_GRID_BUILTIN || (index >= 0 && index <= 8), who + "a built-in index must lie in 0 .. 8");
+  CKARG(kind != EMAP_GRID_SEMANTIC || (index >= 0 && index < ctx->sem_layers), who + "semantic layer is not configured");
+  CKARG(kind != EMAP_GRID_PLUGIN || (index >= 0 && index < ctx->plane_n), who + "plugin plane is not reserved (emap_plugin_planes)");
+  CKARG(kind == EMAP_GRID_PLUGIN ? (flags & ~(EMAP_GRID_FILL_NAN | EMAP_GRID_ADD_Z)) == 0 : flags == 0, who + "flags: FILL_NAN / ADD_Z, on a plugin plane only");
+  return EMAP_OK;
+}
+// tab_init: an empty table on the context's planes; tab_put: appends a checked entry and returns its place; tab_finish: once all are in.
+inline LayerTab tab_init(const emap_ctx* ctx, float center_z, int only_above) {
+  LayerTab t; memset(&t, 0, sizeof t);
+  t.only_above = only_above ? 1 : 0; t.center_z = center_z;
+  t.plane = ctx->ncells_alloc; t.sem_plane = ctx->ncells_alloc; t.normal = ctx->normal; t.sem = ctx->sem; t.plug = ctx->plane_buf;
+  return t;
+}
+inline int tab_put(LayerTab& t, int kind, int index, int flags) {
+  const int l = t.n++;
+  t.kind[l] = (unsigned char)kind; t.index[l] = kind == EMAP_GRID_NORMAL_COLOR ? 0 : index; t.flags[l] = (unsigned char)flags;
+  t.need |= grid_need(kind, index);
+  return l;
+}
+inline void tab_finish(LayerTab& t) {
+  bool fill_nan = false;
+  for (int l = 0; l < t.n; ++l) fill_nan = fill_nan || (t.flags[l] & EMAP_GRID_FILL_NAN);
+  if (fill_nan && !(t.need & 3)) t.need |= 1;      // FILL_NAN reads is_valid: the hot half, unless the cold half (w mirrors it) is loaded anyway
 }
 }  // namespace emap_host
 

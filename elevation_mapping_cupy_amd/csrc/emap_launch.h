@@ -43,26 +43,9 @@ static inline int cloud_unpack_tile(int point_step) {
 #define EM_IMGMSG_SLACK 16
 struct ImgMsgEntry { int kind, layer, plane, pad; double alpha; };
 struct ImgMsgArgs { const unsigned char* msg; int H, W, step, elem, esize, n_chan, big, swap, n_specs, pad; ImgMsgEntry e[EM_IMGMSG_MAX_SPECS]; };
-// k_grid_map (emap_gridmsg.hip): every device-resident layer of a grid_map message from one launch.  Layer l of the table is written to
-// plane pos[l] of `out` (planes of M * M floats, M = C - 2; the host packs the caller's slots in ascending order), element (i, j) at
-// i * M + j (order 0) or j * M + i (order 1: the message's column-major Float32MultiArray).  kind / index: emap_hip.h (EMAP_GRID_*).
-// need: what the table reads of a cell -- bit 0 the hot half, 1 the cold half, 2 .. 4 the normal planes x, y, z (set by grid_need).
-// kind 3: resident plugin plane `index` of `plug` (planes of C * C floats in LOGICAL order: no circular origin), read at the logical source
-// cell; flags[l] bit 0: NaN where the cell is not valid, bit 1: + center_z (the plugin's fill_nan / is_height_layer).
-#define EM_GRID_MAX_LAYERS 32
-#define EM_GRID_TILE 32
-#define EM_GRID_FILL_NAN 1
-#define EM_GRID_ADD_Z 2
-struct GridArgs { int n, order, only_above, need; float center_z; int pad_; long plane, sem_plane; const float* normal; const float* sem; float* out;
-                  unsigned char kind[EM_GRID_MAX_LAYERS], pos[EM_GRID_MAX_LAYERS]; int index[EM_GRID_MAX_LAYERS];
-                  const float* plug; unsigned char flags[EM_GRID_MAX_LAYERS]; };
-static inline int grid_need(int kind, int index) {
-  if (kind == 3) return 0;                                              // plugin plane: its own plane (FILL_NAN: the host adds a half that carries valid)
-  if (kind == 1) return 0;                                              // semantic: its own plane
-  if (kind == 2) return 4 | 8 | 16;                                     // normal colour
-  if (index >= 6) return 4 << (index - 6);                              // normal_x / y / z
-  return index == 2 ? 3 : (index <= 1 ? 1 : 2);                         // traversability: both halves; elevation, variance: hot; time, upper_bound, is_upper_bound: cold (w = valid)
-}
+// The layer table of the output doors on the published map (LayerTab, grid_need), the device code that walks it and GridArgs, the
+// arguments of k_grid_map / k_grid_windows: emap_publish_tile.h.
+#include "emap_publish_tile.h"
 
 // ---- limits shared by the host layer and emap_binned.hip -----------------------------------------------------------------------------
 #define BIN_MAX_T 16384   /* LDS histogram / cursor arrays are dynamic: 4 B per tile */
@@ -222,15 +205,15 @@ void launch_polysafe_fold(hipStream_t, int, const PolyDesc*, int, const PolyPart
 // Submap service on the device (emap_submap.hip): a batch of windows of the published index space from ONE launch.  GridWin: one window
 // -- element (i, j) of it is published element (i0 + i, j0 + j), i.e. logical source cell (M - (i0 + i), M - (j0 + j)) -- and the float
 // at which its planes begin in the packed output (base = n_layers * the cells of the windows before it; plane l of the layer table
-// follows at l * ni * nj: no slot indirection, GridArgs::pos is not read).  GridItem: one 32 x 32 tile of one window, a workgroup each.
+// follows at pos[l] * ni * nj with pos[l] = l: no slot indirection).  GridItem: one 32 x 32 tile of one window, a workgroup each.
 #define EM_GRID_MAX_WINDOWS 64
 struct GridWin { int i0, j0, ni, nj; long base; long pad_; };
 struct GridItem { int win, tr, tc, pad_; };
 void launch_grid_windows(hipStream_t, const KP&, Cells, const GridArgs&, const GridWin*, const GridItem*, int);
 
 // Point-cloud output on the device (emap_cloudout.hip): the valid cells of the published map packed in grid_map's iterator order
-// (lin = j * M + i).  CloudArgs: a layer table as GridArgs carries it (kind / index / flags: emap_hip.h, EMAP_GRID_*; need: grid_need's
-// bits) -- the TESTED entries for k_cloud_count, the EMITTED ones for k_cloud_write, where field[l] is the first dword of entry l in a
+// (lin = j * M + i).  CloudArgs: a layer table (LayerTab, emap_publish_tile.h) -- the TESTED entries for k_cloud_count, the EMITTED
+// ones for k_cloud_write, where field[l] is the first dword of entry l in a
 // record of n_fields dwords and cflags[l] & EM_CLOUD_POINT marks the entry that emits x, y, z.  call: EM_CLOUD_NORMAL_MIN -- a cell
 // passes only if !((nx nx + ny ny) + nz nz < sum_min) in double (sum_min: the smallest double whose square root is not below the
 // caller's bound, so the test IS the one on the norm) --, EM_CLOUD_INDEX -- the last dword of a record is lin.  nt = ceil(M / 32);
@@ -241,9 +224,7 @@ void launch_grid_windows(hipStream_t, const KP&, Cells, const GridArgs&, const G
 #define EM_CLOUD_INDEX 16
 #define EM_CLOUD_SCAN_BLOCK 1024
 #define EM_CLOUD_SCAN_TRIP (4 * EM_CLOUD_SCAN_BLOCK)
-struct CloudArgs { int n, need, only_above, call, nt, n_fields; float center_z; int pad_; long cap; double sum_min; long plane, sem_plane;
-                   const float* normal; const float* sem; const float* plug; int index[EM_GRID_MAX_LAYERS];
-                   unsigned char kind[EM_GRID_MAX_LAYERS], flags[EM_GRID_MAX_LAYERS], cflags[EM_GRID_MAX_LAYERS], field[EM_GRID_MAX_LAYERS]; };
+struct CloudArgs { LayerTab tab; int call, nt, n_fields, pad_; long cap; double sum_min; unsigned char cflags[EM_GRID_MAX_LAYERS], field[EM_GRID_MAX_LAYERS]; };
 void launch_cloud_count(hipStream_t, const KP&, Cells, const CloudArgs&, unsigned int* masks);
 void launch_cloud_scan(hipStream_t, const unsigned int* masks, unsigned int* offs, long W, unsigned int* total);
 void launch_cloud_write(hipStream_t, const KP&, Cells, const CloudArgs&, const float* xs, const float* ys, const unsigned int* masks, const unsigned int* offs, float* out);

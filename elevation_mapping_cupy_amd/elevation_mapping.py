@@ -138,6 +138,25 @@ GRID_BUILTIN_LAYERS = ("elevation", "variance", "traversability", "time", "upper
 GRID_NORMAL_COLOR_LAYERS = ("normal_x", "normal_y", "normal_z", "color")      # what the wrapper appends with enable_normal_color (elevation_mapping_wrapper.cpp:239-251)
 
 
+def _basic_layers(layers, basic_layers):
+    """the wrapper's rule for ``basic_layers=None``: ``["elevation"]`` if it was asked for"""
+    if basic_layers is None:
+        return ["elevation"] if "elevation" in layers else []
+    return list(basic_layers)
+
+
+def _grid_map_envelope(names, flat, ni, nj, position, lengths, resolution, basic_layers, header, **extra):
+    """the duck-typed ``grid_map_msgs/GridMap`` around ``flat`` (``(len(names), ni * nj)``, column-major planes of ``ni x nj`` cells): the header
+    both as ``msg.header`` and ``msg.info.header``, the pose at ``position`` with the identity orientation, one ``Float32MultiArray`` per layer
+    whose ``data`` is a view of its row of ``flat``; ``extra``: fields only some doors add (``index_in_submap``)"""
+    ns = types.SimpleNamespace
+    pose = ns(position=ns(x=position[0], y=position[1], z=0.0), orientation=ns(x=0.0, y=0.0, z=0.0, w=1.0))
+    info = ns(header=header, resolution=resolution, length_x=lengths[0], length_y=lengths[1], pose=pose)
+    data = [ns(layout=ns(dim=[ns(label="column_index", size=nj, stride=ni * nj), ns(label="row_index", size=ni, stride=ni)], data_offset=0),
+               data=flat[k]) for k in range(len(names))]
+    return ns(header=header, info=info, layers=names, basic_layers=list(basic_layers), data=data, outer_start_index=0, inner_start_index=0, **extra)
+
+
 def grid_map_descriptor(layers, semantic_layers=(), normal_color=False, slots=None):
     """``(table, names)`` of a GridMap publisher's layer list for ``emap_publish_grid_map`` (include/emap_hip.h); needs no context.
 
@@ -1054,12 +1073,10 @@ class ElevationMap:
     def get_map_with_name_ref(self, name, data):
         """Fill ``data`` (float32, ``(cell_n-2, cell_n-2)``) in place: border stripped, both axes flipped
         (reference :720-775)."""
-        builtin = {"elevation": 0, "variance": 1, "traversability": 2, "time": 3, "upper_bound": 4, "is_upper_bound": 5,
-                   "normal_x": 6, "normal_y": 7, "normal_z": 8}
-        if name in builtin and self._strip is None and isinstance(data, np.ndarray) and data.dtype == np.float32 \
+        if name in GRID_BUILTIN_LAYERS and self._strip is None and isinstance(data, np.ndarray) and data.dtype == np.float32 \
                 and data.flags["C_CONTIGUOUS"] and data.shape == (self.cell_n - 2, self.cell_n - 2):
             with self.map_lock:   # strip / NaN fill / +center_z / double flip happen in one device kernel
-                self._chk(self._lib.emap_publish_layer(self._ctx, builtin[name], ct.c_float(float(self.center[2])),
+                self._chk(self._lib.emap_publish_layer(self._ctx, GRID_BUILTIN_LAYERS.index(name), ct.c_float(float(self.center[2])),
                                                        int(bool(self.param.use_only_above_for_upper_bound)), f32p(data)))
             return
         with self.map_lock:
@@ -1166,12 +1183,21 @@ class ElevationMap:
                 print("Layer {} is not in the map".format(n))
         return plan
 
+    def _plugin_steps(self, plan):
+        """the ``plugin_chain_plan`` steps of the plugin layers of ``plan`` (the entries without a device source); ``EMAP_PLUGIN_RESIDENT=0``
+        in the environment sends every plugin through its host route"""
+        pm = self.plugin_manager
+        want = [n for n, e in plan if e is None]
+        if pm is None or not want:
+            return []
+        sem = self.semantic_map.layer_names if self.semantic_map is not None else []
+        return plugin_chain_plan(want, pm.plugins, pm.layer_names, self.layer_names, sem, resident=os.environ.get("EMAP_PLUGIN_RESIDENT", "1") != "0")
+
     def _grid_plugins(self, plan, host_plane):
         """the plugin layers of ``plan`` computed in list order, ONCE over the whole map: device-capable plugins as ops of the chain into
         their resident planes, the others on the host -- ``host_plane(name, m)`` takes the published plane (float32, ``(M, M)``, what
         ``get_map_with_name_ref`` leaves).  Sets ``last_plugin_route``; returns the device table ``[(kind, index, position in plan,
         flags)]`` of everything a grid launch can write.  The caller holds ``map_lock``."""
-        sem = self.semantic_map.layer_names if self.semantic_map is not None else []
         pm = self.plugin_manager
         plug = pm.layer_names if pm is not None else []
 
@@ -1183,9 +1209,7 @@ class ElevationMap:
 
         self._last_plugin_route = {}
         if pm is not None and any(e is None for _, e in plan):
-            steps = plugin_chain_plan([n for n, e in plan if e is None], pm.plugins, plug, self.layer_names, sem,
-                                      resident=os.environ.get("EMAP_PLUGIN_RESIDENT", "1") != "0")
-            self._last_plugin_route = pm.run_plan(steps, host_step, self.base_rotation)
+            self._last_plugin_route = pm.run_plan(self._plugin_steps(plan), host_step, self.base_rotation)
         device = []
         for slot, (n, e) in enumerate(plan):
             if e is not None:
@@ -1334,26 +1358,17 @@ class ElevationMap:
         wins = [g[:4] for g in geo if g is not None]
         with self.map_lock:
             names, views = self._submap_layers_locked(wins, layers, out, "message", normal_color)
-        ns = types.SimpleNamespace
-        if basic_layers is None:
-            basic_layers = ["elevation"] if "elevation" in layers else []
+        basic_layers = _basic_layers(layers, basic_layers)
         answers, views = [], iter(views)
         for g in geo:
-            header = ns(frame_id=str(frame_id), stamp=stamp, seq=0)
+            header = types.SimpleNamespace(frame_id=str(frame_id), stamp=stamp, seq=0)
             if g is None:
-                pose = ns(position=ns(x=0.0, y=0.0, z=0.0), orientation=ns(x=0.0, y=0.0, z=0.0, w=1.0))
-                info = ns(header=header, resolution=float(self.resolution), length_x=0.0, length_y=0.0, pose=pose)
-                answers.append((ns(header=header, info=info, layers=[], basic_layers=[], data=[], outer_start_index=0, inner_start_index=0,
-                                   index_in_submap=None), False))
+                answers.append((_grid_map_envelope([], [], 0, 0, (0.0, 0.0), (0.0, 0.0), float(self.resolution), [], header, index_in_submap=None), False))
                 continue
             _, _, ni, nj, sub_pos, sub_len, inside = g
             flat = next(views).reshape(len(names), ni * nj)
-            pose = ns(position=ns(x=sub_pos[0], y=sub_pos[1], z=0.0), orientation=ns(x=0.0, y=0.0, z=0.0, w=1.0))
-            info = ns(header=header, resolution=float(self.resolution), length_x=sub_len[0], length_y=sub_len[1], pose=pose)
-            data = [ns(layout=ns(dim=[ns(label="column_index", size=nj, stride=ni * nj), ns(label="row_index", size=ni, stride=ni)], data_offset=0),
-                       data=flat[k]) for k in range(len(names))]
-            answers.append((ns(header=header, info=info, layers=list(names), basic_layers=list(basic_layers), data=data, outer_start_index=0,
-                               inner_start_index=0, index_in_submap=inside), True))
+            answers.append((_grid_map_envelope(list(names), flat, ni, nj, sub_pos, sub_len, float(self.resolution), basic_layers, header,
+                                               index_in_submap=inside), True))
         return answers
 
     def get_submap_message(self, position_xy, length_xy, layers=None, **keywords):
@@ -1399,13 +1414,7 @@ class ElevationMap:
         return dict(zip(names, planes))
 
     def _any_host_plugin(self, plan):
-        pm = self.plugin_manager
-        want = [n for n, e in plan if e is None]
-        if pm is None or not want:
-            return False
-        sem = self.semantic_map.layer_names if self.semantic_map is not None else []
-        steps = plugin_chain_plan(want, pm.plugins, pm.layer_names, self.layer_names, sem, resident=os.environ.get("EMAP_PLUGIN_RESIDENT", "1") != "0")
-        return any(s[0] == "host" for s in steps)
+        return any(s[0] == "host" for s in self._plugin_steps(plan))
 
     def get_point_cloud_message(self, layers=("elevation",), point_layer="elevation", basic_layers=None, frame_id="", stamp=None, normal_color=False, out=None):
         """The node's ``elevation_map_points`` publisher (elevation_mapping_ros.cpp:501-505: ``GridMapRosConverter::toPointCloud``) without a
@@ -1429,9 +1438,7 @@ class ElevationMap:
         ``map_lock`` for the call."""
         self._require_full_map("get_point_cloud_message")
         layers = list(layers)
-        if basic_layers is None:
-            basic_layers = ["elevation"] if "elevation" in layers else []
-        basic_layers = list(basic_layers)
+        basic_layers = _basic_layers(layers, basic_layers)
         M = self.cell_n - 2
         xs, ys = self._cell_positions()
         with self.map_lock:
@@ -1510,16 +1517,9 @@ class ElevationMap:
         layers = list(layers)
         names, buf = self.get_grid_map_layers(layers, out=out, order="message", normal_color=normal_color)
         M = self.cell_n - 2
-        ns = types.SimpleNamespace
-        header = ns(frame_id=str(frame_id), stamp=stamp, seq=0)
-        pose = ns(position=ns(x=float(self.center[0]), y=float(self.center[1]), z=0.0), orientation=ns(x=0.0, y=0.0, z=0.0, w=1.0))
-        info = ns(header=header, resolution=float(self.resolution), length_x=float(self.map_length), length_y=float(self.map_length), pose=pose)
-        flat = buf.reshape(len(names), M * M)
-        data = [ns(layout=ns(dim=[ns(label="column_index", size=M, stride=M * M), ns(label="row_index", size=M, stride=M)], data_offset=0),
-                   data=flat[k]) for k in range(len(names))]
-        if basic_layers is None:
-            basic_layers = ["elevation"] if "elevation" in layers else []
-        return ns(header=header, info=info, layers=names, basic_layers=list(basic_layers), data=data, outer_start_index=0, inner_start_index=0)
+        header = types.SimpleNamespace(frame_id=str(frame_id), stamp=stamp, seq=0)
+        return _grid_map_envelope(names, buf.reshape(len(names), M * M), M, M, (float(self.center[0]), float(self.center[1])),
+                                  (float(self.map_length), float(self.map_length)), float(self.resolution), _basic_layers(layers, basic_layers), header)
 
     def _require_full_map(self, what):
         if self._strip is not None:

@@ -103,7 +103,11 @@ def test_one_definition_of_the_values_and_no_atomic():
     assert dev.count("float normal_color(") == 1 and dev.count("float publish_value(") == 1
     s = open(os.path.join(CSRC, "emap_cloudout.hip")).read()
     assert "float normal_color(" not in s and "float publish_value(" not in s
-    assert s.count("normal_color(nx[k], ny[k], nz[k])") == 1 and s.count("publish_value(index, m, rr[k], c, C") == 1      # one walk for both kernels
+    walk = open(os.path.join(CSRC, "emap_publish_tile.h")).read()
+    assert walk.count("normal_color(q.nrm[0][k], q.nrm[1][k], q.nrm[2][k])") == 1 and walk.count("publish_value(index, m, q.rr[k], q.c, C") == 1      # one walk ...
+    for door in (s, open(os.path.join(CSRC, "emap_gridmsg.hip")).read(), open(os.path.join(CSRC, "emap_submap.hip")).read()):
+        assert "normal_color(" not in door and "publish_value(" not in door      # ... that no door restates
+    assert s.count("tile_value(A.tab, l, q, C, v)") == 2                       # and both kernels call
     code = "\n".join(line.split("//")[0] for line in s.splitlines())
     assert "atomic" not in code                                                # no atomic decides a position
     launch = open(os.path.join(CSRC, "emap_launch.h")).read()

@@ -151,6 +151,33 @@ def test_a_device_plugin_and_a_host_route_plugin(C, tmp_path):
         m.close()
 
 
+PUB = [pc._entry("smooth_filter", "pub_%d%d" % (f, h), fill_nan=f, height=h, input_layer_name="elevation") for f in (0, 1) for h in (0, 1)]      # fill_nan x is_height_layer
+PUB_CASES = {      # layers, point layer, basic layers
+    "plain and ADD_Z, no cell layer": (["pub_01", "pub_00"], "pub_01", ["pub_01"]),
+    "FILL_NAN where no half is asked for": (["pub_11", "pub_10"], "pub_11", ["pub_11"]),
+    "FILL_NAN beside the hot half": (["elevation", "pub_10", "pub_11"], "elevation", None),
+    "FILL_NAN beside the cold half only": (["upper_bound", "time", "pub_10"], "upper_bound", ["upper_bound", "pub_10"]),
+}
+
+
+@pytest.mark.parametrize("C", (10, 67))
+def test_plugin_planes_with_every_flag_beside_each_half_of_a_cell(C, tmp_path):
+    """the branches of the plugin-plane entry, tested and emitted: no flag, ADD_Z, and FILL_NAN taking is_valid from the hot half it adds,
+    from a hot half that is loaded anyway, and from cold.w when only the cold half is"""
+    cfg = tmp_path / "plugins.yaml"
+    cfg.write_text(pc.yaml_of(PUB))
+    m = gc.start(C, plugin_file=cfg)
+    try:
+        counts = {}
+        for what, (layers, point, basic) in PUB_CASES.items():
+            _, want = _check(m, layers, point_layer=point, basic=basic, what=what)
+            assert set(m.last_plugin_route.values()) == {"device"}, what
+            counts[what] = want.shape[0]
+        assert 0 < counts["FILL_NAN where no half is asked for"] < counts["plain and ADD_Z, no cell layer"]      # the fill does skip cells
+    finally:
+        m.close()
+
+
 # ---- 3. arrows ----------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("C", (10, 35, 67))
 def test_the_normal_arrows(C, monkeypatch):

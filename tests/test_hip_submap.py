@@ -166,6 +166,30 @@ def test_a_device_plugin_and_a_host_route_plugin_in_one_list(C, order, tmp_path)
         m.close()
 
 
+PUB = [pc._entry("smooth_filter", "pub_%d%d" % (f, h), fill_nan=f, height=h, input_layer_name="elevation") for f in (0, 1) for h in (0, 1)]      # fill_nan x is_height_layer
+PUB_LISTS = {"plain and ADD_Z, no cell layer": ["pub_00", "pub_01"], "FILL_NAN where no half is asked for": ["pub_10", "pub_11"],
+             "FILL_NAN beside the hot half": ["elevation", "pub_10", "pub_11"], "FILL_NAN beside the cold half only": ["time", "pub_10", "upper_bound", "pub_11"]}
+
+
+@pytest.mark.parametrize("order", gc.ORDERS)
+@pytest.mark.parametrize("C", (10, 67))
+def test_plugin_planes_with_every_flag_beside_each_half_of_a_cell(C, order, tmp_path):
+    """the branches of the plugin-plane entry: no flag, ADD_Z, and FILL_NAN taking is_valid from the hot half it adds, from a hot half
+    that is loaded anyway, and from cold.w when only the cold half is"""
+    cfg = tmp_path / "plugins.yaml"
+    cfg.write_text(pc.yaml_of(PUB))
+    m = gc.start(C, plugin_file=cfg)
+    try:
+        for what, layers in PUB_LISTS.items():
+            names, views = _check(m, sc.all_windows(C - 2), layers, order, what=what)
+            assert names == layers and set(m.last_plugin_route.values()) == {"device"}, what
+            if "pub_10" in names:
+                whole = views[0][names.index("pub_10")]                         # the first window of the batch is the whole map
+                assert np.isnan(whole).any() and np.isfinite(whole).any(), what
+    finally:
+        m.close()
+
+
 def test_the_plugins_run_once_per_call_not_once_per_window(tmp_path):
     C = 34
     cfg = tmp_path / "plugins.yaml"

@@ -95,6 +95,8 @@ def test_one_definition_of_the_values_for_both_kernels():
     csrc = os.path.join(ROOT, "elevation_mapping_cupy_amd", "csrc")
     dev = open(os.path.join(csrc, "emap_device.h")).read()
     assert dev.count("float normal_color(") == 1 and dev.count("float publish_value(") == 1
+    walk = open(os.path.join(csrc, "emap_publish_tile.h")).read()             # the one walk of the layer table: both kernels run its grid_tile
+    assert walk.count("normal_color(q.nrm[0][k]") == 1 and walk.count("publish_value(index, m, q.rr[k], q.c, C") == 1 and "float normal_color(" not in walk
     for f in ("emap_gridmsg.hip", "emap_submap.hip"):
         s = open(os.path.join(csrc, f)).read()
-        assert "float normal_color(" not in s and "normal_color(nrm[0][k]" in s and "publish_value(index, m, rr[k], c, C" in s, f
+        assert "normal_color(" not in s and "publish_value(" not in s and s.count("publish_tile::grid_tile<ORDER>(") == 1, f
