@@ -198,6 +198,11 @@ struct emap_ctx {
   // on demand, no allocation per call
   unsigned char* cloud_tab; size_t cloud_tab_cap; unsigned char* cloud_pin; size_t cloud_pin_cap;      // bytes
   float* cloud_out; size_t cloud_out_cap;                     // floats
+  // plane segmentation on the device (emap_api_planeseg.hip): ONE device buffer for the per-cell planes, the mask and offset words and
+  // the head words (PlaneBufs, emap_launch.h), the slots of the labels that get a plane -- sized by how many there ARE, known after the
+  // first wait -- and the pinned buffer the head words and the slots land in; all grown on demand, no allocation per call
+  unsigned char* pseg_buf; size_t pseg_cap; unsigned char* pseg_pin; size_t pseg_pin_cap;      // bytes
+  PlaneSlot* pseg_slots; size_t pseg_slots_cap;               // slots
   // frame state
   bool use_override; double sum_override; unsigned int cnt_override;
   bool committed;

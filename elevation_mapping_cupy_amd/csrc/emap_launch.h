@@ -228,3 +228,30 @@ struct CloudArgs { LayerTab tab; int call, nt, n_fields, pad_; long cap; double 
 void launch_cloud_count(hipStream_t, const KP&, Cells, const CloudArgs&, unsigned int* masks);
 void launch_cloud_scan(hipStream_t, const unsigned int* masks, unsigned int* offs, long W, unsigned int* total);
 void launch_cloud_write(hipStream_t, const KP&, Cells, const CloudArgs&, const float* xs, const float* ys, const unsigned int* masks, const unsigned int* offs, float* out);
+
+// Plane segmentation on the device (emap_planeseg.hip): the front of convex_plane_decomposition's SlidingWindowPlaneExtractor on ONE
+// source layer of the published map -- planar cells, connected labels, one plane per label.  Every plane below is
+// dense M x M in published index space, cell (i, j) at idx = i * M + j.  PlaneArgs: the call's constants (angles arrive as cosines, the
+// patch threshold squared, all in double).  PlaneBufs: the planes and words the chain works on, carved by the host file out of buffers
+// the context owns -- src: the source heights; nrm: 3 planes of window normals (float); bit / bit2: the planar bytes and the opening's
+// second image; parent: the union-find links (a link only ever points to a SMALLER idx; -1: not planar), later the numbered labels;
+// root: every cell's root, a plane of its own; cnt / amin: per ROOT cell the finite members and the smallest finite member; mask1 /
+// offs1: a bit per cell "is a root" and the exclusive scan of its popcounts (k_cloud_scan's layout: EM_CLOUD_SCAN_TRIP words a trip);
+// mask2 / offs2: the same for "is a root with at least min_points members", i.e. owns a slot; head: [0] labels, [1] slots.
+// PlaneSlot: one label that gets a plane.  s[]: the exact integer moments n, S di, S dj, S q, S di di, S dj dj, S di dj, S di q,
+// S dj q, S q q about the anchor (root cell, height of cell amin); kdist / kdot: monotone keys of the largest plane distance and of
+// the largest NEGATED normal dot product (atomicMax, identity 0); the rest is written by k_ps_finalise.
+#define EM_PLANE_SWEEPS 4        /* Jacobi sweeps of the 3 x 3 eigenproblem: FIXED (tests/test_plane_seg_cases.py measures the count) */
+#define EM_PLANE_OPEN_MAX 8      /* opening radius the door accepts (a cap, not a measurement) */
+#define EM_PLANE_Q_BITS 13       /* heights enter the label moments as multiples of 2^-13 m about the anchor */
+#define EM_PLANE_Q_RANGE 32.0    /* ... and a cell farther than this from its anchor is left out and counted */
+struct PlaneArgs { int M, K, conn, open_r, min_points, pad_; double res, thr2, cos_local, cos_plane, ox, oy; };
+struct PlaneBufs { float* src; float* nrm; unsigned char* bit; unsigned char* bit2; int* parent; int* root; int* cnt; int* amin;
+                   unsigned int* mask1; unsigned int* offs1; unsigned int* mask2; unsigned int* offs2; unsigned int* head; };
+struct PlaneSlot { long long s[10]; unsigned long long kdist, kdot; double support[3], normal[3]; int label, root, accept, left_out; };
+void launch_ps_source(hipStream_t, const KP&, Cells, const LayerTab&, float* src);
+void launch_ps_window(hipStream_t, const PlaneArgs&, const PlaneBufs&);
+void launch_ps_morph(hipStream_t, int M, int radius, int dilate, const unsigned char* in, unsigned char* out);
+void launch_ps_labels(hipStream_t, const PlaneArgs&, const PlaneBufs&, const unsigned char* bit);
+void launch_ps_moments(hipStream_t, const PlaneArgs&, const PlaneBufs&, PlaneSlot* slots);
+void launch_ps_planes(hipStream_t, const PlaneArgs&, const PlaneBufs&, PlaneSlot* slots, int n_slots, int* labels);

@@ -526,6 +526,7 @@ class ElevationMap:
         self._last_plugin_route = {}
         self.last_submap_route = None               # "device" | "host": the route of the last submap call (EMAP_SUBMAP_RESIDENT)
         self.last_point_cloud_route = None          # "device" | "host": the route of the last point-cloud / arrow call (EMAP_CLOUD_RESIDENT)
+        self.last_plane_segmentation_route = None   # "device" | "host": the route of the last get_plane_segmentation call (EMAP_PLANES_RESIDENT)
         self._mask = self._mask_polygon = None      # safety-polygon service: the mask is built when it is read
         self.last_polygon_route = None              # "device" | "host": the route of the last safety check
         self.untraversable_polygon = None
@@ -1506,6 +1507,75 @@ class ElevationMap:
         starts = np.stack([xs[ids % M], ys[ids // M], rec[:, 2].astype(np.float64)], axis=1)
         ends = starts + rec[:, 3:6].astype(np.float64) * scale
         return types.SimpleNamespace(ids=ids, starts=starts, ends=ends)
+
+    # ---- plane segmentation (include/emap_hip.h: emap_plane_segmentation) -----------------------------------------------------------------
+    def get_plane_segmentation(self, layer="elevation", *, kernel_size=3, planarity_opening_filter=0, plane_inclination_threshold_degrees=30.0,
+                               local_plane_inclination_threshold_degrees=35.0, plane_patch_error_threshold=0.02, min_number_points_per_label=4,
+                               connectivity=4, global_plane_fit_distance_error_threshold=0.025, global_plane_fit_angle_error_threshold_degrees=25.0,
+                               normals=False, out=None):
+        """The front of convex_plane_decomposition (SlidingWindowPlaneExtractor::runExtraction without RANSAC) on one published layer, without
+        the map leaving the device: a plane fitted to the ``kernel_size``^2 window of every cell, planar cells, optionally an opening,
+        connected labels, one plane per label (DESIGN.md section 21 holds the contract).  The keywords are the reference's
+        ``parameters.yaml`` names and defaults.  Returns a namespace: ``labels`` int32 ``(M, M)`` in the index space of
+        ``get_grid_map_layers(order="rows")``, 0 = background (``out``: an array of that kind to fill); ``n_labels``; ``planes``: a structured
+        array (``label``, ``n_points``, ``needs_refinement``, ``n_left_out``, ``support`` and ``normal`` 3 x float64, map frame) with one
+        row per label that has a plane, ascending; ``normals`` float32 ``(3, M, M)`` with ``normals=True``, else ``None``; ``origin_xy`` (the
+        position of cell (0, 0)) and ``resolution``: cell ``(i, j)`` lies at ``origin_xy - (i, j) * resolution``.
+
+        ``layer``: a map layer, a semantic layer or a plugin layer, as ``get_grid_map_layers`` publishes it; a plugin layer runs through the
+        plugin chain first and is read as a resident plane -- one that takes its host route is refused (``ValueError``), not downloaded and
+        uploaded again.  ``EMAP_PLANES_RESIDENT=0`` in the environment: the whole layer is downloaded and segmented by the host model
+        (``plane_segmentation.segment``), the same answer; ``last_plane_segmentation_route`` tells which ran."""
+        from . import plane_segmentation as host_model
+        self._require_full_map("get_plane_segmentation")
+        kernel_size, opening, min_points, connectivity = int(kernel_size), int(planarity_opening_filter), int(min_number_points_per_label), int(connectivity)
+        if kernel_size not in (3, 5, 7) or connectivity not in (4, 8) or not 0 <= opening <= _lib.PLANE_OPEN_MAX or min_points < 0:
+            raise ValueError("kernel_size is 3, 5 or 7, connectivity 4 or 8, planarity_opening_filter 0 .. %d, min_number_points_per_label not negative" % _lib.PLANE_OPEN_MAX)
+        angles = [float(a) for a in (plane_inclination_threshold_degrees, local_plane_inclination_threshold_degrees, global_plane_fit_angle_error_threshold_degrees)]
+        lengths = [float(plane_patch_error_threshold), float(global_plane_fit_distance_error_threshold)]
+        if not all(np.isfinite(v) and v > 0.0 for v in angles + lengths) or any(a > 180.0 for a in angles):
+            raise ValueError("thresholds must be positive and finite (angles in degrees, at most 180)")
+        M = self.cell_n - 2
+        if out is None:
+            out = np.empty((M, M), np.int32)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.int32 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.shape == (M, M)):
+            raise ValueError("out must be a writeable C-contiguous int32 array of shape (%d, %d)" % (M, M))
+        xs, ys = self._cell_positions()
+        origin, res = (float(xs[0]), float(ys[0])), float(np.float32(self.resolution))
+        keywords = dict(kernel_size=kernel_size, planarity_opening_filter=opening, plane_inclination_threshold_degrees=angles[0],
+                        local_plane_inclination_threshold_degrees=angles[1], plane_patch_error_threshold=lengths[0], min_number_points_per_label=min_points,
+                        connectivity=connectivity, global_plane_fit_distance_error_threshold=lengths[1], global_plane_fit_angle_error_threshold_degrees=angles[2])
+        with self.map_lock:
+            plan = self._grid_plan([layer], False)
+            if len(plan) != 1:
+                raise ValueError("layer %r is not a layer this map publishes" % (layer,))
+            resident = os.environ.get("EMAP_PLANES_RESIDENT", "1") != "0"
+            self.last_plane_segmentation_route = "device" if resident else "host"
+            if not resident:
+                _, planes = self._grid_map_layers_locked([layer], None, "rows", False)
+                r = host_model.segment(planes[0], res, origin, **keywords)
+                out[...] = r.labels
+                return types.SimpleNamespace(labels=out, n_labels=r.n_labels, planes=r.planes, normals=r.normals if normals else None, origin_xy=origin, resolution=res)
+            if self._any_host_plugin(plan):
+                raise ValueError("plugin layer %r takes its host route: it is not resident on the device (get_grid_map_layers computes it on the host)" % (layer,))
+            kind, index, _, flags = self._grid_plugins(plan, None)[0]
+            src = EmapGridLayerEx(int(kind), int(index), 0, int(flags))
+            cos_plane, cos_local, cos_angle = host_model.cosines(*angles)
+            P = _lib.EmapPlaneParams(kernel_size, opening, min_points, connectivity, int(bool(self.param.use_only_above_for_upper_bound)), 0, float(self.center[2]), 0.0,
+                                     res, origin[0], origin[1], lengths[0], cos_local, cos_plane, lengths[1], cos_angle)
+            nrm = np.empty((3, M, M), np.float32) if normals else None
+            capacity = 256
+            while True:                                 # (a second trip only when more than `capacity` labels have a plane)
+                planes = np.zeros(capacity, _lib.PLANE_RECORD_DTYPE)
+                n_labels, n_planes = ct.c_int32(0), ct.c_int64(0)
+                rc = self._lib.emap_plane_segmentation(self._ctx, ct.byref(src), ct.byref(P), out.ctypes.data_as(ct.POINTER(ct.c_int32)), f32p(nrm) if normals else None,
+                                                       planes.ctypes.data_as(ct.POINTER(_lib.EmapPlaneRecord)), capacity, ct.byref(n_labels), ct.byref(n_planes))
+                if rc == -1 and n_planes.value > capacity:
+                    capacity = int(n_planes.value)
+                    continue
+                self._chk(rc)
+                break
+        return types.SimpleNamespace(labels=out, n_labels=int(n_labels.value), planes=planes[:n_planes.value], normals=nrm, origin_xy=origin, resolution=res)
 
     def get_grid_map_message(self, layers, basic_layers=None, frame_id="", stamp=None, normal_color=False, out=None):
         """A duck-typed ``grid_map_msgs/GridMap`` of ``layers`` (``types.SimpleNamespace``, no ROS import): ``info.resolution``,

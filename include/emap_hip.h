@@ -308,6 +308,43 @@ typedef struct emap_cloud_field { int32_t kind, index, flags, cloud_flags; } ema
 int emap_publish_point_cloud(emap_ctx* ctx, const emap_cloud_field* fields, int32_t n_fields, float center_z,
                              int32_t use_only_above_for_upper_bound, const float* x_of_i, const float* y_of_j, double normal_min,
                              int32_t call_flags, uint8_t* host_out, int64_t capacity_points, int64_t* n_points, int32_t* point_step);
+/* Plane segmentation: the front of convex_plane_decomposition on ONE layer of the published map, on the device -- what
+ * SlidingWindowPlaneExtractor::runExtraction (SlidingWindowPlaneExtractor.cpp:49-77) does with a downloaded GridMap:
+ * runSlidingWindowDetector (:115-144: a plane fitted to the kernel_size^2 window of every cell with a finite height, :79-105, :19-41;
+ * planar when the error and the inclination pass, :107-113; optionally an opening with a cross, :137-143), runSegmentation (:147-150:
+ * connected components, connectivity 4 or 8), computePlaneParametersForLabel without RANSAC (:165-199 and the else branch :213-219: a
+ * label with fewer than max(min_number_points_per_label, 3) finite cells gets no plane and keeps its cells; a label whose plane is
+ * steeper than the inclination limit becomes background) and the verdict of isGloballyPlanar (:277-300) as needs_refinement.  RANSAC
+ * itself, contours and the preprocessing are not part of it.  The contract -- a FIXED number of Jacobi sweeps, the order of the window
+ * sums, the edge rule, the numbering, the fixed-point label moments -- is DESIGN.md section 21; grid_map's SlidingWindowIterator and
+ * OpenCV's connectedComponents are restated there, not pinned by a compiled reference.
+ * source: kind / index / flags as in emap_publish_grid_map_ex (slot is not read).  The index space is that door's: M = cell_n - 2 a
+ * side, cell (i, j) at i * M + j.  params: angles arrive as COSINES and the caller computes them in double; origin_x / origin_y: the
+ * position of cell (0, 0); a cell's point is (origin_x - i * resolution, origin_y - j * resolution, height).
+ * host_labels: M * M int32, 0 = background, label = 1 + the rank of the component's first cell in row-major order (a rejected label
+ * leaves a gap).  host_normals: NULL or 3 * M * M floats, the window normals (zero where the height is not finite).  host_planes:
+ * one record per label that has a plane, in ascending label order; n_left_out: cells farther than 32 m from the label's first cell,
+ * which the fixed-point moments leave out.  *n_labels: the components; *n_planes: the records.
+ * Two waits: the chain up to the numbering, an 8-byte copy of the label and slot counts, a wait; the context sizes its slot buffer by
+ * that count; moments, planes and final labels, the copies, a second wait.  If more than capacity_planes labels have a plane,
+ * *n_labels, *n_planes, host_labels and host_normals are set, NO record is written and EMAP_ERR_INVALID is returned (a caller tells
+ * it from a refusal by *n_planes > capacity_planes).  The buffers belong to the context and grow on demand.
+ * Refused with EMAP_ERR_INVALID before anything is launched or copied, every output and the map untouched: a NULL pointer (host_normals
+ * may be NULL); everything emap_publish_grid_map_ex refuses of an entry; kernel_size other than 3, 5, 7; connectivity other than 4, 8;
+ * planarity_opening_filter outside 0 .. EMAP_PLANE_OPEN_MAX; min_number_points_per_label < 0; a resolution or threshold that is not
+ * positive and finite; a cosine outside [-1, 1]; an origin or center_z that is not finite; a negative capacity_planes; a row-strip
+ * context. */
+enum { EMAP_PLANE_OPEN_MAX = 8 };
+typedef struct emap_plane_params {
+  int32_t kernel_size, planarity_opening_filter, min_number_points_per_label, connectivity, use_only_above_for_upper_bound, reserved;
+  float center_z, reserved_f;
+  double resolution, origin_x, origin_y, plane_patch_error_threshold, cos_local_plane_inclination, cos_plane_inclination,
+         global_plane_fit_distance_error_threshold, cos_global_plane_fit_angle;
+} emap_plane_params;
+typedef struct emap_plane_record { int32_t label, n_points, needs_refinement, n_left_out; double support[3], normal[3]; } emap_plane_record;
+int emap_plane_segmentation(emap_ctx* ctx, const emap_grid_layer_ex* source, const emap_plane_params* params, int32_t* host_labels,
+                            float* host_normals, emap_plane_record* host_planes, int64_t capacity_planes, int32_t* n_labels,
+                            int64_t* n_planes);
 /* ElevationMap.shift_map_xy / shift_map_z (EM/elevation_mapping.py:200-226): roll by (dx rows, dy cols) with
  * padding (0; variance plane initial_variance), planes 0 and 5 += dz -- as a rotation of the map's circular origin plus a pending
  * entry that later kernels replay: no cell is moved, only the entering band of the semantic layers is cleared.  Works on strips
