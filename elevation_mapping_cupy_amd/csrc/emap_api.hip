@@ -328,6 +328,7 @@ int emap_destroy(emap_ctx* ctx) {
   hipFree(ctx->sub_tab); hipFree(ctx->sub_out); if (ctx->sub_pin) hipHostFree(ctx->sub_pin);
   hipFree(ctx->cloud_tab); hipFree(ctx->cloud_out); if (ctx->cloud_pin) hipHostFree(ctx->cloud_pin);
   hipFree(ctx->pseg_buf); hipFree(ctx->pseg_slots); if (ctx->pseg_pin) hipHostFree(ctx->pseg_pin);
+  hipFree(ctx->terr_buf); if (ctx->terr_pin) hipHostFree(ctx->terr_pin);
   hipFree(ctx->plane_buf); hipFree(ctx->chain_buf); hipFree(ctx->chain_cnt); hipFree(ctx->chain_red); hipFree(ctx->chain_inp); hipFree(ctx->chain_pca);
   hipFree(ctx->sem_alpha); hipFree(ctx->sem); hipFree(ctx->sem_sums); hipFree(ctx->sem_col); hipFree(ctx->cnt_plane);
   emap_comm_destroy(ctx);

@@ -3,7 +3,8 @@
 // planes (:115-144), connected labels (:147-150), one plane per label (:165-220) and the verdict of isGloballyPlanar (:277-300) -- on
 // one layer of the published map, which the reference's node downloads as a GridMap for it.  One chain of launches up to the numbering,
 // an 8-byte copy of the label and slot counts and a wait; the slot buffer is sized by that count (a checkerboard has M * M / 2 labels
-// and no slot); moments, planes and final labels, the copies and a second wait.  Every buffer belongs to the context.
+// and no slot); moments, planes and final labels, the copies and a second wait.  Every buffer belongs to the context.  The chain has two
+// halves, planeseg_source and planeseg_segment (behind the entry point): emap_planar_terrain segments a preprocessed plane with the second.
 #include "emap_host.h"
 #include <cmath>
 #include <cstddef>
@@ -48,33 +49,53 @@ int emap_plane_segmentation(emap_ctx* ctx, const emap_grid_layer_ex* source, con
   CKARG(ctx->strip.halo_rows == 0 && ctx->strip.row_count == ctx->prm.cell_n, w + "single-strip contexts only");
   { const int rc = check_layer_entry(ctx, w, source->kind, source->index, source->flags, true); if (rc) return rc; }
 
+  SF_CHECK();
+  CK(hipSetDevice(ctx->device));
+  FLUSH();
+  PlaneArgs A; PlaneBufs B;
+  { const int rc = planeseg_source(ctx, *source, p, &A, &B); if (rc) return rc; }
+  return planeseg_segment(ctx, w, p, A, B, host_labels, host_normals, host_planes, capacity_planes, n_labels, n_planes);
+}
+
+}  // extern "C"
+
+// ---- the two halves of the chain (also behind emap_planar_terrain, emap_api_terrain.hip, which segments a preprocessed plane) ----------------
+namespace emap_host {
+// the context's buffers, grown and carved (*B), the call's constants (*A) and the source layer as a dense M x M plane in B->src
+int planeseg_source(emap_ctx* ctx, const emap_grid_layer_ex& source, const emap_plane_params& p, PlaneArgs* Aout, PlaneBufs* Bout) {
   const int M = ctx->prm.cell_n - 2;
   const size_t N = (size_t)M * M, W = (N + 31) / 32, Wp = (W + EM_CLOUD_SCAN_TRIP - 1) / EM_CLOUD_SCAN_TRIP * EM_CLOUD_SCAN_TRIP;
   // the device buffer: [head words] [src] [nrm x 3] [parent] [root] [cnt] [amin] [mask1] [offs1] [mask2] [offs2] [bit] [bit2]
   const size_t o_src = 16, o_nrm = o_src + up16(4 * N), o_par = o_nrm + up16(12 * N), o_root = o_par + up16(4 * N), o_cnt = o_root + up16(4 * N),
                o_amin = o_cnt + up16(4 * N), o_m1 = o_amin + up16(4 * N), o_o1 = o_m1 + 4 * Wp, o_m2 = o_o1 + 4 * Wp, o_o2 = o_m2 + 4 * Wp,
                o_bit = o_o2 + 4 * Wp, o_bit2 = o_bit + up16(N), dev_bytes = o_bit2 + up16(N);
-  PlaneArgs A; memset(&A, 0, sizeof A);
+  PlaneArgs& A = *Aout; memset(&A, 0, sizeof A);
   A.M = M; A.K = p.kernel_size; A.conn = p.connectivity; A.open_r = p.planarity_opening_filter;
   A.min_points = p.min_number_points_per_label > 3 ? p.min_number_points_per_label : 3;      // (:193)
   A.res = p.resolution; A.thr2 = p.plane_patch_error_threshold * p.plane_patch_error_threshold;      // (:108)
   A.cos_local = p.cos_local_plane_inclination; A.cos_plane = p.cos_plane_inclination; A.ox = p.origin_x; A.oy = p.origin_y;
 
-  SF_CHECK();
-  CK(hipSetDevice(ctx->device));
-  FLUSH();
   { const int rc = grow(ctx, &ctx->pseg_buf, &ctx->pseg_cap, dev_bytes); if (rc) return rc; }
   { const int rc = grow(ctx, &ctx->pseg_pin, &ctx->pseg_pin_cap, (size_t)16, Grow::pinned); if (rc) return rc; }      // (every call ends with a wait: no DMA of the pinned buffer is in flight here)
   unsigned char* d = ctx->pseg_buf;
-  PlaneBufs B;
+  PlaneBufs& B = *Bout;
   B.head = reinterpret_cast<unsigned int*>(d); B.src = reinterpret_cast<float*>(d + o_src); B.nrm = reinterpret_cast<float*>(d + o_nrm);
   B.parent = reinterpret_cast<int*>(d + o_par); B.root = reinterpret_cast<int*>(d + o_root); B.cnt = reinterpret_cast<int*>(d + o_cnt);
   B.amin = reinterpret_cast<int*>(d + o_amin); B.mask1 = reinterpret_cast<unsigned int*>(d + o_m1); B.offs1 = reinterpret_cast<unsigned int*>(d + o_o1);
   B.mask2 = reinterpret_cast<unsigned int*>(d + o_m2); B.offs2 = reinterpret_cast<unsigned int*>(d + o_o2); B.bit = d + o_bit; B.bit2 = d + o_bit2;
   LayerTab tab = tab_init(ctx, p.center_z, p.use_only_above_for_upper_bound);
-  tab_put(tab, source->kind, source->index, source->flags);
+  tab_put(tab, source.kind, source.index, source.flags);
   tab_finish(tab);
   launch_ps_source(ctx->stream, ctx->kp, ctx->cells, tab, B.src);
+  return EMAP_OK;
+}
+
+// the planes of B.src (M x M floats on the device, wherever they lie) segmented: window planes, labels, one plane per label; the labels
+// stay in B.parent, the normals in B.nrm
+int planeseg_segment(emap_ctx* ctx, const std::string& w, const emap_plane_params& p, const PlaneArgs& A, const PlaneBufs& B, int32_t* host_labels, float* host_normals,
+                     emap_plane_record* host_planes, int64_t capacity_planes, int32_t* n_labels, int64_t* n_planes) {
+  const int M = A.M;
+  const size_t N = (size_t)M * M, W = (N + 31) / 32;
   launch_ps_window(ctx->stream, A, B);
   if (A.open_r > 0) {                                           // MORPH_OPEN: erode, then dilate (:137-143)
     launch_ps_morph(ctx->stream, M, A.open_r, 0, B.bit, B.bit2);
@@ -117,5 +138,4 @@ int emap_plane_segmentation(emap_ctx* ctx, const emap_grid_layer_ex* source, con
   }
   return EMAP_OK;
 }
-
-}  // extern "C"
+}  // namespace emap_host

@@ -203,6 +203,10 @@ struct emap_ctx {
   // first wait -- and the pinned buffer the head words and the slots land in; all grown on demand, no allocation per call
   unsigned char* pseg_buf; size_t pseg_cap; unsigned char* pseg_pin; size_t pseg_pin_cap;      // bytes
   PlaneSlot* pseg_slots; size_t pseg_slots_cap;               // slots
+  // planar terrain on the device (emap_api_terrain.hip): ONE device buffer -- the uploaded tables (TerrainTab, emap_launch.h), the float
+  // planes of the pre- and postprocessing and the links, roots and keys of the NaN components -- and the pinned buffer the tables are
+  // built in; both grown on demand, no allocation per call
+  unsigned char* terr_buf; size_t terr_cap; unsigned char* terr_pin; size_t terr_pin_cap;      // bytes
   // frame state
   bool use_override; double sum_override; unsigned int cnt_override;
   bool committed;
@@ -272,6 +276,11 @@ int halo_exchange_start(emap_ctx* ctx);
 int normal_exchange(emap_ctx* ctx);
 bool rays_by_ray(const emap_ctx* ctx);
 int rays_by_ray_pass(emap_ctx* ctx, const float R[9], const float t[3], const Frame* f);
+// emap_api_planeseg.hip: the two halves of emap_plane_segmentation -- the source layer as a dense plane in the context's buffers (grown
+// and carved: *B, the call's constants: *A), and the segmentation of the M x M floats B.src points to (two waits; `who` ends in ": ")
+int planeseg_source(emap_ctx* ctx, const emap_grid_layer_ex& source, const emap_plane_params& p, PlaneArgs* A, PlaneBufs* B);
+int planeseg_segment(emap_ctx* ctx, const std::string& who, const emap_plane_params& p, const PlaneArgs& A, const PlaneBufs& B, int32_t* host_labels, float* host_normals,
+                     emap_plane_record* host_planes, int64_t capacity_planes, int32_t* n_labels, int64_t* n_planes);
 // emap_api_depth.hip: the next slot of cloud_stage and the owned cloud (tot floats) of the doors that produce their cloud
 int owned_cloud_prepare(emap_ctx* ctx, size_t pin_bytes, size_t dev_bytes, long tot);
 

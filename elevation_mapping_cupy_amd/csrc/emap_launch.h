@@ -255,3 +255,29 @@ void launch_ps_morph(hipStream_t, int M, int radius, int dilate, const unsigned 
 void launch_ps_labels(hipStream_t, const PlaneArgs&, const PlaneBufs&, const unsigned char* bit);
 void launch_ps_moments(hipStream_t, const PlaneArgs&, const PlaneBufs&, PlaneSlot* slots);
 void launch_ps_planes(hipStream_t, const PlaneArgs&, const PlaneBufs&, PlaneSlot* slots, int n_slots, int* labels);
+// k_ps_local / k_ps_merge / k_ps_flatten alone: the root of every set cell of a byte plane (root[]: -1 where the byte is 0), cnt[] zeroed and
+// amin[] at 0x7fffffff for every cell, mask1 the "is a root" bits.  launch_ps_labels starts with it; the planar terrain (below) labels its
+// NaN cells with it.
+void launch_ps_components(hipStream_t, int M, int conn, const unsigned char* bit, int* parent, int* root, int* cnt, int* amin, unsigned int* mask1);
+
+// Planar terrain on the device (emap_terrain.hip): what convex_plane_decomposition publishes around the segmentation -- the preprocessing
+// of GridMapPreprocessing::preprocess (minValues inpainting, median) in front of it, Postprocessing::postprocess (smooth_planar, the
+// dilated and lifted elevation) behind it.  Every plane is dense M x M in published index space, as above.
+// TerrainTab: the call's small tables, built on the host and uploaded -- close / lift: the row spans of OpenCV's elliptic structuring
+// element of the closing (size kd) and of the dilation in non-planar regions (row a covers the columns [lo[a], hi[a])); off: the sloped
+// dilation's kd x kd height offsets; gauss: the Gaussian's taps.  A float's monotone KEY (tr_key) is an int whose signed order is the
+// numeric order, -0 below +0: every minimum, maximum and order statistic of the chain is taken on keys, so it is a function of the bits.
+#define EM_TERRAIN_KERNEL_MAX 31      /* every kernel size of the chain, in cells (a cap: the LDS tile holds a halo of 15) */
+#define EM_TERRAIN_OFFSET_MAX 15      /* nonplanar_horizontal_offset: a dilation of 2 * 15 + 1 cells */
+#define EM_TERRAIN_REPEATS_MAX 8      /* median passes (a cap, not a measurement) */
+struct TerrainSpans { signed char lo[EM_TERRAIN_KERNEL_MAX + 1], hi[EM_TERRAIN_KERNEL_MAX + 1]; };
+struct TerrainTab { TerrainSpans close, lift; float gauss[EM_TERRAIN_KERNEL_MAX + 1]; float off[EM_TERRAIN_KERNEL_MAX * EM_TERRAIN_KERNEL_MAX + 3]; };
+void launch_tr_nanbit(hipStream_t, long N, const float* in, unsigned char* bit);
+void launch_tr_rim(hipStream_t, int M, const float* in, const unsigned char* bit, const int* root, int* amin);
+void launch_tr_fill(hipStream_t, long N, const float* in, const unsigned char* bit, const int* root, const int* amin, float* out);
+void launch_tr_median(hipStream_t, int M, int k, const float* in, float* out);
+void launch_tr_mask(hipStream_t, long N, const float* e, const int* labels, float* w, float* m, unsigned char* bit);
+void launch_tr_morph(hipStream_t, int M, int kd, int dilate, const TerrainSpans* spans, const float* in, float* out);
+void launch_tr_sloped(hipStream_t, int M, int kd, const float* off, const float* in, float* out);
+void launch_tr_blur(hipStream_t, int M, int k, const float* taps, double scale, const float* in, float* out);
+void launch_tr_lift(hipStream_t, long N, const float* e, const float* d, const float* m, int add_on, float add, int sub_on, float sub, float* out);

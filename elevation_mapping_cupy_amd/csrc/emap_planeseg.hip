@@ -454,13 +454,18 @@ void launch_ps_window(hipStream_t s, const PlaneArgs& A, const PlaneBufs& B) {
 void launch_ps_morph(hipStream_t s, int M, int radius, int dilate, const unsigned char* in, unsigned char* out) {
   hipLaunchKernelGGL(k_ps_morph, dim3(ps_blocks((long)M * M)), dim3(EM_BLOCK), 0, s, M, radius, dilate, in, out);
 }
-// local pass, border merge, flatten + root bits, member counts, slot bits: parent, root, cnt, amin, mask1, mask2 are written
-void launch_ps_labels(hipStream_t s, const PlaneArgs& A, const PlaneBufs& B, const unsigned char* bit) {
-  const int M = A.M, nt = (M + T - 1) / T;
+// local pass, border merge, flatten + root bits (launch_ps_components: also the planar terrain's NaN components, emap_terrain.hip), then
+// member counts, slot bits: parent, root, cnt, amin, mask1, mask2 are written
+void launch_ps_components(hipStream_t s, int M, int conn, const unsigned char* bit, int* parent, int* root, int* cnt, int* amin, unsigned int* mask1) {
+  const int nt = (M + T - 1) / T;
   const long N = (long)M * M;
-  hipLaunchKernelGGL(k_ps_local, dim3(nt * nt), dim3(EM_BLOCK), 0, s, M, A.conn, bit, B.parent, B.cnt, B.amin);
-  if (nt > 1) hipLaunchKernelGGL(k_ps_merge, dim3(ps_blocks(N)), dim3(EM_BLOCK), 0, s, M, A.conn, bit, B.parent);
-  hipLaunchKernelGGL(k_ps_flatten, dim3(ps_blocks(N)), dim3(EM_BLOCK), 0, s, N, B.parent, B.root, B.mask1);
+  hipLaunchKernelGGL(k_ps_local, dim3(nt * nt), dim3(EM_BLOCK), 0, s, M, conn, bit, parent, cnt, amin);
+  if (nt > 1) hipLaunchKernelGGL(k_ps_merge, dim3(ps_blocks(N)), dim3(EM_BLOCK), 0, s, M, conn, bit, parent);
+  hipLaunchKernelGGL(k_ps_flatten, dim3(ps_blocks(N)), dim3(EM_BLOCK), 0, s, N, parent, root, mask1);
+}
+void launch_ps_labels(hipStream_t s, const PlaneArgs& A, const PlaneBufs& B, const unsigned char* bit) {
+  const long N = (long)A.M * A.M;
+  launch_ps_components(s, A.M, A.conn, bit, B.parent, B.root, B.cnt, B.amin, B.mask1);
   hipLaunchKernelGGL(k_ps_count, dim3(ps_fold_blocks(N)), dim3(EM_BLOCK), 0, s, N, B.src, B.root, B.cnt, B.amin);
   hipLaunchKernelGGL(k_ps_bits2, dim3(ps_blocks(N)), dim3(EM_BLOCK), 0, s, N, A.min_points, B.root, B.cnt, B.mask2);
 }

@@ -527,6 +527,7 @@ class ElevationMap:
         self.last_submap_route = None               # "device" | "host": the route of the last submap call (EMAP_SUBMAP_RESIDENT)
         self.last_point_cloud_route = None          # "device" | "host": the route of the last point-cloud / arrow call (EMAP_CLOUD_RESIDENT)
         self.last_plane_segmentation_route = None   # "device" | "host": the route of the last get_plane_segmentation call (EMAP_PLANES_RESIDENT)
+        self.last_planar_terrain_route = None       # the same of the last get_planar_terrain call (EMAP_TERRAIN_RESIDENT)
         self._mask = self._mask_polygon = None      # safety-polygon service: the mask is built when it is read
         self.last_polygon_route = None              # "device" | "host": the route of the last safety check
         self.untraversable_polygon = None
@@ -1528,13 +1529,10 @@ class ElevationMap:
         (``plane_segmentation.segment``), the same answer; ``last_plane_segmentation_route`` tells which ran."""
         from . import plane_segmentation as host_model
         self._require_full_map("get_plane_segmentation")
-        kernel_size, opening, min_points, connectivity = int(kernel_size), int(planarity_opening_filter), int(min_number_points_per_label), int(connectivity)
-        if kernel_size not in (3, 5, 7) or connectivity not in (4, 8) or not 0 <= opening <= _lib.PLANE_OPEN_MAX or min_points < 0:
-            raise ValueError("kernel_size is 3, 5 or 7, connectivity 4 or 8, planarity_opening_filter 0 .. %d, min_number_points_per_label not negative" % _lib.PLANE_OPEN_MAX)
-        angles = [float(a) for a in (plane_inclination_threshold_degrees, local_plane_inclination_threshold_degrees, global_plane_fit_angle_error_threshold_degrees)]
-        lengths = [float(plane_patch_error_threshold), float(global_plane_fit_distance_error_threshold)]
-        if not all(np.isfinite(v) and v > 0.0 for v in angles + lengths) or any(a > 180.0 for a in angles):
-            raise ValueError("thresholds must be positive and finite (angles in degrees, at most 180)")
+        keywords, angles, lengths = self._plane_keywords(kernel_size, planarity_opening_filter, plane_inclination_threshold_degrees, local_plane_inclination_threshold_degrees,
+                                                         plane_patch_error_threshold, min_number_points_per_label, connectivity, global_plane_fit_distance_error_threshold,
+                                                         global_plane_fit_angle_error_threshold_degrees)
+        kernel_size, opening, min_points, connectivity = (keywords[k] for k in ("kernel_size", "planarity_opening_filter", "min_number_points_per_label", "connectivity"))
         M = self.cell_n - 2
         if out is None:
             out = np.empty((M, M), np.int32)
@@ -1542,9 +1540,6 @@ class ElevationMap:
             raise ValueError("out must be a writeable C-contiguous int32 array of shape (%d, %d)" % (M, M))
         xs, ys = self._cell_positions()
         origin, res = (float(xs[0]), float(ys[0])), float(np.float32(self.resolution))
-        keywords = dict(kernel_size=kernel_size, planarity_opening_filter=opening, plane_inclination_threshold_degrees=angles[0],
-                        local_plane_inclination_threshold_degrees=angles[1], plane_patch_error_threshold=lengths[0], min_number_points_per_label=min_points,
-                        connectivity=connectivity, global_plane_fit_distance_error_threshold=lengths[1], global_plane_fit_angle_error_threshold_degrees=angles[2])
         with self.map_lock:
             plan = self._grid_plan([layer], False)
             if len(plan) != 1:
@@ -1576,6 +1571,95 @@ class ElevationMap:
                 self._chk(rc)
                 break
         return types.SimpleNamespace(labels=out, n_labels=int(n_labels.value), planes=planes[:n_planes.value], normals=nrm, origin_xy=origin, resolution=res)
+
+    @staticmethod
+    def _plane_keywords(kernel_size, planarity_opening_filter, plane_inclination_threshold_degrees, local_plane_inclination_threshold_degrees, plane_patch_error_threshold,
+                        min_number_points_per_label, connectivity, global_plane_fit_distance_error_threshold, global_plane_fit_angle_error_threshold_degrees):
+        """the segmentation's keywords, converted and checked: ``(keywords for the host model, the three angles, the two lengths)``"""
+        kernel_size, opening, min_points, connectivity = int(kernel_size), int(planarity_opening_filter), int(min_number_points_per_label), int(connectivity)
+        if kernel_size not in (3, 5, 7) or connectivity not in (4, 8) or not 0 <= opening <= _lib.PLANE_OPEN_MAX or min_points < 0:
+            raise ValueError("kernel_size is 3, 5 or 7, connectivity 4 or 8, planarity_opening_filter 0 .. %d, min_number_points_per_label not negative" % _lib.PLANE_OPEN_MAX)
+        angles = [float(a) for a in (plane_inclination_threshold_degrees, local_plane_inclination_threshold_degrees, global_plane_fit_angle_error_threshold_degrees)]
+        lengths = [float(plane_patch_error_threshold), float(global_plane_fit_distance_error_threshold)]
+        if not all(np.isfinite(v) and v > 0.0 for v in angles + lengths) or any(a > 180.0 for a in angles):
+            raise ValueError("thresholds must be positive and finite (angles in degrees, at most 180)")
+        keywords = dict(kernel_size=kernel_size, planarity_opening_filter=opening, plane_inclination_threshold_degrees=angles[0],
+                        local_plane_inclination_threshold_degrees=angles[1], plane_patch_error_threshold=lengths[0], min_number_points_per_label=min_points,
+                        connectivity=connectivity, global_plane_fit_distance_error_threshold=lengths[1], global_plane_fit_angle_error_threshold_degrees=angles[2])
+        return keywords, angles, lengths
+
+    # ---- planar terrain (include/emap_hip.h: emap_planar_terrain) --------------------------------------------------------------------------
+    def get_planar_terrain(self, layer="elevation", *, preprocess=None, postprocess=None, intermediates=False, normals=False, kernel_size=3,
+                           planarity_opening_filter=0, plane_inclination_threshold_degrees=30.0, local_plane_inclination_threshold_degrees=35.0,
+                           plane_patch_error_threshold=0.02, min_number_points_per_label=4, connectivity=4, global_plane_fit_distance_error_threshold=0.025,
+                           global_plane_fit_angle_error_threshold_degrees=25.0):
+        """What convex_plane_decomposition publishes around ``get_plane_segmentation``, without the map leaving the device (DESIGN.md
+        section 22 holds the contract): optionally the preprocessing of the layer (``preprocess``: a dict with the reference's
+        ``kernelSize`` -- 3 --, ``numberOfRepeats`` -- 1 -- and optionally ``resolution``, which must be the map's; ``{}`` is the reference's
+        defaults, ``None`` runs neither the minValues inpainting nor the median), the segmentation of that plane with the keywords of
+        ``get_plane_segmentation``, and ``Postprocessing::postprocess`` (``postprocess``: a dict with the keys and defaults of
+        Postprocessing.h:7-25; ``None``: the defaults).  Returns ``get_plane_segmentation``'s namespace (``support[2]`` of the planes raised by
+        ``extracted_planes_height_offset``) plus float32 ``(M, M)`` planes: ``elevation`` (non-planar cells dilated, everything lifted),
+        ``smooth_planar``, ``plane_classification`` (1.0 / 0.0) and ``elevation_before_postprocess``; with ``intermediates=True`` also the
+        reference's helper layers ``elevationWithNaN``, ``elevationWithNaN_i``, ``elevationWithNaNClosed`` and
+        ``elevationWithNaNClosedDilated``.  Only the planes asked for are copied back.
+
+        ``layer`` as in ``get_plane_segmentation`` (a plugin layer that takes its host route is refused).  ``EMAP_TERRAIN_RESIDENT=0`` in
+        the environment: the layer is downloaded and everything is computed by the host model (``planar_terrain.terrain``), the same
+        answer; ``last_planar_terrain_route`` tells which ran."""
+        from . import plane_segmentation as seg_model
+        from . import planar_terrain as host_model
+        self._require_full_map("get_planar_terrain")
+        keywords, angles, lengths = self._plane_keywords(kernel_size, planarity_opening_filter, plane_inclination_threshold_degrees, local_plane_inclination_threshold_degrees,
+                                                         plane_patch_error_threshold, min_number_points_per_label, connectivity, global_plane_fit_distance_error_threshold,
+                                                         global_plane_fit_angle_error_threshold_degrees)
+        M = self.cell_n - 2
+        xs, ys = self._cell_positions()
+        origin, res = (float(xs[0]), float(ys[0])), float(np.float32(self.resolution))
+        pre, post, _ = host_model.check(M, res, preprocess, postprocess)
+        names = host_model.PLANES[:8 if intermediates else 4]
+        with self.map_lock:
+            plan = self._grid_plan([layer], False)
+            if len(plan) != 1:
+                raise ValueError("layer %r is not a layer this map publishes" % (layer,))
+            resident = os.environ.get("EMAP_TERRAIN_RESIDENT", "1") != "0"
+            self.last_planar_terrain_route = "device" if resident else "host"
+            if not resident:
+                _, planes = self._grid_map_layers_locked([layer], None, "rows", False)
+                r = host_model.terrain(planes[0], res, origin, preprocess, post, **keywords)
+                out = types.SimpleNamespace(labels=r.labels, n_labels=r.n_labels, planes=r.planes, normals=r.normals if normals else None, origin_xy=origin, resolution=res)
+                for n in names:
+                    setattr(out, n, getattr(r, n))
+                return out
+            if self._any_host_plugin(plan):
+                raise ValueError("plugin layer %r takes its host route: it is not resident on the device (get_grid_map_layers computes it on the host)" % (layer,))
+            kind, index, _, flags = self._grid_plugins(plan, None)[0]
+            src = EmapGridLayerEx(int(kind), int(index), 0, int(flags))
+            cos_plane, cos_local, cos_angle = seg_model.cosines(*angles)
+            P = _lib.EmapPlaneParams(keywords["kernel_size"], keywords["planarity_opening_filter"], keywords["min_number_points_per_label"], keywords["connectivity"],
+                                     int(bool(self.param.use_only_above_for_upper_bound)), 0, float(self.center[2]), 0.0,
+                                     res, origin[0], origin[1], lengths[0], cos_local, cos_plane, lengths[1], cos_angle)
+            Q = _lib.EmapTerrainParams(0 if pre is None else 1, 1 if pre is None else pre[0], 0 if pre is None else pre[1], post["nonplanar_horizontal_offset"],
+                                       (1 << len(names)) - 1, 0, post["smoothing_dilation_size"], post["smoothing_box_kernel_size"], post["smoothing_gauss_kernel_size"],
+                                       post["extracted_planes_height_offset"], post["nonplanar_height_offset"])
+            labels = np.empty((M, M), np.int32)
+            got = {n: np.empty((M, M), np.float32) for n in names}
+            O = _lib.EmapTerrainPlanes()
+            for k, n in enumerate(names):
+                O.plane[k] = f32p(got[n])
+            nrm = np.empty((3, M, M), np.float32) if normals else None
+            capacity = 256
+            while True:                                 # (a second trip only when more than `capacity` labels have a plane)
+                planes = np.zeros(capacity, _lib.PLANE_RECORD_DTYPE)
+                n_labels, n_planes = ct.c_int32(0), ct.c_int64(0)
+                rc = self._lib.emap_planar_terrain(self._ctx, ct.byref(src), ct.byref(P), ct.byref(Q), labels.ctypes.data_as(ct.POINTER(ct.c_int32)), f32p(nrm) if normals else None,
+                                                   planes.ctypes.data_as(ct.POINTER(_lib.EmapPlaneRecord)), capacity, ct.byref(n_labels), ct.byref(n_planes), ct.byref(O))
+                if rc == -1 and n_planes.value > capacity:
+                    capacity = int(n_planes.value)
+                    continue
+                self._chk(rc)
+                break
+        return types.SimpleNamespace(labels=labels, n_labels=int(n_labels.value), planes=planes[:n_planes.value], normals=nrm, origin_xy=origin, resolution=res, **got)
 
     def get_grid_map_message(self, layers, basic_layers=None, frame_id="", stamp=None, normal_color=False, out=None):
         """A duck-typed ``grid_map_msgs/GridMap`` of ``layers`` (``types.SimpleNamespace``, no ROS import): ``info.resolution``,

@@ -345,6 +345,42 @@ typedef struct emap_plane_record { int32_t label, n_points, needs_refinement, n_
 int emap_plane_segmentation(emap_ctx* ctx, const emap_grid_layer_ex* source, const emap_plane_params* params, int32_t* host_labels,
                             float* host_normals, emap_plane_record* host_planes, int64_t capacity_planes, int32_t* n_labels,
                             int64_t* n_planes);
+/* Planar terrain: what convex_plane_decomposition publishes around that segmentation, on the device, as one chain of launches --
+ * GridMapPreprocessing::preprocess (GridMapPreprocessing.cpp:14-39) in front of it with terrain->preprocess = 1: minValues inpainting
+ * (grid_map_filters_rsl inpainting.cpp:25-94: every NaN cell gets the smallest value that is not NaN around its 4-connected NaN
+ * component) and a median (smoothing.cpp:23-42, cv::medianBlur: median_kernel_size is clamped to 1 .. 5 as :21 does, 1 is a no-op,
+ * median_repeats passes, BORDER_REPLICATE); and Postprocessing::postprocess (Postprocessing.cpp:14-31) behind it: smooth_planar
+ * (:73-144: the planar heights inpainted, closed with an ellipse, dilated with a slope of one cell height per cell, box mean,
+ * Gaussian; the three smoothing sizes are HALF widths in metres, a kernel is 2 * int(round(size / resolution)) + 1 cells), the
+ * elevation dilated in non-planar cells (:33-53, an ellipse of 2 * nonplanar_horizontal_offset + 1 cells, skipped at 0) and lifted
+ * (:55-65), and support[2] of every record raised by extracted_planes_height_offset (:65-71).  The resampling step, RANSAC, contours
+ * and convex regions are not part of it.  The contract -- minima, maxima and medians on the bits, the elliptic element, the SHIFTED
+ * window of the sloped dilation, the summation order of the two means, one quiet NaN -- is DESIGN.md section 22; OpenCV and grid_map
+ * are restated there, not pinned by a compiled reference.
+ * source, params, host_labels .. n_planes: as emap_plane_segmentation; with preprocess = 0 they receive exactly what that call gives
+ * (support[2] aside).  out->plane[k] receives plane k (M * M floats, cell (i, j) at i * M + j) if bit k of terrain->want is set and
+ * is not touched otherwise: EMAP_TERRAIN_ELEVATION (the post-processed elevation), _SMOOTH_PLANAR, _CLASSIFICATION (1.0 where the
+ * final label is not 0, else 0.0), _BEFORE (the elevation the segmentation read: preprocessed, or the source), and the reference's
+ * helper layers elevationWithNaN, elevationWithNaN_i, elevationWithNaNClosed, elevationWithNaNClosedDilated.
+ * Waits: the segmentation's two, and one behind the copies of the planes.  The buffers belong to the context and grow on demand.
+ * Refused with EMAP_ERR_INVALID before anything is launched or copied, every output and the map untouched: everything
+ * emap_plane_segmentation refuses; a NULL terrain or out; preprocess other than 0, 1; with preprocess an even median size after the
+ * clamp or median_repeats outside 0 .. EMAP_TERRAIN_REPEATS_MAX; nonplanar_horizontal_offset outside 0 .. EMAP_TERRAIN_OFFSET_MAX; a
+ * smoothing size that is negative or not finite; any kernel of more than EMAP_TERRAIN_KERNEL_MAX cells or more than M cells; a height
+ * offset that is not finite; an unknown bit in want, or a set bit whose pointer is NULL. */
+enum { EMAP_TERRAIN_KERNEL_MAX = 31, EMAP_TERRAIN_OFFSET_MAX = 15, EMAP_TERRAIN_REPEATS_MAX = 8, EMAP_TERRAIN_PLANES = 8 };
+enum { EMAP_TERRAIN_ELEVATION = 1, EMAP_TERRAIN_SMOOTH_PLANAR = 2, EMAP_TERRAIN_CLASSIFICATION = 4, EMAP_TERRAIN_BEFORE = 8,
+       EMAP_TERRAIN_WITH_NAN = 16, EMAP_TERRAIN_WITH_NAN_I = 32, EMAP_TERRAIN_CLOSED = 64, EMAP_TERRAIN_CLOSED_DILATED = 128,
+       EMAP_TERRAIN_ALL = 255 };
+typedef struct emap_terrain_params {
+  int32_t preprocess, median_kernel_size, median_repeats, nonplanar_horizontal_offset, want, reserved;
+  double smoothing_dilation_size, smoothing_box_kernel_size, smoothing_gauss_kernel_size, extracted_planes_height_offset,
+         nonplanar_height_offset;
+} emap_terrain_params;
+typedef struct emap_terrain_planes { float* plane[8]; } emap_terrain_planes;
+int emap_planar_terrain(emap_ctx* ctx, const emap_grid_layer_ex* source, const emap_plane_params* params,
+                        const emap_terrain_params* terrain, int32_t* host_labels, float* host_normals, emap_plane_record* host_planes,
+                        int64_t capacity_planes, int32_t* n_labels, int64_t* n_planes, const emap_terrain_planes* out);
 /* ElevationMap.shift_map_xy / shift_map_z (EM/elevation_mapping.py:200-226): roll by (dx rows, dy cols) with
  * padding (0; variance plane initial_variance), planes 0 and 5 += dz -- as a rotation of the map's circular origin plus a pending
  * entry that later kernels replay: no cell is moved, only the entering band of the semantic layers is cleared.  Works on strips
