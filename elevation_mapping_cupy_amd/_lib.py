@@ -126,6 +126,19 @@ TERRAIN_PLANES = ("elevation", "smooth_planar", "plane_classification", "elevati
                   "elevationWithNaN", "elevationWithNaN_i", "elevationWithNaNClosed", "elevationWithNaNClosedDilated")
 
 
+class EmapRegionParams(ct.Structure):
+    """struct emap_region_params (include/emap_hip.h: emap_planar_regions)."""
+    _fields_ = [("mode", ct.c_int32), ("margin_size", ct.c_int32), ("reserved", ct.c_int32 * 2)]
+
+
+class EmapRegionRing(ct.Structure):
+    """struct emap_region_ring (include/emap_hip.h: emap_planar_regions)."""
+    _fields_ = [(n, ct.c_int32) for n in ("first_vertex", "n_vertices", "image", "is_hole", "label", "root", "crack", "boundary")]
+
+
+REGION_MARGIN_MAX, REGION_SIDE_MAX, REGION_RAW_SIDE_MAX = 14, 7724, 23170      # EMAP_REGION_MARGIN_MAX / _SIDE_MAX / _RAW_SIDE_MAX (caps)
+
+
 class EmapPluginOp(ct.Structure):
     """struct emap_plugin_op (include/emap_hip.h: emap_plugin_chain)."""
     _fields_ = [(n, ct.c_int32) for n in ("type", "dst_plane", "src_kind", "src_index", "i0", "i1", "flags")] + [("f0", ct.c_float)]
@@ -174,7 +187,7 @@ SYMBOLS = [
     "emap_set_drift_inputs", "emap_drift_sums_to_device", "emap_set_drift_inputs_device",
     "emap_local_drift_sums", "emap_set_scatter_mode", "emap_fuse", "emap_fuse_average", "emap_commit", "emap_rays", "emap_average", "emap_overlap_clear",
     "emap_dilate", "emap_traversability_normals", "emap_post", "emap_post_part", "emap_update_variance", "emap_update_time", "emap_get_stats",
-    "emap_get_layer", "emap_set_layer", "emap_publish_layer", "emap_publish_grid_map", "emap_publish_grid_map_ex", "emap_publish_grid_windows", "emap_publish_point_cloud", "emap_plane_segmentation", "emap_planar_terrain", "emap_shift", "emap_strip_logical_begin", "emap_semantic_configure", "emap_semantic_update", "emap_frame_semantics",
+    "emap_get_layer", "emap_set_layer", "emap_publish_layer", "emap_publish_grid_map", "emap_publish_grid_map_ex", "emap_publish_grid_windows", "emap_publish_point_cloud", "emap_plane_segmentation", "emap_planar_terrain", "emap_planar_regions", "emap_shift", "emap_strip_logical_begin", "emap_semantic_configure", "emap_semantic_update", "emap_frame_semantics",
     "emap_semantic_get_layer", "emap_semantic_set_layer", "emap_semantic_clear", "emap_semantic_get_alpha", "emap_semantic_set_alpha", "emap_semantic_class_max", "emap_semantic_accumulate", "emap_semantic_finalize", "emap_min_filter", "emap_max_filter", "emap_smooth_filter", "emap_erode", "emap_plugin_planes", "emap_plugin_plane_write", "emap_plugin_plane_read", "emap_plugin_chain", "emap_plugin_chain_ex", "emap_inpaint_u8", "emap_inpaint_telea_u8", "emap_inpaint_ns_u8", "emap_inpainter_create", "emap_inpainter_destroy", "emap_inpainter_set_steps", "emap_inpaint_telea_fronts_u8", "emap_image_correspondence", "emap_image_get_correspondence",
     "emap_image_fuse", "emap_image_set_tolerance", "emap_image_fuse_arrays", "emap_input_image_message", "emap_polygon_mask", "emap_polygon_safety", "emap_dilate_planes", "emap_halo_bytes", "emap_halo_pack", "emap_halo_unpack", "emap_normal_row_lag", "emap_normal_halo_pack", "emap_normal_halo_unpack", "emap_normal_lag_plan",
     "emap_comm_unique_id", "emap_comm_init", "emap_comm_destroy", "emap_comm_selftest", "emap_comm_count", "emap_comm_wire_bytes", "emap_comm_allreduce_host", "emap_comm_gather_layer", "emap_update_sharded", "emap_set_ray_mode",
@@ -254,6 +267,9 @@ def load():
         lib.emap_planar_terrain.argtypes = [ct.c_void_p, ct.POINTER(EmapGridLayerEx), ct.POINTER(EmapPlaneParams), ct.POINTER(EmapTerrainParams), ct.POINTER(ct.c_int32),
                                             ct.POINTER(ct.c_float), ct.POINTER(EmapPlaneRecord), ct.c_int64, ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int64),
                                             ct.POINTER(EmapTerrainPlanes)]
+    if hasattr(lib, "emap_planar_regions"):
+        lib.emap_planar_regions.argtypes = [ct.c_void_p, ct.POINTER(ct.c_int32), ct.c_int32, ct.c_int32, ct.POINTER(EmapRegionParams), ct.POINTER(EmapRegionRing), ct.c_int64,
+                                            ct.POINTER(ct.c_int32), ct.c_int64, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64)]
     got = int(lib.emap_abi_version())
     if got != ABI_VERSION and not os.environ.get("EMAP_HIP_LIB"):
         raise EmapError("%s speaks ABI version %d, this binding expects %d (include/emap_hip.h: EMAP_ABI_VERSION) -- rebuild with "

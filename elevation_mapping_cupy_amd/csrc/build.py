@@ -16,7 +16,7 @@ SOURCES = ["emap_kernels.hip", "emap_binned.hip", "emap_semantic.hip", "emap_api
            "emap_inpaint_host.hip", "emap_inpaint_ns.cpp", "emap_inpaint_fronts.hip", "emap_inpaint_chain.hip",
            "emap_polysafe.hip", "emap_api_polysafe.hip", "emap_submap.hip", "emap_api_submap.hip",
            "emap_cloudout.hip", "emap_api_cloudout.hip", "emap_planeseg.hip", "emap_api_planeseg.hip",
-           "emap_terrain.hip", "emap_api_terrain.hip"]      # (.cpp: host-only C++)
+           "emap_terrain.hip", "emap_api_terrain.hip", "emap_regions.hip", "emap_api_regions.hip"]      # (.cpp: host-only C++)
 HEADERS = ["emap_device.h", "emap_launch.h", "emap_publish_tile.h", "emap_bin_hist.h", "emap_post_tile.h", "emap_camera.h", "emap_polygon.h", "emap_host.h", os.path.join("..", "..", "include", "emap_hip.h")]
 DEPS = SOURCES + HEADERS
 MAX_WORKERS = 16      # compilers at once: one per source, but never more than the CPUs a build may use

@@ -329,6 +329,7 @@ int emap_destroy(emap_ctx* ctx) {
   hipFree(ctx->cloud_tab); hipFree(ctx->cloud_out); if (ctx->cloud_pin) hipHostFree(ctx->cloud_pin);
   hipFree(ctx->pseg_buf); hipFree(ctx->pseg_slots); if (ctx->pseg_pin) hipHostFree(ctx->pseg_pin);
   hipFree(ctx->terr_buf); if (ctx->terr_pin) hipHostFree(ctx->terr_pin);
+  hipFree(ctx->reg_buf); hipFree(ctx->reg_cracks); if (ctx->reg_pin) hipHostFree(ctx->reg_pin);
   hipFree(ctx->plane_buf); hipFree(ctx->chain_buf); hipFree(ctx->chain_cnt); hipFree(ctx->chain_red); hipFree(ctx->chain_inp); hipFree(ctx->chain_pca);
   hipFree(ctx->sem_alpha); hipFree(ctx->sem); hipFree(ctx->sem_sums); hipFree(ctx->sem_col); hipFree(ctx->cnt_plane);
   emap_comm_destroy(ctx);
@@ -344,6 +345,7 @@ int emap_destroy(emap_ctx* ctx) {
 int emap_clear(emap_ctx* ctx) {
   CKARG(ctx, "null ctx"); SF_CHECK();
   CK(hipSetDevice(ctx->device));
+  ctx->pseg_labels = nullptr;                                  // the labels of the last segmentation are not this map's any more
   // ElevationMap.clear (elevation_mapping.py:119-128): all planes 0, variance = initial_variance
   Cell z = {0.f, (float)ctx->prm.initial_variance, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   launch_fill_cells(ctx->stream, ctx->cells, ctx->ncells_alloc, z);
@@ -1177,6 +1179,7 @@ int emap_shift(emap_ctx* ctx, int32_t shift_rows, int32_t shift_cols, float dz) 
   const int C = ctx->prm.cell_n;
   CKARG(shift_rows > -(1 << 20) && shift_rows < (1 << 20) && shift_cols > -(1 << 20) && shift_cols < (1 << 20), "absurd shift");   // (a shift of cell_n or more resets every cell: the replay predicate covers it)
   if (shift_rows == 0 && shift_cols == 0 && dz == 0.f) return EMAP_OK;
+  ctx->pseg_labels = nullptr;                                  // (as emap_clear)
   if (ctx->kp.mv.n == EM_MAX_MOVES) FLUSH();       // more moves than the replay list holds before the next frame: one full pass
   KP& k = ctx->kp;
   k.org_r = ((k.org_r - shift_rows) % C + C) % C;   // roll: new logical r holds old logical r - shift  =>  physical = r - shift + org

@@ -75,6 +75,7 @@ int planeseg_source(emap_ctx* ctx, const emap_grid_layer_ex& source, const emap_
   A.res = p.resolution; A.thr2 = p.plane_patch_error_threshold * p.plane_patch_error_threshold;      // (:108)
   A.cos_local = p.cos_local_plane_inclination; A.cos_plane = p.cos_plane_inclination; A.ox = p.origin_x; A.oy = p.origin_y;
 
+  ctx->pseg_labels = nullptr;                                  // the buffer is carved again: the labels of the call before are gone (emap_planar_regions)
   { const int rc = grow(ctx, &ctx->pseg_buf, &ctx->pseg_cap, dev_bytes); if (rc) return rc; }
   { const int rc = grow(ctx, &ctx->pseg_pin, &ctx->pseg_pin_cap, (size_t)16, Grow::pinned); if (rc) return rc; }      // (every call ends with a wait: no DMA of the pinned buffer is in flight here)
   unsigned char* d = ctx->pseg_buf;
@@ -122,6 +123,7 @@ int planeseg_segment(emap_ctx* ctx, const std::string& w, const emap_plane_param
   CK(hipMemcpyAsync(host_labels, B.parent, 4 * N, hipMemcpyDeviceToHost, ctx->stream));
   if (host_normals) CK(hipMemcpyAsync(host_normals, B.nrm, 12 * N, hipMemcpyDeviceToHost, ctx->stream));
   CK(hipStreamSynchronize(ctx->stream));
+  ctx->pseg_labels = B.parent; ctx->pseg_n_labels = (int)head[0];      // the final labels are in place (emap_planar_regions reads them there)
 
   int64_t accepted = 0;
   for (size_t k = 0; k < n_slots; ++k) { PlaneSlot s; memcpy(&s, ctx->pseg_pin + 16 + k * sizeof(PlaneSlot), sizeof s); accepted += s.accept ? 1 : 0; }

@@ -26,17 +26,7 @@ int kernel_cells(double size, double res) {
   const double r = std::round(size / res);
   return r > (double)EM_TERRAIN_KERNEL_MAX ? 0 : 2 * (int)r + 1;
 }
-// getStructuringElement(MORPH_ELLIPSE, (k, k)): row a covers the columns [lo[a], hi[a])
-void ellipse_spans(int k, TerrainSpans* sp) {
-  memset(sp, 0, sizeof *sp);
-  const int r = k / 2, c = k / 2;
-  for (int a = 0; a < k; ++a) {
-    const int dy = a - r;
-    const int dx = r ? (int)std::rint((double)c * std::sqrt((double)(r * r - dy * dy) / (double)(r * r))) : 0;
-    sp->lo[a] = (signed char)(c - dx > 0 ? c - dx : 0);
-    sp->hi[a] = (signed char)(c + dx + 1 < k ? c + dx + 1 : k);
-  }
-}
+// (ellipse_spans, getStructuringElement(MORPH_ELLIPSE, (k, k)): emap_host.h -- the planar regions erode with the same element)
 // getGaussianKernel(k, 0) rounded to float: the fixed tables up to 7, else sigma = 0.3 ((k - 1) / 2 - 1) + 0.8, normalised in double
 void gauss_taps(int k, float* t) {
   static const float small[4][7] = {{1.f}, {0.25f, 0.5f, 0.25f}, {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f}, {0.03125f, 0.109375f, 0.21875f, 0.28125f, 0.21875f, 0.109375f, 0.03125f}};

@@ -8,6 +8,7 @@
 #pragma once
 #include "emap_launch.h"
 #include "../../include/emap_hip.h"
+#include <cmath>
 #include <condition_variable>
 #include <cstring>
 #include <functional>
@@ -207,6 +208,13 @@ struct emap_ctx {
   // planes of the pre- and postprocessing and the links, roots and keys of the NaN components -- and the pinned buffer the tables are
   // built in; both grown on demand, no allocation per call
   unsigned char* terr_buf; size_t terr_cap; unsigned char* terr_pin; size_t terr_pin_cap;      // bytes
+  // planar regions on the device (emap_api_regions.hip): the buffer sized by the pixels of the traced images (RegionBufs, emap_launch.h),
+  // the buffer sized by the cracks -- known after the first wait -- (RegionCracks) and the pinned buffer the counts land in; all grown on
+  // demand, no allocation per call.  The call reads the labels of the last segmentation where they lie: pseg_labels points into
+  // pseg_buf (PlaneBufs::parent, M x M, pseg_n_labels components) and is valid from the moment planeseg_segment has the final labels in
+  // place until the buffer is carved again (planeseg_source), the map is cleared or it is shifted; nullptr: no valid labels
+  unsigned char* reg_buf; size_t reg_cap; unsigned char* reg_cracks; size_t reg_cracks_cap; unsigned char* reg_pin; size_t reg_pin_cap;      // bytes
+  const int* pseg_labels; int pseg_n_labels;
   // frame state
   bool use_override; double sum_override; unsigned int cnt_override;
   bool committed;
@@ -281,6 +289,18 @@ int rays_by_ray_pass(emap_ctx* ctx, const float R[9], const float t[3], const Fr
 int planeseg_source(emap_ctx* ctx, const emap_grid_layer_ex& source, const emap_plane_params& p, PlaneArgs* A, PlaneBufs* B);
 int planeseg_segment(emap_ctx* ctx, const std::string& who, const emap_plane_params& p, const PlaneArgs& A, const PlaneBufs& B, int32_t* host_labels, float* host_normals,
                      emap_plane_record* host_planes, int64_t capacity_planes, int32_t* n_labels, int64_t* n_planes);
+// getStructuringElement(MORPH_ELLIPSE, (k, k)), k odd and at most EM_TERRAIN_KERNEL_MAX: row a covers the columns [lo[a], hi[a]) -- the
+// element of the planar terrain's closing and dilation and of the planar regions' margin erosion
+inline void ellipse_spans(int k, TerrainSpans* sp) {
+  memset(sp, 0, sizeof *sp);
+  const int r = k / 2, c = k / 2;
+  for (int a = 0; a < k; ++a) {
+    const int dy = a - r;
+    const int dx = r ? (int)std::rint((double)c * std::sqrt((double)(r * r - dy * dy) / (double)(r * r))) : 0;
+    sp->lo[a] = (signed char)(c - dx > 0 ? c - dx : 0);
+    sp->hi[a] = (signed char)(c + dx + 1 < k ? c + dx + 1 : k);
+  }
+}
 // emap_api_depth.hip: the next slot of cloud_stage and the owned cloud (tot floats) of the doors that produce their cloud
 int owned_cloud_prepare(emap_ctx* ctx, size_t pin_bytes, size_t dev_bytes, long tot);
 

@@ -281,3 +281,33 @@ void launch_tr_morph(hipStream_t, int M, int kd, int dilate, const TerrainSpans*
 void launch_tr_sloped(hipStream_t, int M, int kd, const float* off, const float* in, float* out);
 void launch_tr_blur(hipStream_t, int M, int k, const float* taps, double scale, const float* in, float* out);
 void launch_tr_lift(hipStream_t, long N, const float* e, const float* d, const float* m, int add_on, float add, int sub_on, float sub, float* out);
+// k_ps_link (emap_planeseg.hip): element k of 0 .. n - 1 united with other[k] by the segmentation's union-find on global memory (the
+// invariant in that file's head: parent[k] == k before the launch, every access to parent[] an agent-scope atomic -- the workgroups of a
+// launch run on several XCDs whose L2s are not coherent for plain accesses --, the root of a set its smallest index whatever the order of
+// the atomics).  With a permutation in other[], the sets are its cycles: the planar regions (below) find their rings with it.
+void launch_ps_link(hipStream_t, int n, const int* other, int* parent);
+
+// Planar regions on the device (emap_regions.hip): the contour stage of convex_plane_decomposition on a label plane -- per connected piece
+// of a label a boundary polygon with holes and its insets.  RegionArgs: M the side of the label plane, U the side
+// of the traced images (3 M - 2, raw mode: M), k the margin ellipse's size in pixels, Wc the crack-mask words of ONE image
+// (ceil(U U / 8)).  RegionBufs: what is sized by the pixels -- labels: the label plane (raw mode: the U x U mask); em: per pixel bit 0
+// "survives the margin ellipse", bit 1 "survives the cross"; bm: the byte "in B_m"; flag: n_labels + 1 words "the label keeps its
+// margin", zeroed by the caller; A / B: the boundary and the inset image; bitA / bitB: their != 0 bytes; rootA / rootB: every pixel's
+// component root; cmask / coffs: 4 crack bits per pixel, A's words in front of B's, and their scan (k_cloud_scan's layout); head: [0]
+// cracks, [1] rings, [2] vertices.  RegionCracks: what is sized by the cracks, in COMPACT indices (the rank of the crack's bit) -- raw:
+// image << 31 | 4 idx + s; succ / pred: the permutation and its inverse; parent / cyc: the union-find links and every crack's ring (its
+// smallest crack); vbit: the crack emits a vertex; nv: the doubling's two buffers (next, vertices from here to the ring's end); hmask /
+// hoffs: the bit "is a ring's smallest crack" and its scan; rcnt / rfirst: per ring its vertices and their exclusive prefix; rings /
+// verts: the answer.  RegionRing: struct emap_region_ring (emap_hip.h; emap_api_regions.hip asserts the layout).
+#define EM_REGION_MARGIN_MAX 14      /* 2 (1 + 14) + 1 = EM_TERRAIN_KERNEL_MAX pixels */
+struct RegionArgs { int M, U, mode, k; long Wc; };
+struct RegionBufs { const int* labels; unsigned char* em; unsigned char* bm; unsigned int* flag; int* A; int* B; unsigned char* bitA; unsigned char* bitB;
+                    int* rootA; int* rootB; unsigned int* cmask; unsigned int* coffs; unsigned int* head; };
+struct RegionRing { int first_vertex, n_vertices, image, is_hole, label, root, crack, boundary; };
+struct RegionCracks { unsigned int* raw; int* succ; int* pred; int* parent; int* cyc; unsigned char* vbit; int2* nv[2]; unsigned int* hmask; unsigned int* hoffs;
+                      int* rcnt; int* rfirst; RegionRing* rings; int2* verts; };
+// ceil(log2 n) doubling rounds (at least 1): 2^rounds steps reach every crack of the longest possible ring
+static inline int region_rounds(int n) { int r = 1; while ((1L << r) < (long)n) ++r; return r; }
+void launch_rg_images(hipStream_t, const RegionArgs&, const TerrainSpans&, const RegionBufs&);
+void launch_rg_cracks(hipStream_t, const RegionArgs&, const RegionBufs&);
+void launch_rg_trace(hipStream_t, const RegionArgs&, const RegionBufs&, const RegionCracks&, int n_cracks);

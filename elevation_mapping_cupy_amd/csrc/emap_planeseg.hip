@@ -437,6 +437,12 @@ __global__ __launch_bounds__(EM_BLOCK) void k_ps_fold(PlaneArgs A, PlaneBufs B, 
   if (valid && ((todo >> lane) & 1)) { atomicMax(&slots[cur].kdist, kd); atomicMax(&slots[cur].kdot, kn); }
 }
 
+// ---- h. the same union-find on a list of pairs (k, other[k]): the cycles of a permutation (the planar regions' cracks, emap_regions.hip) ------
+__global__ __launch_bounds__(EM_BLOCK) void k_ps_link(int n, const int* __restrict__ other, int* parent) {
+  const int k = blockIdx.x * EM_BLOCK + threadIdx.x;
+  if (k < n) ps_union_agent(parent, k, other[k]);
+}
+
 // ---- launchers ---------------------------------------------------------------------------------------------------------------------------
 static inline unsigned int ps_blocks(long N) { return (unsigned int)((N + EM_BLOCK - 1) / EM_BLOCK); }
 static inline unsigned int ps_fold_blocks(long N) { return (unsigned int)((N + EM_BLOCK * PS_CPT - 1) / (EM_BLOCK * PS_CPT)); }
@@ -462,6 +468,9 @@ void launch_ps_components(hipStream_t s, int M, int conn, const unsigned char* b
   hipLaunchKernelGGL(k_ps_local, dim3(nt * nt), dim3(EM_BLOCK), 0, s, M, conn, bit, parent, cnt, amin);
   if (nt > 1) hipLaunchKernelGGL(k_ps_merge, dim3(ps_blocks(N)), dim3(EM_BLOCK), 0, s, M, conn, bit, parent);
   hipLaunchKernelGGL(k_ps_flatten, dim3(ps_blocks(N)), dim3(EM_BLOCK), 0, s, N, parent, root, mask1);
+}
+void launch_ps_link(hipStream_t s, int n, const int* other, int* parent) {
+  if (n > 0) hipLaunchKernelGGL(k_ps_link, dim3(ps_blocks(n)), dim3(EM_BLOCK), 0, s, n, other, parent);
 }
 void launch_ps_labels(hipStream_t s, const PlaneArgs& A, const PlaneBufs& B, const unsigned char* bit) {
   const long N = (long)A.M * A.M;

@@ -7,6 +7,7 @@ there is no CuPy, no PyTorch and no CPU compute fallback here.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as ct
 import os
 import threading
@@ -528,6 +529,7 @@ class ElevationMap:
         self.last_point_cloud_route = None          # "device" | "host": the route of the last point-cloud / arrow call (EMAP_CLOUD_RESIDENT)
         self.last_plane_segmentation_route = None   # "device" | "host": the route of the last get_plane_segmentation call (EMAP_PLANES_RESIDENT)
         self.last_planar_terrain_route = None       # the same of the last get_planar_terrain call (EMAP_TERRAIN_RESIDENT)
+        self.last_planar_regions_route = None       # the same of the contour stage of the last get_planar_regions / trace_mask call (EMAP_REGIONS_RESIDENT)
         self._mask = self._mask_polygon = None      # safety-polygon service: the mask is built when it is read
         self.last_polygon_route = None              # "device" | "host": the route of the last safety check
         self.untraversable_polygon = None
@@ -1592,7 +1594,7 @@ class ElevationMap:
     def get_planar_terrain(self, layer="elevation", *, preprocess=None, postprocess=None, intermediates=False, normals=False, kernel_size=3,
                            planarity_opening_filter=0, plane_inclination_threshold_degrees=30.0, local_plane_inclination_threshold_degrees=35.0,
                            plane_patch_error_threshold=0.02, min_number_points_per_label=4, connectivity=4, global_plane_fit_distance_error_threshold=0.025,
-                           global_plane_fit_angle_error_threshold_degrees=25.0):
+                           global_plane_fit_angle_error_threshold_degrees=25.0, _locked=False):
         """What convex_plane_decomposition publishes around ``get_plane_segmentation``, without the map leaving the device (DESIGN.md
         section 22 holds the contract): optionally the preprocessing of the layer (``preprocess``: a dict with the reference's
         ``kernelSize`` -- 3 --, ``numberOfRepeats`` -- 1 -- and optionally ``resolution``, which must be the map's; ``{}`` is the reference's
@@ -1606,7 +1608,7 @@ class ElevationMap:
 
         ``layer`` as in ``get_plane_segmentation`` (a plugin layer that takes its host route is refused).  ``EMAP_TERRAIN_RESIDENT=0`` in
         the environment: the layer is downloaded and everything is computed by the host model (``planar_terrain.terrain``), the same
-        answer; ``last_planar_terrain_route`` tells which ran."""
+        answer; ``last_planar_terrain_route`` tells which ran.  (``_locked``: the caller holds ``map_lock`` -- ``get_planar_regions``.)"""
         from . import plane_segmentation as seg_model
         from . import planar_terrain as host_model
         self._require_full_map("get_planar_terrain")
@@ -1618,7 +1620,7 @@ class ElevationMap:
         origin, res = (float(xs[0]), float(ys[0])), float(np.float32(self.resolution))
         pre, post, _ = host_model.check(M, res, preprocess, postprocess)
         names = host_model.PLANES[:8 if intermediates else 4]
-        with self.map_lock:
+        with (contextlib.nullcontext() if _locked else self.map_lock):
             plan = self._grid_plan([layer], False)
             if len(plan) != 1:
                 raise ValueError("layer %r is not a layer this map publishes" % (layer,))
@@ -1660,6 +1662,75 @@ class ElevationMap:
                 self._chk(rc)
                 break
         return types.SimpleNamespace(labels=labels, n_labels=int(n_labels.value), planes=planes[:n_planes.value], normals=nrm, origin_xy=origin, resolution=res, **got)
+
+    # ---- planar regions (include/emap_hip.h: emap_planar_regions) --------------------------------------------------------------------------
+    def get_planar_regions(self, layer="elevation", *, margin_size=1, **terrain_keywords):
+        """``get_planar_terrain`` and, behind it under the same lock, the contour stage of convex_plane_decomposition
+        (``ContourExtraction::extractPlanarRegions``) on the labels it left on the device (DESIGN.md section 23 holds the contract): per
+        connected piece of a label a boundary polygon with holes and its inset polygons, traced on the x 3 upsampled label image after an
+        erosion by ``margin_size`` (the reference's ``marginSize``, 0 .. 14).  ``terrain_keywords``: the keywords of ``get_planar_terrain``.
+        Returns that call's namespace plus ``rings`` (a structured array, ``planar_regions.RING_DTYPE``), ``vertices`` int32 ``(n, 2)``
+        (x = column, y = row of the upsampled image) and ``regions``: a list in ascending (label, first pixel), each a namespace of
+        ``label``, ``plane`` (the label's record), ``transform_plane_to_world`` (4 x 4 float64), ``boundary`` and ``insets`` (a polygon is
+        a dict of ``outer`` / ``holes`` in pixels and ``outer_plane`` / ``holes_plane`` in plane coordinates, float64) and ``bbox2d``.
+
+        ``EMAP_REGIONS_RESIDENT=0`` in the environment: the contour stage runs in the host model (``planar_regions.regions``) on the labels
+        the terrain call returned, the same answer; ``last_planar_regions_route`` tells which ran."""
+        from . import planar_regions as host_model
+        margin_size = int(margin_size)
+        if not 0 <= margin_size <= _lib.REGION_MARGIN_MAX:
+            raise ValueError("margin_size must lie in 0 .. %d" % _lib.REGION_MARGIN_MAX)
+        with self.map_lock:
+            r = self.get_planar_terrain(layer, _locked=True, **terrain_keywords)
+            resident = os.environ.get("EMAP_REGIONS_RESIDENT", "1") != "0"
+            self.last_planar_regions_route = "device" if resident else "host"
+            if resident and self.last_planar_terrain_route == "device":
+                r.rings, r.vertices = self._planar_regions_call(None, 0, 0, 0, margin_size)
+            elif resident:                              # the terrain took its host route: its labels are the caller's
+                r.rings, r.vertices = self._planar_regions_call(r.labels, r.labels.shape[0], r.n_labels, 0, margin_size)
+            else:
+                t = host_model.trace_labels(r.labels, r.n_labels, margin_size, 0)
+                r.rings, r.vertices = t.rings, t.vertices
+        r.regions = host_model.build_regions(r.rings, r.vertices, r.planes, r.resolution, r.origin_xy)
+        return r
+
+    def trace_mask(self, mask):
+        """The borders of a 0 / 1 mask at its own resolution, traced on the device as ``get_planar_regions`` traces its label images (the
+        raw mode of ``emap_planar_regions``): image 0 is the mask, image 1 its erosion by the 3 x 3 cross with the outer rows and columns
+        zeroed.  ``mask``: a square integer or bool array of at least 2 x 2.  Returns a namespace of ``rings`` and ``vertices`` as
+        ``get_planar_regions`` and ``polygons``: ``planar_regions.assemble`` of them."""
+        from . import planar_regions as host_model
+        self._require_full_map("trace_mask")
+        m = np.ascontiguousarray(mask, np.int32)
+        host_model.check_labels(m, 1, 0, 1)
+        with self.map_lock:
+            resident = os.environ.get("EMAP_REGIONS_RESIDENT", "1") != "0"
+            self.last_planar_regions_route = "device" if resident else "host"
+            if resident:
+                rings, vertices = self._planar_regions_call(m, m.shape[0], 1, 1, 0)
+            else:
+                t = host_model.trace_labels(m, 1, 0, 1)
+                rings, vertices = t.rings, t.vertices
+        return types.SimpleNamespace(rings=rings, vertices=vertices, polygons=host_model.assemble(rings, vertices))
+
+    def _planar_regions_call(self, labels, side, n_labels, mode, margin_size):
+        """``emap_planar_regions`` with buffers that fit: ``(rings, vertices)``; ``labels`` None: the resident labels"""
+        from . import planar_regions as host_model
+        self._require_full_map("get_planar_regions")
+        P = _lib.EmapRegionParams(int(mode), int(margin_size))
+        cap_r, cap_v = 256, 4096
+        while True:                                     # (a second trip only when the answer is larger than the buffers)
+            rings, verts = np.zeros(cap_r, host_model.RING_DTYPE), np.zeros((cap_v, 2), np.int32)
+            n_r, n_v = ct.c_int64(0), ct.c_int64(0)
+            rc = self._lib.emap_planar_regions(self._ctx, None if labels is None else labels.ctypes.data_as(ct.POINTER(ct.c_int32)), int(side), int(n_labels), ct.byref(P),
+                                               rings.ctypes.data_as(ct.POINTER(_lib.EmapRegionRing)), cap_r, verts.ctypes.data_as(ct.POINTER(ct.c_int32)), cap_v,
+                                               ct.byref(n_r), ct.byref(n_v))
+            if rc == -1 and (n_r.value > cap_r or n_v.value > cap_v):
+                cap_r, cap_v = max(cap_r, int(n_r.value)), max(cap_v, int(n_v.value))
+                continue
+            self._chk(rc)
+            break
+        return rings[:n_r.value].copy(), verts[:n_v.value].copy()
 
     def get_grid_map_message(self, layers, basic_layers=None, frame_id="", stamp=None, normal_color=False, out=None):
         """A duck-typed ``grid_map_msgs/GridMap`` of ``layers`` (``types.SimpleNamespace``, no ROS import): ``info.resolution``,

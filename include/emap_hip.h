@@ -381,6 +381,37 @@ typedef struct emap_terrain_planes { float* plane[8]; } emap_terrain_planes;
 int emap_planar_terrain(emap_ctx* ctx, const emap_grid_layer_ex* source, const emap_plane_params* params,
                         const emap_terrain_params* terrain, int32_t* host_labels, float* host_normals, emap_plane_record* host_planes,
                         int64_t capacity_planes, int32_t* n_labels, int64_t* n_planes, const emap_terrain_planes* out);
+/* Planar regions: the middle stage of the same pipeline, ContourExtraction::extractPlanarRegions (ContourExtraction.cpp:28-128), on
+ * the device -- per connected piece of a label a boundary polygon with holes and its inset polygons, traced on the x 3 upsampled label
+ * image (Upsampling.cpp:12-68; U = 3 * side - 2 pixels a side, never materialised on the host).  The answer is integer exact and a
+ * function of the label plane alone.  The contract -- the upsampling rule, the all-label erosions with the margin ellipse of
+ * 2 * (1 + margin_size) + 1 pixels and the 3 x 3 cross, the per-label fallback to the cross, 8-connected components, borders as cycles
+ * of CRACKS, the vertex rule of CHAIN_APPROX_SIMPLE, the order of the answer -- is DESIGN.md section 23; OpenCV's erode / findContours
+ * and CGAL's isInside are restated there, not pinned by a compiled reference.  RANSAC and convex region growing are not part of it.
+ * host_labels: side * side int32 in 0 .. n_labels (0: background), uploaded and used; or NULL: the labels the last
+ * emap_plane_segmentation / emap_planar_terrain left on this context (side must be 0 or cell_n - 2; n_labels is not read).
+ * params->mode 0: regions.  mode 1: host_labels is a mask of 0 and 1 traced as it is (U = side; A is the mask, B its cross erosion with
+ * the frame zeroed; margin_size is not read).
+ * A crack is (pixel p, side s) with the index 4 * (row * U + column) + s: side 0 the top edge travelled west, 1 the left edge travelled
+ * south, 2 the bottom edge travelled east, 3 the right edge travelled north.  host_rings: one record per border (ring), image 0 (the
+ * boundaries, A) before image 1 (the insets, B), in ascending smallest crack within an image: first_vertex / n_vertices: its run of
+ * host_vertices; is_hole: 0 for the outer ring of its component; label; root: the smallest pixel index of its 8-connected component;
+ * crack: its smallest crack; boundary: the root of the image-0 component that holds the pixel `root`.  host_vertices: (x = column,
+ * y = row) int32 pairs, in ring order, then in the order of travel from the ring's smallest crack on.
+ * Three waits: the crack count; the ring and vertex counts; exactly the rings and vertices.  If a capacity is too small, *n_rings and
+ * *n_vertices are set, nothing else is written and EMAP_ERR_INVALID is returned (a caller tells it from a refusal by the counts).  The
+ * buffers belong to the context and grow on demand.
+ * Refused with EMAP_ERR_INVALID before anything is uploaded, launched or copied, every output untouched: a NULL params, n_rings or
+ * n_vertices, a NULL host_rings / host_vertices with a positive capacity, a negative capacity; an unknown mode; margin_size outside
+ * 0 .. EMAP_REGION_MARGIN_MAX (mode 0); side < 2 or beyond EMAP_REGION_SIDE_MAX (mode 1: EMAP_REGION_RAW_SIDE_MAX): crack indices are
+ * 32-bit; a label outside 0 .. n_labels, a negative n_labels, a mask value other than 0 and 1; NULL host_labels in mode 1, without
+ * valid resident labels (none yet, or emap_clear / emap_shift since) or with a side that is not the map's; a row-strip context. */
+enum { EMAP_REGION_MARGIN_MAX = 14, EMAP_REGION_SIDE_MAX = 7724, EMAP_REGION_RAW_SIDE_MAX = 23170 };
+typedef struct emap_region_params { int32_t mode, margin_size, reserved[2]; } emap_region_params;
+typedef struct emap_region_ring { int32_t first_vertex, n_vertices, image, is_hole, label, root, crack, boundary; } emap_region_ring;
+int emap_planar_regions(emap_ctx* ctx, const int32_t* host_labels, int32_t side, int32_t n_labels, const emap_region_params* params,
+                        emap_region_ring* host_rings, int64_t capacity_rings, int32_t* host_vertices, int64_t capacity_vertices,
+                        int64_t* n_rings, int64_t* n_vertices);
 /* ElevationMap.shift_map_xy / shift_map_z (EM/elevation_mapping.py:200-226): roll by (dx rows, dy cols) with
  * padding (0; variance plane initial_variance), planes 0 and 5 += dz -- as a rotation of the map's circular origin plus a pending
  * entry that later kernels replay: no cell is moved, only the entering band of the semantic layers is cleared.  Works on strips

@@ -74,7 +74,7 @@ def main():
     print("# s_waitcnt), LDS, vector memory, s_nop (hazard wait states the compiler inserted), s_waitcnt")
     print("# (the vgpr column of profiles/*_kernel_stats.txt is rocprofv3's VGPR_Count, which reads half of NumVgprs on this stack: k_post<32, 0> 24 there, 48 here)")
     total, spilled = 0, []
-    for src in ("emap_kernels.hip", "emap_binned.hip", "emap_semantic.hip", "emap_depth.hip", "emap_cloudmsg.hip", "emap_image_msg.hip", "emap_gridmsg.hip", "emap_plugchain.hip", "emap_pca.hip", "emap_inpaint_chain.hip", "emap_polysafe.hip", "emap_submap.hip", "emap_cloudout.hip", "emap_planeseg.hip", "emap_terrain.hip"):
+    for src in ("emap_kernels.hip", "emap_binned.hip", "emap_semantic.hip", "emap_depth.hip", "emap_cloudmsg.hip", "emap_image_msg.hip", "emap_gridmsg.hip", "emap_plugchain.hip", "emap_pca.hip", "emap_inpaint_chain.hip", "emap_polysafe.hip", "emap_submap.hip", "emap_cloudout.hip", "emap_planeseg.hip", "emap_terrain.hip", "emap_regions.hip"):
         recs = kernels_of(src)
         names = demangle([r["mangled"] for r in recs])
         print("\n## %s: %d kernel instantiations" % (src, len(recs)))
