@@ -314,7 +314,7 @@ int emap_destroy(emap_ctx* ctx) {
   hipSetDevice(ctx->device);
   if (ctx->post_pending) post_settle(ctx);      // (the stream ends with the complete frame, whoever looks at it next)
   if (ctx->stream) hipStreamSynchronize(ctx->stream);
-  hipFree(ctx->cells.hot); hipFree(ctx->cells.cold); hipFree(ctx->acc); hipFree(ctx->accr); hipFree(ctx->trav_in);
+  hipFree(ctx->cells.hot); hipFree(ctx->cells.cold); hipFree(ctx->acc); hipFree(ctx->accr); hipFree(ctx->trav_in); hipFree(ctx->trav_flag);
   hipFree(ctx->normal); hipFree(ctx->scratch); hipFree(ctx->plug_buf); hipFree(ctx->plug_cnt); hipFree(ctx->slots); hipFree(ctx->frame); hipFree(ctx->cnt_sync);
   for (int k = 0; k < 2; ++k) { hipFree(ctx->pts_dev[k]); if (ctx->pts_pin[k]) hipHostFree(ctx->pts_pin[k]); if (ctx->ev_copied[k]) hipEventDestroy(ctx->ev_copied[k]); if (ctx->ev_used[k]) hipEventDestroy(ctx->ev_used[k]); }
   hipFree(ctx->own_cloud); stage_free(&ctx->cloud_stage); stage_free(&ctx->image_stage);
@@ -805,7 +805,13 @@ static int count_impl(emap_ctx* ctx, const float R[9], const float t[3], const F
     // output from the map as it is then, so a launch that wrote less than everything leaves the pass OWED (post_pending stays set), and a
     // frame that reads nothing launches the plain histogram and leaves it owed as well.  EMAP_POST_LEAN=0 (read per frame: A/B knob and
     // test hook): the full pass, as before.
-    bool hist_done = false;
+    // Without a visibility pass the ONE reader of the pass taken along is drift_inlier in this frame's k_tile_count, and all it asks is
+    // whether traversability is above traversability_inlier: POST_OUT_TRAV writes that predicate as a byte per cell into the flag plane
+    // (ctx->trav_flag) and no word into the hot half, and k_tile_count is launched in the form that reads the plane -- exactly then;
+    // every other launch of it (a FULL or TRAV_NORMALS pass, a settled or staged frame, emap_count) reads the word, which a full pass
+    // has written by then.  The word stays stale from the lean launch to the next full pass, as traversability_input and the normals
+    // already did: the invariant at post_settle covers it.  EMAP_POST_FLAGS=0 (read per frame: A/B knob and test hook): the word store.
+    bool hist_done = false, flags_written = false;
     if (ctx->post_pending) {
       const bool along = f && !tm && !own && ctx->kp.mv.n == 0;
       const bool rays_on = ctx->prm.enable_visibility_cleanup != 0;
@@ -814,19 +820,30 @@ static int count_impl(emap_ctx* ctx, const float R[9], const float t[3], const F
         out = rays_on ? POST_OUT_TRAV_NORMALS : POST_OUT_TRAV;
         if (const char* e = getenv("EMAP_POST_LEAN")) { if (atoi(e) == 0) out = POST_OUT_FULL; }
       }
-      if (along && out == POST_OUT_TRAV && !gate_possible) ctx->post_took = 32;      // nothing of the pass is read: no stencil workgroup is launched
+      const bool trav_only = out == POST_OUT_TRAV;
+      if (along && trav_only && !gate_possible) ctx->post_took = 32;      // nothing of the pass is read: no stencil workgroup is launched
       else {
+        if (trav_only) {
+          if (const char* e = getenv("EMAP_POST_FLAGS")) { if (atoi(e) == 0) out = POST_OUT_TRAV_WORD; }
+          if (out == POST_OUT_TRAV && !ctx->trav_flag) {      // the first lean launch of this context: every byte "the word you hold"
+            unsigned char* pl = nullptr;
+            CK(hipMalloc((void**)&pl, (size_t)ctx->ncells_alloc));
+            if (hipMemsetAsync(pl, TRAV_FLAG_WORD, (size_t)ctx->ncells_alloc, ctx->stream) != hipSuccess) { hipFree(pl); ctx->err = "hipMemsetAsync(trav_flag)"; return EMAP_ERR_HIP; }
+            ctx->trav_flag = pl;
+          }
+        }
         if (along) {
           long max_wg = 0;
           if (const char* e = getenv("EMAP_POST_FUSE_MAX_WG")) max_wg = atol(e);
           hist_done = launch_post_hist(ctx->stream, ctx->device, ctx->kp, ctx->prm.w1, ctx->prm.w2, ctx->prm.w3, ctx->prm.w_out, ctx->cells, ctx->trav_in, ctx->normal,
-                                       ctx->ncells_alloc, ctx->prm.dilation_size, pose, ctx->bg, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->bin_hist, max_wg, out);
+                                       ctx->ncells_alloc, ctx->prm.dilation_size, pose, ctx->bg, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->bin_hist, max_wg, out, ctx->trav_flag);
         }
         if (hist_done) {
           ++ctx->post_fused;
+          flags_written = out == POST_OUT_TRAV;
           if (out == POST_OUT_FULL) ctx->post_pending = false; else ctx->post_took = 16;
           // outputs carry the current origin (post_part_impl) -- the planes that were written
-          if (out != POST_OUT_TRAV) { ctx->kp.norg_r = ctx->kp.org_r; ctx->kp.norg_c = ctx->kp.org_c; }
+          if (!trav_only) { ctx->kp.norg_r = ctx->kp.org_r; ctx->kp.norg_c = ctx->kp.org_c; }
           if (out == POST_OUT_FULL) { ctx->torg_r = ctx->kp.org_r; ctx->torg_c = ctx->kp.org_c; }
         } else if ((rc = post_settle(ctx))) return rc;
       }
@@ -866,7 +883,8 @@ static int count_impl(emap_ctx* ctx, const float R[9], const float t[3], const F
     launch_bin_scatter(ctx->stream, ctx->kp, pose, ctx->bg, ctx->cloud.pts, ctx->cloud.n, ctx->cloud.stride, ctx->bin_hist, ctx->bin_tile_start, ctx->bin_recs, own, ctx->bin_own_cnt,
                        ctx->cloud.chan, ctx->carry);
     if (tm) CK(hipEventRecord(ctx->ev[ST_GATE], ctx->stream));        // the "gate" stage = per-tile error sums + k_gate
-    if (gate_possible) launch_tile_count(ctx->stream, ctx->kp, ctx->bg, ctx->bin_recs, ctx->bin_rs, ctx->bin_tile_start, ctx->cells, ctx->slots, ctx->split, ctx->cloud.n);
+    if (gate_possible) launch_tile_count(ctx->stream, ctx->kp, ctx->bg, ctx->bin_recs, ctx->bin_rs, ctx->bin_tile_start, ctx->cells, ctx->slots, ctx->split, ctx->cloud.n,
+                                         flags_written ? ctx->trav_flag : nullptr);
   } else {
     { const int rc = post_settle(ctx); if (rc) return rc; }
     ctx->carry.on = 0;

@@ -346,6 +346,13 @@ __device__ __forceinline__ bool tile_work(const BinGeo& G, const SplitView& SV, 
 __device__ __forceinline__ bool drift_inlier(const KP& P, const float4 m, float z) {
   return m.z > 0.5f && (double)fabsf(m.x - z) < (double)m.y * P.mt && (double)m.y < P.dcvi_half && (double)m.w > P.trav_inlier;
 }
+// ... with the traversability condition as a byte of the flag plane (TRAV_FLAG_*, emap_launch.h): the predicate the stencil pass this
+// frame took along evaluated on the value it did not store (POST_CELL, POST_OUT_TRAV), or "the word you hold" for the cells that pass
+// does not decide.  The other three conditions are the ones above.
+__device__ __forceinline__ bool drift_inlier(const KP& P, const float4 m, float z, unsigned int flag) {
+  const bool trav = flag == TRAV_FLAG_WORD ? (double)m.w > P.trav_inlier : flag != TRAV_FLAG_BELOW;
+  return m.z > 0.5f && (double)fabsf(m.x - z) < (double)m.y * P.mt && (double)m.y < P.dcvi_half && trav;
+}
 
 #define TF_BLOCK 1024   /* threads per tile of the tile kernels */
 #ifndef SPLIT_U
@@ -374,11 +381,16 @@ __device__ __forceinline__ void stage_hot_tile(const KP& P, Cells cells, float4*
 // the tile is tested against its cell there -- the per-point gather of a random 32-byte cell (a whole 128-byte line per point,
 // 144 MB fetched for 48 MB needed, profiles/r01f_pmc_cfg2.json) is gone.  Wave-reduced sums go to the 256 padded slots.
 // RS: stride of the sorted records in 16-byte units (2: BinRec32 of a frame that carries its channels; only the leading 16 bytes are read here)
-template <bool SPLIT, int RS>
+// FLAGS: the traversability condition comes from the flag plane `tflag` (one byte per cell, indexed as cells.hot: what this frame's
+// k_post_hist wrote with POST_OUT_TRAV) and not from the word in the hot half, which that launch left stale.  The tile's 16 x 64 bytes
+// are requested in front of the staging, as the first records are, and go to LDS beside the cells: no dependent trip is added.
+template <bool SPLIT, int RS, bool FLAGS>
 __device__ __forceinline__ void tile_count_body(const KP& P, const BinGeo& G, const BinRec* __restrict__ recs, Cells cells,
-                                                ErrSlot* __restrict__ slots, const SplitView& SV, const TileWork& w) {
+                                                ErrSlot* __restrict__ slots, const SplitView& SV, const TileWork& w,
+                                                const unsigned char* __restrict__ tflag) {
   constexpr int NC = BIN_TR * BIN_TC;
   __shared__ float4 s_cell[NC];
+  __shared__ unsigned char s_flag[FLAGS ? NC : 1];
   __shared__ unsigned int s_pts[NC], s_inl[NC];             // parts of a heavy tile only: per-cell counts for k_tile_fuse
   const int t = w.t, sb = w.sb;
   const int ty = t / G.tiles_x, tx = t - ty * G.tiles_x;
@@ -395,7 +407,13 @@ __device__ __forceinline__ void tile_count_body(const KP& P, const BinGeo& G, co
   BinRec rr[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) { const unsigned int k = r0 + u * TF_BLOCK + threadIdx.x; if (k < r1) rr[u] = recs[(size_t)k * RS]; }
+  unsigned char fl = TRAV_FLAG_WORD;                                 // (a cell beyond the map / strip: staged as zero, never an inlier)
+  if (FLAGS) {                                                       // the thread's cell of the tile, as stage_hot_tile addresses it
+    const int lrow = row_base + (int)(threadIdx.x >> 6), col = tx * BIN_TC + (int)(threadIdx.x & 63);
+    if (lrow < P.nrows && col < P.C) fl = tflag[(long)(lrow + P.halo) * P.C + col];
+  }
   stage_hot_tile(P, cells, s_cell, row_base, tx);
+  if (FLAGS) s_flag[threadIdx.x] = fl;
   if (split) { s_pts[threadIdx.x] = 0u; s_inl[threadIdx.x] = 0u; }
   __syncthreads();
   const unsigned int sel = (unsigned int)sb;
@@ -413,7 +431,7 @@ __device__ __forceinline__ void tile_count_body(const KP& P, const BinGeo& G, co
         const unsigned int lcb = r.lc_inl & 0x7fffffffu;
         if ((lcb >> 10) == sel) {
           const float4 m = s_cell[lcb & 1023u];
-          if (drift_inlier(P, m, r.z)) { inl = true; e_fix += __double2ll_rn((double)(r.z - m.x) * EM_SCALE_E); }
+          if (FLAGS ? drift_inlier(P, m, r.z, (unsigned int)s_flag[lcb & 1023u]) : drift_inlier(P, m, r.z)) { inl = true; e_fix += __double2ll_rn((double)(r.z - m.x) * EM_SCALE_E); }
           if (split) { atomicAdd(&s_pts[lcb & 1023u], 1u); if (inl) atomicAdd(&s_inl[lcb & 1023u], 1u); }
         }
       }
@@ -440,7 +458,16 @@ __global__ __launch_bounds__(TF_BLOCK) void k_tile_count(KP P, BinGeo G, const B
                                                           const unsigned int* __restrict__ tile_start, Cells cells,
                                                           ErrSlot* __restrict__ slots, SplitView SV) {
   TileWork w;
-  if (tile_work<SPLIT>(G, SV, tile_start, w)) tile_count_body<SPLIT, RS>(P, G, recs, cells, slots, SV, w);
+  if (tile_work<SPLIT>(G, SV, tile_start, w)) tile_count_body<SPLIT, RS, false>(P, G, recs, cells, slots, SV, w, nullptr);
+}
+// The same kernel with the traversability condition read from the flag plane (tile_count_body, FLAGS): the frames whose k_post_hist
+// launch wrote it (count_impl).  A kernel of its own name: the instantiations above stay what they were.
+template <bool SPLIT, int RS>
+__global__ __launch_bounds__(TF_BLOCK) void k_tile_count_flags(KP P, BinGeo G, const BinRec* __restrict__ recs,
+                                                                const unsigned int* __restrict__ tile_start, Cells cells,
+                                                                ErrSlot* __restrict__ slots, SplitView SV, const unsigned char* __restrict__ tflag) {
+  TileWork w;
+  if (tile_work<SPLIT>(G, SV, tile_start, w)) tile_count_body<SPLIT, RS, true>(P, G, recs, cells, slots, SV, w, tflag);
 }
 
 // AVG = true (whole frames, emap_update): the epilogue commits AND averages the tile in registers and writes the 32-byte cells
@@ -812,11 +839,16 @@ void launch_bin_scatter(hipStream_t s, const KP& P, const Pose& T, const BinGeo&
   }
 }
 void launch_tile_count(hipStream_t s, const KP& P, const BinGeo& G, const BinRec* recs, int rs, const unsigned int* tile_start, Cells cells,
-                       ErrSlot* slots, const SplitView& SV, long n) {
+                       ErrSlot* slots, const SplitView& SV, long n, const unsigned char* trav_flag) {
   static_assert(TF_BLOCK == BIN_TR * BIN_TC, "one thread per cell of a tile");
   (void)n;
   const bool split = SV.on && SV.cap > 0;
   const dim3 g((split ? (unsigned int)SV.cap * G.sub : 0u) + tile_grid(G)), b(TF_BLOCK);
+  if (trav_flag) {      // this frame's k_post_hist wrote the flag plane and left the traversability word stale
+    if (split) { if (rs == 2) hipLaunchKernelGGL((k_tile_count_flags<true, 2>), g, b, 0, s, P, G, recs, tile_start, cells, slots, SV, trav_flag); else hipLaunchKernelGGL((k_tile_count_flags<true, 1>), g, b, 0, s, P, G, recs, tile_start, cells, slots, SV, trav_flag); }
+    else { if (rs == 2) hipLaunchKernelGGL((k_tile_count_flags<false, 2>), g, b, 0, s, P, G, recs, tile_start, cells, slots, SV, trav_flag); else hipLaunchKernelGGL((k_tile_count_flags<false, 1>), g, b, 0, s, P, G, recs, tile_start, cells, slots, SV, trav_flag); }
+    return;
+  }
   if (split) { if (rs == 2) hipLaunchKernelGGL((k_tile_count<true, 2>), g, b, 0, s, P, G, recs, tile_start, cells, slots, SV); else hipLaunchKernelGGL((k_tile_count<true, 1>), g, b, 0, s, P, G, recs, tile_start, cells, slots, SV); }
   else { if (rs == 2) hipLaunchKernelGGL((k_tile_count<false, 2>), g, b, 0, s, P, G, recs, tile_start, cells, slots, SV); else hipLaunchKernelGGL((k_tile_count<false, 1>), g, b, 0, s, P, G, recs, tile_start, cells, slots, SV); }
 }

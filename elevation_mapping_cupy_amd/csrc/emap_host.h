@@ -149,6 +149,10 @@ struct emap_ctx {
   bool post_pending;
   int post_took;                   // this frame and the pending pass, as bits of update_path: 16 taken along lean, 32 left owed without a launch
   unsigned int post_fused;         // fused launches since creation (emap_post_fused_launches)
+  // The flag plane: one byte per cell in the storage order of cells.hot (ncells_alloc bytes, TRAV_FLAG_*), made the first time a pass goes
+  // along with POST_OUT_TRAV.  It lives from that k_post_hist launch to the k_tile_count of the same frame (count_impl) and means nothing
+  // outside it: every other reader of traversability takes the word in the hot half, behind a full pass.
+  unsigned char* trav_flag;
   BinGeo bg; BinRec* bin_recs; size_t bin_recs_cap; bool bin_strip;
   float4* bin_own; size_t bin_own_cap; unsigned int* bin_own_cnt;   // staged 16-byte records (BinStg: emap_binned.hip) of the owned points per block (strip contexts without a visibility pass); bin_own_cnt: BIN_MAX_B words, sized once
   unsigned int* bin_hist; size_t bin_hist_cap; unsigned int* bin_tile_total; unsigned int* bin_tile_start;

@@ -1102,7 +1102,13 @@ __device__ __forceinline__ float exp_neg(float a) {
 // along in its histogram launch (k_post_hist) writes what THAT frame reads -- traversability (its drift statistics), the normals too
 // when it runs a visibility pass -- and stays owed: a full pass rewrites every output before anything else can look (post_settle,
 // emap_api.hip).  POST_OUT_TRAV drops the store of traversability_input, the normal epilogue (five IEEE divisions, the square root)
-// and its three stores.  (The values: emap_launch.h.)
+// and its three stores -- and the traversability WORD: in that frame the value has one reader, the drift gate's predicate
+// (double)trav > traversability_inlier (drift_inlier, emap_binned.hip), and a 4-byte store at stride 16 dirties every line of the hot
+// array (17.6 MB written back for 4 MB of payload at 1024^2) to carry one bit per cell.  The predicate goes as ONE BYTE into the flag
+// plane `tflag` (a constant of the expanding kernel as OUT is: null where OUT never selects it), indexed as cells.hot is; a cell the
+// stencils do not decide (do_trav false: the 3-cell border) gets TRAV_FLAG_WORD, "the word you hold".  hot.w is not written and stays
+// stale until the next full pass (post_settle has the invariant).  POST_OUT_TRAV_WORD: the same set with the word store
+// (EMAP_POST_FLAGS=0).  (The values: emap_launch.h.)
 #define POST_CELL(WT, ES, t0, dp, own_valid, do_trav, do_normal, c)                                                         \
   do {                                                                                                                    \
     typedef float v2f __attribute__((ext_vector_type(2)));                                                               \
@@ -1127,9 +1133,11 @@ __device__ __forceinline__ float exp_neg(float a) {
         acc = fmaf((WT).wo[q][2], fabsf(s23.x), acc);                                                                       \
         acc = fmaf((WT).wo[q][3], fabsf(s23.y), acc);                                                                       \
       }                                                                                                                   \
-      cells.hot[c].w = exp_neg(acc);                  /* trav: a 4-byte store into the 16-byte hot half */                \
-    }                                                                                                                     \
-    if (OUT == POST_OUT_TRAV) break;                                                                                      \
+      const float tv = exp_neg(acc);                                                                                      \
+      if (OUT == POST_OUT_TRAV) tflag[c] = (double)tv > P.trav_inlier ? TRAV_FLAG_ABOVE : TRAV_FLAG_BELOW;   /* the one reader's predicate (drift_inlier), one byte */ \
+      else cells.hot[c].w = tv;                       /* trav: a 4-byte store into the 16-byte hot half */                \
+    } else if (OUT == POST_OUT_TRAV) tflag[c] = TRAV_FLAG_WORD;           /* border: the word the hot half holds */      \
+    if (OUT == POST_OUT_TRAV || OUT == POST_OUT_TRAV_WORD) break;                                                         \
     float nx = 0.f, ny = 0.f, nz = 0.f;                                                                                   \
     if ((do_normal) && (own_valid) > 0.5f) {                              /* (is_valid of the cell itself) */             \
       const float dzdx = (t0)[ES] - h, dzdy = (t0)[(ES) * (dp)] - h;                                                      \
@@ -1248,6 +1256,7 @@ template <int PT_R, int STAGE>
 __global__ __launch_bounds__(512) void k_post_dma(KP P, TravW Wt, Cells cells, float* __restrict__ trav_in,
                                                   float* __restrict__ normal, long plane_stride, int d, PostSegs S) {
   constexpr int OUT = POST_OUT_FULL;
+  constexpr unsigned char* tflag = nullptr;      // (POST_CELL: the full pass writes no flag plane)
   int seg_b = S.b[0], seg_e = S.e[0], ty = blockIdx.y;
 #pragma unroll
   for (int k = 1; k < 4; ++k) if (k < S.n && (int)blockIdx.y >= S.t0[k]) { seg_b = S.b[k]; seg_e = S.e[k]; ty = blockIdx.y - S.t0[k]; }
@@ -1365,6 +1374,7 @@ template <int PT_R, int STAGE>
 __global__ __launch_bounds__(PT_R >= 32 ? POST_T32 : 512) void k_post(KP P, TravW Wt, Cells cells, float* __restrict__ trav_in,
                                                     float* __restrict__ normal, long plane_stride, int d, PostSegs S) {
   constexpr int OUT = POST_OUT_FULL;
+  constexpr unsigned char* tflag = nullptr;      // (POST_CELL: the full pass writes no flag plane)
 #define POST_BX blockIdx.x
 #define POST_BY blockIdx.y
 #include "emap_post_tile.h"
@@ -1381,7 +1391,8 @@ __global__ __launch_bounds__(PT_R >= 32 ? POST_T32 : 512) void k_post(KP P, Trav
 // hist0 a multiple of 8: workgroup b runs on XCD b % 8, so the histogram workgroup of a chunk then sits on the XCD of its twin in
 // k_bin_scatter (bin_chunk_of_block), as it does in k_bin_hist.  That placement is for speed only; nothing depends on it for the result.
 // The tiles stand in front of the histogram workgroups (hist0 = n_tiles rounded up to 8); the other order was measured
-// (EMAP_POST_HIST_FRONT).  Stage 0, one row interval, 512 threads.  OUT: the output set of the stencil tiles (POST_CELL).
+// (EMAP_POST_HIST_FRONT).  Stage 0, one row interval, 512 threads.  OUT: the output set of the stencil tiles (POST_CELL);
+// tflag: the flag plane POST_OUT_TRAV writes (one byte per cell of cells.hot; not looked at by the other sets).
 #ifndef POST_HIST_U
 #define POST_HIST_U 4      /* loads in flight per thread of a histogram workgroup: two batches of 4; one batch of 8 was measured slower */
 #endif
@@ -1389,7 +1400,7 @@ template <int MODE, int PT_R, int OUT>
 __global__ __launch_bounds__(512) void k_post_hist(KP P, TravW Wt, Cells cells, float* __restrict__ trav_in, float* __restrict__ normal,
                                                    long plane_stride, int d, PostSegs S, int tiles_x, int n_tiles, int tile0, int hist0,
                                                    Pose T, BinGeo G, const float* __restrict__ pts, long n, int stride,
-                                                   unsigned int* __restrict__ hist) {
+                                                   unsigned int* __restrict__ hist, unsigned char* __restrict__ tflag) {
   static_assert(PT_R < 32 || POST_T32 == 512, "k_post_hist runs both bodies with 512 threads");
   const int b = (int)blockIdx.x;                               // (uniform)
   if ((unsigned int)(b - tile0) < (unsigned int)n_tiles) {
@@ -1812,9 +1823,9 @@ template <auto KERN> static long post_hist_resident(size_t lds, int dev) {
 // the caller runs the two launches.  out: the output set of the stencil tiles (POST_OUT_*); anything but POST_OUT_FULL leaves the pass owed.
 bool launch_post_hist(hipStream_t s, int dev, const KP& P, const float* w1, const float* w2, const float* w3, const float* wo, Cells cells,
                       float* trav_in, float* normal, long plane_stride, int d, const Pose& T, const BinGeo& G, const float* pts, long n, int stride,
-                      unsigned int* hist, long max_wg, int out) {
+                      unsigned int* hist, long max_wg, int out, unsigned char* tflag) {
   const int R = post_hist_tile_rows(P, d);
-  if (!R) return false;
+  if (!R || (out == POST_OUT_TRAV && !tflag)) return false;
   const TravW W = post_weights(w1, w2, w3, wo);
   PostSegs S; memset(&S, 0, sizeof S);
   S.emagic = post_emagic(d);
@@ -1833,8 +1844,9 @@ bool launch_post_hist(hipStream_t s, int dev, const KP& P, const float* w1, cons
     const long room = post_hist_resident<k_post_hist<MODE, RR, OO>>(lds, dev); \
     if (grid > (max_wg > 0 && max_wg < room ? max_wg : room)) break; \
     hipLaunchKernelGGL(kern, dim3((unsigned int)grid), dim3(512), lds, s, P, W, cells, trav_in, normal, plane_stride, d, S, tiles_x, n_tiles, tile0, hist0, \
-                       T, G, pts, n, stride, hist); ok = true; } while (0)
+                       T, G, pts, n, stride, hist, tflag); ok = true; } while (0)
 #define POST_HIST_OUT(MODE, RR) do { if (out == POST_OUT_TRAV) POST_HIST_GO(MODE, RR, POST_OUT_TRAV); \
+    else if (out == POST_OUT_TRAV_WORD) POST_HIST_GO(MODE, RR, POST_OUT_TRAV_WORD); \
     else if (out == POST_OUT_TRAV_NORMALS) POST_HIST_GO(MODE, RR, POST_OUT_TRAV_NORMALS); else POST_HIST_GO(MODE, RR, POST_OUT_FULL); } while (0)
   if (P.mode == 0) { if (R == 32) POST_HIST_OUT(0, 32); else POST_HIST_OUT(0, 16); }
   else { if (R == 32) POST_HIST_OUT(1, 32); else POST_HIST_OUT(1, 16); }

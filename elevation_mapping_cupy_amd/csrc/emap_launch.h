@@ -75,10 +75,15 @@ void launch_var_time(hipStream_t, const KP&, Cells, int, int);
 int post_tile_rows(const KP&);
 void launch_post(hipStream_t, const KP&, const float*, const float*, const float*, const float*, Cells, float*, float*, long, int, int, const int*, const int*, int, int);
 int post_hist_tile_rows(const KP&, int);
-// output set of the stencil pass a frame takes along (POST_CELL, emap_kernels.hip): everything | no traversability_input | traversability only
-enum { POST_OUT_FULL = 0, POST_OUT_TRAV_NORMALS = 1, POST_OUT_TRAV = 2 };
+// output set of the stencil pass a frame takes along (POST_CELL, emap_kernels.hip): everything | no traversability_input | traversability
+// only, as the drift gate's predicate in the flag plane (TRAV_FLAG_*, one byte per cell; the last pointer) | traversability only, as the
+// word in the hot half (EMAP_POST_FLAGS=0)
+enum { POST_OUT_FULL = 0, POST_OUT_TRAV_NORMALS = 1, POST_OUT_TRAV = 2, POST_OUT_TRAV_WORD = 3 };
+// A byte of the flag plane: the cell's traversability is not / is above traversability_inlier, or the stencil pass does not decide the
+// cell (the 3-cell border) and the word in the hot half holds.
+enum { TRAV_FLAG_BELOW = 0, TRAV_FLAG_ABOVE = 1, TRAV_FLAG_WORD = 2 };
 bool launch_post_hist(hipStream_t, int, const KP&, const float*, const float*, const float*, const float*, Cells, float*, float*, long, int,
-                      const Pose&, const BinGeo&, const float*, long, int, unsigned int*, long, int);
+                      const Pose&, const BinGeo&, const float*, long, int, unsigned int*, long, int, unsigned char*);
 void launch_get_plane(hipStream_t, const KP&, Cells, int, float*);
 void launch_publish(hipStream_t, const KP&, Cells, const float*, long, int, float, int, float*);
 void launch_set_plane(hipStream_t, const KP&, Cells, int, const float*);
@@ -109,7 +114,8 @@ void launch_erode(hipStream_t, int, int, const float*, float*);
 void launch_bin_hist(hipStream_t, const KP&, const Pose&, const BinGeo&, const float*, long, int, unsigned int*, BinStg*, unsigned int*);
 void launch_bin_scan(hipStream_t, const BinGeo&, unsigned int*, unsigned int*, unsigned int*, unsigned int*, const SplitView&);
 void launch_bin_scatter(hipStream_t, const KP&, const Pose&, const BinGeo&, const float*, long, int, const unsigned int*, const unsigned int*, BinRec*, const BinStg*, const unsigned int*, const ChanView&, const SemCarry&);
-void launch_tile_count(hipStream_t, const KP&, const BinGeo&, const BinRec*, int, const unsigned int*, Cells, ErrSlot*, const SplitView&, long);
+void launch_tile_count(hipStream_t, const KP&, const BinGeo&, const BinRec*, int, const unsigned int*, Cells, ErrSlot*, const SplitView&, long,
+                       const unsigned char* trav_flag);      // trav_flag: the flag plane this frame's k_post_hist wrote (POST_OUT_TRAV), or nullptr: traversability is the word in the hot half
 void launch_tile_semantic(hipStream_t, const KP&, const BinGeo&, const SemSpec&, const BinRec*, int, int, const unsigned int*, const ChanView&, long,
                           const unsigned int*, float*, float*, long, const SplitView&, void*, int);
 size_t sem_split_bytes(int);
